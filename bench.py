@@ -30,6 +30,8 @@ The JSON line carries, next to the contract's fields:
   join_b                Join B (k_lines_exists over a 3.4 M-line table) with the device-built region tables
   depth                 `gffx depth`'s kernel (k_depth_regions) on the same regions against a 3.4 M-line table
   cpu_baseline          the oracle's Join A on 1 thread (the reference is serial there), + all cores, + Join B on all cores
+  dump_outputs          with --dump-outputs DIR: the results of the timed region's last pass, written as DIR/*.npy (counts, root_fids
+                        per region; the inputs are seeded, so two builds run with the same arguments can be compared file for file)
 
 For N>1 (launched by torch.distributed.run, one rank per GPU) --scaling weak (default) gives every rank 1 M regions of an
 N x 1 M batch sharded by chromosome bucket (gffx_amd.shard, LPT with splitting; index replicated); --scaling strong shards
@@ -97,7 +99,15 @@ def parse_args():
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed pass computed in its last step as DIR/<name>.npy (float64, "
+                         "at most 64 MB in all; see dump_outputs)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.passes_per_step < 1:
+        ap.error("--steps and --passes-per-step must be at least 1")
+    if a.dump_outputs and a.out != "counts" and a.strategy != "direct" and a.offsets == "none":
+        ap.error("--dump-outputs needs the segment starts of the pairs: --offsets seg, u32 or u64")
+    return a
 
 
 def rank_placement(env, n_devices):
@@ -232,6 +242,7 @@ class Pass:
         arr = (ctypes.c_void_p * len(self.batches))(*[bb._h for bb in self.batches])
         self.engine.check(self.engine.lib().gffx_hip_batches_run_n(arr, len(self.batches), self.mode, 0, self.flags, self.strategy,
                                                                    n_passes))
+        self.last = self.batches[(n_passes - 1) % len(self.batches)]  # (pass i runs on batches[i % len]: the batch of the last pass)
 
     def sync(self):
         for bb in self.batches:
@@ -387,6 +398,61 @@ def measure_traffic(args, block_threads=None, blocks=None, group=1):
 def to_dev(torch, regions, dev):
     t = torch.from_numpy(np.ascontiguousarray(regions).view(np.int32))  # u32 bit patterns
     return tuple(t[:, k].contiguous().to(dev) for k in range(3))
+
+
+DUMP_BYTES = 64_000_000  # --dump-outputs: all files of a run together, .npy headers included
+DUMP_SEED = 2024
+
+
+def pass_results(engine, bb, out_flags):
+    """What a caller of the pass receives from batch bb: (counts in input order, every region's segment start in the pair buffer,
+    the pairs: root_fids or (root_fid, start, end) triples; None, None for a counts-only pass)."""
+    counts = bb.counts()
+    if not out_flags & (engine.OUT_FIDS | engine.OUT_TRIPLES):
+        return counts, None, None
+    pairs = bb.triples() if out_flags & engine.OUT_TRIPLES else bb.fids()
+    if out_flags & engine.OUT_SEGBASE:
+        starts = bb.offsets_from_segbase(counts)
+    elif out_flags & engine.OUT_OFFSETS32:
+        starts = bb.offsets32()
+    elif out_flags & engine.OUT_OFFSETS:
+        starts = bb.offsets()[:-1]
+    else:  # the direct strategy: CSR in input order
+        starts = np.cumsum(counts, dtype=np.uint64) - counts
+    return counts, starts, pairs
+
+
+def dump_outputs(directory, counts, starts, pairs, budget=DUMP_BYTES, seed=DUMP_SEED, suffix=""):
+    """--dump-outputs: a pass's results as float64 .npy files that two builds can compare entry for entry.
+      rows     the input rows the other files describe, ascending: all of them, or -- when the whole would take more than `budget`
+               bytes -- the regions of a fixed permutation (seeded with `seed`) up to the budget
+      counts   kept pairs of each of these rows
+      fids / triples (not for a counts-only pass)  the pairs of these rows, row after row, each row's own pairs sorted: the engine's
+               contract is the multiset of pairs per region -- where the segments lie in the pair buffer and the order inside one
+               change from run to run (include/gffx_hip.h, "Output order")
+    Returns {file name: shape}."""
+    c = counts.astype(np.int64)
+    width = 0 if pairs is None else (1 if pairs.ndim == 1 else pairs.shape[1])
+    cost = 16 + 8 * width * c  # bytes per row: its row number, its count, its pairs
+    budget -= 3 * 256  # (the .npy headers)
+    if int(cost.sum()) <= budget:
+        rows = np.arange(len(c))
+    else:
+        perm = np.random.default_rng(seed).permutation(len(c))
+        rows = np.sort(perm[: int(np.searchsorted(np.cumsum(cost[perm]), budget, side="right"))])
+    out = {"rows": rows, "counts": c[rows]}
+    if pairs is not None:
+        cr = c[rows]
+        first = np.cumsum(cr) - cr
+        idx = np.arange(int(cr.sum()), dtype=np.int64) + np.repeat(starts[rows].astype(np.int64) - first, cr)
+        p = pairs[idx].reshape(len(idx), width)
+        rid = np.repeat(np.arange(len(rows)), cr)
+        p = p[np.lexsort(tuple(p[:, k] for k in reversed(range(width))) + (rid,))]
+        out["fids" if width == 1 else "triples"] = p[:, 0] if width == 1 else p
+    os.makedirs(directory, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + suffix + ".npy"), a.astype(np.float64))
+    return {name + suffix: list(a.shape) for name, a in out.items()}
 
 
 def xfer_leg(engine, torch, ix, regions, mode, pairs, reps=8):
@@ -672,6 +738,10 @@ def main():
     elapsed = float(np.median(all_elapsed))
     barrier()
     run.check(pairs)
+    dumped = None
+    if args.dump_outputs:  # (before any other leg runs a batch of the timed region again)
+        dumped = dump_outputs(args.dump_outputs, *pass_results(engine, run.last, out_flags), budget=DUMP_BYTES // world,
+                              suffix="" if world == 1 else "_rank%d" % rank)
     exchange_ms = None
     if world > 1:
         tx = time.perf_counter()
@@ -783,6 +853,10 @@ def main():
                                      run.pass_us_one_event_pair, timed_threads, timed_blocks),
             "group_launch": group_launch,
         }
+        if dumped is not None:
+            result["dump_outputs"] = {"dir": args.dump_outputs, "files": dumped,
+                                      "note": "the results of the timed region's last pass; N > 1: every rank writes its shard's "
+                                              "<name>_rank<r>.npy (files: rank 0's)"}
     if world == 1:
         # ---- strictly serial passes (one batch, one stream): what the committed rocprofv3 kernel stats show
         ser = Pass(engine, ix, cols, nq, 1, mode, out_flags, strategy)

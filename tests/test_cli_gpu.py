@@ -5,6 +5,7 @@ import json
 import os
 import shutil
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -185,21 +186,31 @@ def test_multi_gpu_cli_is_byte_identical_and_streams_in_chunks(tmp_path):
             assert open(out, "rb").read() == open(want, "rb").read(), (flags, n)
 
 
+RCCL_CHILD = r'''
+import ctypes as C, sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+from gffx_amd import _ffi
+
+L = _ffi.lib()
+devs = (C.c_int * 1)(0)
+cin = np.array([123456789, 987654321], dtype=np.uint64)
+cout = np.zeros(2, dtype=np.uint64)
+_ffi.check(L.gffx_hip_allgather_counts(1, devs, cin.ctypes.data_as(_ffi.u64p), cout.ctypes.data_as(_ffi.u64p)))
+assert np.array_equal(cin, cout)
+two = (C.c_int * 2)(0, 0)
+assert L.gffx_hip_allgather_counts(2, two, cin.ctypes.data_as(_ffi.u64p), cout.ctypes.data_as(_ffi.u64p)) != 0  # same device twice
+print("ok")
+'''
+
+
 def test_rccl_allgather_of_hit_counts_through_the_c_abi():
     """gffx_hip_allgather_counts: ncclCommInitAll + ncclAllGather (librccl, loaded on first use); on a 1-GPU box the
-    communicator has one rank."""
-    import ctypes as C
-
-    from gffx_amd import _ffi
-
-    L = _ffi.lib()
-    devs = (C.c_int * 1)(0)
-    cin = np.array([123456789, 987654321], dtype=np.uint64)
-    cout = np.zeros(2, dtype=np.uint64)
-    _ffi.check(L.gffx_hip_allgather_counts(1, devs, cin.ctypes.data_as(_ffi.u64p), cout.ctypes.data_as(_ffi.u64p)))
-    assert np.array_equal(cin, cout)
-    two = (C.c_int * 2)(0, 0)
-    assert L.gffx_hip_allgather_counts(2, two, cin.ctypes.data_as(_ffi.u64p), cout.ctypes.data_as(_ffi.u64p)) != 0  # same device twice
+    communicator has one rank.  In a fresh process: librccl stays loaded (RTLD_GLOBAL) until the process ends, and the
+    pytest process also loads torch, which brings its own RCCL and HIP runtime -- the whole suite in one process aborted at
+    exit (double free) with both in it."""
+    r = subprocess.run([sys.executable, "-c", RCCL_CHILD, ROOT], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "ok" in r.stdout.splitlines(), (r.returncode, r.stdout[-500:], r.stderr[-2000:])  # (RCCL may print a banner)
 
 
 def test_stats_json_carries_the_stage_timers_and_counts(tmp_path, golden_dir):

@@ -4,8 +4,8 @@
 # instruction mix per dispatch, separate passes, --kernel-trace only) of `tools/joinb_bench.py --quick 1000000`.
 set -u
 TAG=$1
+R=$(cd "$(dirname "$0")/.." && pwd)  # the checkout this script is in
 cd /tmp && export TMPDIR=/tmp
-R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R

@@ -4,8 +4,8 @@
 # streams overlap)
 set -u
 TAG=$1; shift
+R=$(cd "$(dirname "$0")/.." && pwd)  # the checkout this script is in
 cd /tmp && export TMPDIR=/tmp
-R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R

@@ -7,8 +7,8 @@
 set -u
 TAG=$1; shift
 ARGS="--steps 20 --warmup 3 --passes-per-step 1 --repeats 1 --no-cpu-baseline --quick --inflight 1 $*"  # serial passes: per-kernel durations without overlap
+R=$(cd "$(dirname "$0")/.." && pwd)  # the checkout this script is in
 cd /tmp && export TMPDIR=/tmp
-R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
