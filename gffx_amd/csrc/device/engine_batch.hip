@@ -462,10 +462,8 @@ static int pick_strategy(const gffx_hip_batch *b, int strategy) {
     return b->mostly_slow ? GFFX_STRATEGY_FUSED : GFFX_STRATEGY_WINDOWS;
 }
 
-// Everything of a run before its kernels: arguments, AUTO's choice of strategy and form, the output buffers.  *launch = false: the
-// run is complete without a kernel of the strategies (an empty batch).  What it enqueues goes to the batch's own stream.
-static int batch_prepare_run(gffx_hip_batch *b, int mode, int invert, uint32_t out_flags, int strategy, bool *launch) {
-    *launch = false;
+// The checks of a run that change nothing: a batch that fails one is left exactly as its last pass left it.
+static int batch_check_run(const gffx_hip_batch *b, int mode, uint32_t out_flags, int strategy) {
     if (!b) return fail(GFFX_E_INVALID, "gffx_hip_batch_run: batch is NULL");
     if (!b->have_regions) return fail(GFFX_E_STATE, "gffx_hip_batch_run: no regions set");
     if (mode < 0 || mode > 2) return fail(GFFX_E_INVALID, "gffx_hip_batch_run: bad mode %d", mode);
@@ -474,6 +472,20 @@ static int batch_prepare_run(gffx_hip_batch *b, int mode, int invert, uint32_t o
     if (strategy == GFFX_STRATEGY_SORTED && (!b->ix->partition_ok || b->max_q >= (1ull << 32)))
         return fail(GFFX_E_INVALID, "gffx_hip_batch_run: the partitioned strategy needs <= %u seqids / genome cells "
                                     "and < 2^32 queries per batch (this index has %u seqids)", kMaxCells, b->ix->n_chr);
+    if ((out_flags & GFFX_OUT_SEGBASE) && (out_flags & GFFX_OUT_TRIPLES))
+        return fail(GFFX_E_INVALID, "gffx_hip_batch_run: GFFX_OUT_SEGBASE is an output of the root_fid passes, not of GFFX_OUT_TRIPLES");
+    // (an explicit strategy other than WINDOWS stays what it is: batch_prepare_run takes the windows strategy for these flags under AUTO only)
+    if ((out_flags & (GFFX_OUT_OFFSETS32 | GFFX_OUT_BITMAP_KEEP | GFFX_OUT_SEGBASE)) && strategy != GFFX_STRATEGY_AUTO && strategy != GFFX_STRATEGY_WINDOWS)
+        return fail(GFFX_E_INVALID, "gffx_hip_batch_run: GFFX_OUT_OFFSETS32 / GFFX_OUT_BITMAP_KEEP / GFFX_OUT_SEGBASE need the windows strategy (or AUTO)");
+    return GFFX_OK;
+}
+
+// Everything of a run before its kernels: arguments, AUTO's choice of strategy and form, the output buffers.  *launch = false: the
+// run is complete without a kernel of the strategies (an empty batch).  What it enqueues goes to the batch's own stream.
+static int batch_prepare_run(gffx_hip_batch *b, int mode, int invert, uint32_t out_flags, int strategy, bool *launch) {
+    *launch = false;
+    int rc = batch_check_run(b, mode, out_flags, strategy);
+    if (rc) return rc;
     GFFX_HIP_TRY(hipSetDevice(b->ix->device));
     b->mode = mode;
     b->invert = invert ? 1 : 0;
@@ -501,13 +513,8 @@ static int batch_prepare_run(gffx_hip_batch *b, int mode, int invert, uint32_t o
     // would be missing from gffx_hip_batch_kept_pairs_accumulated (the sweep kernel does not feed the per-block sums; round 5's advisor)
     if (waive && strategy == GFFX_STRATEGY_AUTO) b->strategy = GFFX_STRATEGY_WINDOWS;
     if (waive && b->strategy != GFFX_STRATEGY_WINDOWS) b->flags = (b->flags & ~(uint32_t)GFFX_OUT_NO_COUNTS) | GFFX_OUT_COUNTS;
-    if ((out_flags & GFFX_OUT_SEGBASE) && (out_flags & GFFX_OUT_TRIPLES))
-        return fail(GFFX_E_INVALID, "gffx_hip_batch_run: GFFX_OUT_SEGBASE is an output of the root_fid passes, not of GFFX_OUT_TRIPLES");
-    if ((out_flags & (GFFX_OUT_OFFSETS32 | GFFX_OUT_BITMAP_KEEP | GFFX_OUT_SEGBASE)) && b->strategy != GFFX_STRATEGY_WINDOWS) {
-        if (strategy != GFFX_STRATEGY_AUTO)
-            return fail(GFFX_E_INVALID, "gffx_hip_batch_run: GFFX_OUT_OFFSETS32 / GFFX_OUT_BITMAP_KEEP / GFFX_OUT_SEGBASE need the windows strategy (or AUTO)");
-        b->strategy = GFFX_STRATEGY_WINDOWS;  // (AUTO's sweep-kernel choice is a speed matter only)
-    }
+    if ((out_flags & (GFFX_OUT_OFFSETS32 | GFFX_OUT_BITMAP_KEEP | GFFX_OUT_SEGBASE)) && b->strategy != GFFX_STRATEGY_WINDOWS)
+        b->strategy = GFFX_STRATEGY_WINDOWS;  // (AUTO only: batch_check_run refused the others.  AUTO's sweep-kernel choice is a speed matter only)
     b->ran = true;
     b->waited = false;
     b->total = 0;
@@ -518,7 +525,6 @@ static int batch_prepare_run(gffx_hip_batch *b, int mode, int invert, uint32_t o
         b->ix->busy_batches.v.fetch_add(1, std::memory_order_relaxed);
     }
     const uint64_t nq = b->nq;
-    int rc;
     if (nq == 0 && (rc = batch_own_stream(b))) return rc;
     if (b->flags & GFFX_OUT_OFFSETS) {
         if (!b->d_offsets && (rc = dev_alloc(&b->d_offsets, b->max_q + 1))) return rc;
@@ -862,10 +868,9 @@ extern "C" int gffx_hip_batch_timed_runs(gffx_hip_batch *b, int mode, int invert
                                          double *total_ms) {
     if (!b || !total_ms || !n) return fail(GFFX_E_INVALID, "gffx_hip_batch_timed_runs: bad argument");
     GFFX_HIP_TRY(hipSetDevice(b->ix->device));
-    hipEvent_t a, z;
-    GFFX_HIP_TRY(hipEventCreate(&a));
-    GFFX_HIP_TRY(hipEventCreate(&z));
-    int rc = gffx_hip_batch_run(b, mode, invert, out_flags, strategy);  // (sizes the buffers; not timed)
+    hipEvent_t a = nullptr, z = nullptr;
+    int rc = hipEventCreate(&a) != hipSuccess || hipEventCreate(&z) != hipSuccess ? fail(GFFX_E_HIP, "gffx_hip_batch_timed_runs: hipEventCreate failed") : GFFX_OK;
+    if (!rc) rc = gffx_hip_batch_run(b, mode, invert, out_flags, strategy);  // (sizes the buffers; not timed)
     if (!rc) rc = gffx_hip_batch_sync(b);
     if (!rc) {
         (void)hipEventRecord(a, b->stream);
@@ -875,8 +880,8 @@ extern "C" int gffx_hip_batch_timed_runs(gffx_hip_batch *b, int mode, int invert
         float ms = 0.f;
         if (!rc && hipEventElapsedTime(&ms, a, z) == hipSuccess) *total_ms = ms;
     }
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(z);
+    if (a) (void)hipEventDestroy(a);
+    if (z) (void)hipEventDestroy(z);
     return rc;
 }
 
@@ -889,7 +894,14 @@ static int run_group(gffx_hip_batch *const *bs, uint32_t n, int mode, int invert
     bool all = n >= 2;
     for (uint32_t t = 0; t < n; ++t) {
         const int rc = batch_prepare_run(bs[t], mode, invert, out_flags, strategy, &launch[t]);
-        if (rc) return rc;
+        if (rc) {
+            // Members 0..t-1 are prepared (marked run, unwaited, busy, under the new mode and flags): they get their passes, one by
+            // one, so that every batch marked as run holds a real pass -- a wait on a prepared but unlaunched member would read the
+            // previous pass's status words and buffers.  Then member t's error.
+            for (uint32_t u = 0; u < t; ++u)
+                if (launch[u]) (void)batch_launch_run(bs[u]);
+            return rc;
+        }
         all = all && launch[t];
     }
     if (all && windows_groupable(bs, n)) return run_windows_group(bs, n, which_stream);
@@ -930,6 +942,13 @@ static GroupPlan plan_groups(gffx_hip_batch *const *batches, uint32_t n_batches)
 extern "C" int gffx_hip_batches_run_n(gffx_hip_batch *const *batches, uint32_t n_batches, int mode, int invert, uint32_t out_flags,
                                       int strategy, uint64_t n_passes) {
     if (!batches || !n_batches) return fail(GFFX_E_INVALID, "gffx_hip_batches_run_n: no batches");
+    // Every batch that takes a pass is checked before anything is prepared or launched: a call that fails these checks leaves every
+    // batch as its last completed pass left it (a member prepared for a group whose later member then failed would otherwise be
+    // marked run with nothing launched for it)
+    for (uint64_t i = 0; i < std::min<uint64_t>(n_passes, n_batches); ++i) {
+        const int rc = batch_check_run(batches[i], mode, out_flags, strategy);
+        if (rc) return rc;
+    }
     const GroupPlan plan = plan_groups(batches, n_batches);
     if (!plan.cycle) {
         for (uint64_t i = 0; i < n_passes; ++i) {
@@ -970,10 +989,9 @@ extern "C" int gffx_hip_batches_timed_runs(gffx_hip_batch *const *batches, uint3
     for (uint32_t t = 0; t < n_batches && !rc; ++t) rc = gffx_hip_batch_sync(batches[t]);
     if (rc) return rc;
     GFFX_HIP_TRY(hipSetDevice(batches[0]->ix->device));
-    hipEvent_t a, z;
-    GFFX_HIP_TRY(hipEventCreate(&a));
-    GFFX_HIP_TRY(hipEventCreate(&z));
-    rc = run_group(batches, n_batches, mode, invert, out_flags, strategy, 0);  // (moves every batch to the group stream, if they group)
+    hipEvent_t a = nullptr, z = nullptr;  // (destroyed on every path below)
+    rc = hipEventCreate(&a) != hipSuccess || hipEventCreate(&z) != hipSuccess ? fail(GFFX_E_HIP, "gffx_hip_batches_timed_runs: hipEventCreate failed") : GFFX_OK;
+    if (!rc) rc = run_group(batches, n_batches, mode, invert, out_flags, strategy, 0);  // (moves every batch to the group stream, if they group)
     const hipStream_t s = batches[0]->last_stream ? batches[0]->last_stream : batches[0]->stream;
     if (grouped) *grouped = batches[0]->last_stream ? 1u : 0u;
     if (!rc) {
@@ -984,8 +1002,8 @@ extern "C" int gffx_hip_batches_timed_runs(gffx_hip_batch *const *batches, uint3
         float ms = 0.f;
         if (!rc && hipEventElapsedTime(&ms, a, z) == hipSuccess) *total_ms = ms;
     }
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(z);
+    if (a) (void)hipEventDestroy(a);
+    if (z) (void)hipEventDestroy(z);
     return rc;
 }
 

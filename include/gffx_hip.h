@@ -302,7 +302,12 @@ int gffx_hip_batch_timed_runs(gffx_hip_batch *, int mode, int invert, uint32_t o
  * regions): per-batch order is what it always was.  Up to three batches run pass by pass (their launches share the chip as in round
  * 5); from four on the batches are cut into groups of equal size (<= 8), half of them on each of two such streams, so that one group's
  * drain overlaps the next one's ramp.  Results are exactly those of n_passes single _run calls.  Knob GFFX_HIP_GROUP of batches[0]
- * ("Tuning knobs" above). */
+ * ("Tuning knobs" above).
+ * On failure: the arguments and every batch that takes a pass (NULL, no regions set, a mode, strategy or flags _run would refuse) are
+ * checked before anything runs -- a call that fails there launches nothing, and every batch keeps its last completed pass (a _wait
+ * and the results read what that pass left).  A failure after that (a HIP or allocation error of one batch) leaves the passes
+ * enqueued before it, and those of the batches already prepared for the same launch, as passes run one by one: every batch the
+ * call marked as run has a real pass behind its next _wait; the failing batch itself is in the state a failed _run leaves. */
 int gffx_hip_batches_run_n(gffx_hip_batch *const *batches, uint32_t n_batches, int mode, int invert, uint32_t out_flags,
                            int strategy, uint64_t n_passes);
 /* How _batches_run_n cuts passes over these batches into launches: *groups per walk over the batches (0: pass by pass), the *largest

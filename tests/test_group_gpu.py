@@ -250,3 +250,51 @@ def test_rounds_by_ticket_on_small_grids(tickets, threads, blocks):
             assert np.array_equal(b.counts(), wc) and b.total_hits == len(want)
         b.close()
     ix.close()
+
+
+@pytest.mark.parametrize("group", [2, 0])
+def test_a_failed_call_leaves_every_batch_its_last_pass(group):
+    """gffx_hip_batches_run_n with a batch that cannot run (no regions) fails with GFFX_E_STATE and launches nothing: every other batch
+    keeps its last completed pass -- mode, flags, results -- and is idle (a member prepared for the failed call's pass but never
+    launched would read the previous pass's buffers under the new mode and flags at its wait).  Grouped (GROUP=2: [b0, b1] [b2, b3])
+    and pass by pass (GROUP=0)."""
+    roots = _roots()
+    oix, ix = _oracle(roots), _index(roots)
+    sets = [synth.synth_bed(n, seed=8000 + i, edge_frac=0.02, roots=roots) for i, n in enumerate([30_000, 12_289, 50_000, 20_000])]
+    bs = _make_batches(ix, sets)
+    bs[0].set_option("GROUP", group)
+    engine.run_batches(bs, OverlapMode.Contained, False, engine.OUT_FIDS | engine.OUT_SEGBASE)
+    for b in bs:
+        b.wait()
+    empty = engine.QueryBatch(ix, 1000)  # created, never given regions
+    with pytest.raises(engine._ffi.GffxHipError) as ei:
+        engine.run_batches(bs[:3] + [empty], OverlapMode.Overlap, False, engine.OUT_TRIPLES | engine.OUT_OFFSETS | engine.OUT_ROOT_BITMAP)
+    assert ei.value.code == -6  # GFFX_E_STATE
+    for b, r in zip(bs[:3], sets):
+        b.wait()
+        want, wc, _ = _want_pairs(oix, r, OverlapMode.Contained, False)
+        c = b.counts()
+        assert np.array_equal(c, wc)
+        assert b.total_hits == len(want)
+        assert np.array_equal(_pairs_of(b, r, c, b.offsets_from_segbase(c)), want)
+    # the batch that would have been prepared last is idle: a lone pass of 600 k regions afterwards still takes 1024-thread blocks
+    big = synth.synth_bed(600_000, seed=8100, edge_frac=0.01, roots=roots)
+    lone = engine.QueryBatch(ix, len(big))
+    lone.set_regions(big)
+    lone.run(OverlapMode.Overlap, False, engine.OUT_FIDS | engine.OUT_SEGBASE)
+    lone.wait()
+    assert lone.block_threads == 1024
+    lone.close()
+    # ... and a normal Overlap call over four valid batches is the oracle's
+    flags = engine.OUT_TRIPLES | engine.OUT_OFFSETS | engine.OUT_ROOT_BITMAP
+    engine.run_batches(bs, OverlapMode.Overlap, False, flags)
+    for b, r in zip(bs, sets):
+        b.wait()
+        want, wc, wt = _want_pairs(oix, r, OverlapMode.Overlap, False)
+        assert np.array_equal(b.counts(), wc)
+        order = lambda a: a[np.lexsort((a[:, 2], a[:, 1], a[:, 0]))]  # noqa: E731
+        assert np.array_equal(order(b.triples()), order(wt))
+        assert np.array_equal(b.unique_roots(), np.unique(wt[:, 0]))
+    for b in bs + [empty]:
+        b.close()
+    ix.close()
