@@ -99,6 +99,15 @@ SIGNATURES = {
     "gffx_hip_depth_accumulate": (C.c_int, [vp, vp]),
     "gffx_hip_depth_reset": (C.c_int, [vp]),
     "gffx_hip_depth_copy": (C.c_int, [vp, u64p, u32p, u32p]),
+    "gffx_hip_bgzf_inflate": (C.c_int, [C.c_int, u8p, C.c_uint64, u8p, C.c_uint64, u64p]),
+    "gffx_hip_bam_create": (C.c_int, [C.c_int, C.c_uint32, u32p, C.c_uint64, C.c_uint64, C.POINTER(vp)]),
+    "gffx_hip_bam_feed": (C.c_int, [vp, u8p, C.c_uint64]),
+    "gffx_hip_bam_finish": (C.c_int, [vp]),
+    "gffx_hip_bam_rows": (C.c_uint64, [vp]),
+    "gffx_hip_bam_counts": (C.c_int, [vp, u64p, u64p, u64p, u64p]),
+    "gffx_hip_bam_stage_ms": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gffx_hip_bam_copy_rows": (C.c_int, [vp, u32p]),
+    "gffx_hip_bam_destroy": (None, [vp]),
 }
 
 _lib = None

@@ -73,13 +73,21 @@ void run(const CoverageArgs &args) {
     }
     DeviceWarmup warm(args.device);  // (the runtime comes up beside the loaders and the BED parser)
     TreeIndexData index_data = TreeIndexData::load_tree_index(args.input);  // :511
-    if (ext == "bam" || ext == "sam" || ext == "cram")
-        throw Error("BAM/SAM/CRAM sources need htslib, which this build does not carry; use a .bed source");
-    if (ext != "bed")
+    if (ext == "sam" || ext == "cram")
+        throw Error("SAM/CRAM sources need htslib, which this build does not carry; use a .bam or .bed source");
+    if (ext != "bed" && ext != "bam")
         throw Error("Unsupported file type: \"" + args.source + "\". Expected .bam/.sam/.cram or .bed");  // :535-540
-    const std::vector<intersect::Region> regions = depth::parse_bed_rows(args.source, index_data.seqid_to_num, capped_threads(args.threads));  // :230-256
-    if (verbose) std::fprintf(stderr, "[INFO] %zu BED rows kept\n", regions.size());
-    timer.lap("Loading index + parsing BED");
+    std::vector<intersect::Region> regions;
+    if (ext == "bam") {  // coverage.rs:125-168: the same (chr, start, end) rows, from BAM records
+        warm.wait();
+        const std::vector<uint32_t> flat = bam::read_rows(args.source, index_data.seqid_to_num, args.device, verbose);
+        regions.reserve(flat.size() / 3);
+        for (size_t i = 0; i + 2 < flat.size(); i += 3) regions.emplace_back(flat[i], flat[i + 1], flat[i + 2]);
+    } else {
+        regions = depth::parse_bed_rows(args.source, index_data.seqid_to_num, capped_threads(args.threads));  // :230-256
+    }
+    if (verbose) std::fprintf(stderr, "[INFO] %zu %s rows kept\n", regions.size(), ext == "bam" ? "BAM" : "BED");
+    timer.lap(ext == "bam" ? "Loading index + reading BAM" : "Loading index + parsing BED");
 
     std::string out = "id\tchr\tstart\tend\tbreadth\tfraction\n";  // :463
     size_t written = 0;

@@ -206,19 +206,25 @@ void run(const DepthArgs &args) {
         throw Error("Cannot open GFF file: \"" + args.input + "\"");
     }
     TreeIndexData index_data = TreeIndexData::load_tree_index(args.input);  // :573
-    if (ext == "bam" || ext == "sam" || ext == "cram")
-        throw Error("BAM/SAM/CRAM sources need htslib, which this build does not carry; use a .bed source");
-    if (ext != "bed")
+    if (ext == "sam" || ext == "cram")
+        throw Error("SAM/CRAM sources need htslib, which this build does not carry; use a .bam or .bed source");
+    if (ext != "bed" && ext != "bam")
         throw Error("Unsupported file type: \"" + args.source + "\". Expected .bam/.sam/.cram or .bed");  // :597-600
     timer.lap("Loading index");
     const size_t threads = capped_threads(args.threads);
     // the kept rows as flat triples, one vector per parsed piece (file order); part_row[p] = rows before piece p
-    const std::vector<std::vector<uint32_t>> part = parse_bed_rows_flat(args.source, index_data.seqid_to_num, threads);
+    std::vector<std::vector<uint32_t>> part;
+    if (ext == "bam") {  // depth.rs:297-372: the same (chr, start, end) rows, from BAM records
+        warm.wait();
+        part.push_back(bam::read_rows(args.source, index_data.seqid_to_num, args.device, verbose));
+    } else {
+        part = parse_bed_rows_flat(args.source, index_data.seqid_to_num, threads);
+    }
     std::vector<size_t> part_row(part.size() + 1, 0);
     for (size_t p = 0; p < part.size(); ++p) part_row[p + 1] = part_row[p] + part[p].size() / 3;
     const size_t n_rows = part_row.back();
-    if (verbose) std::fprintf(stderr, "[INFO] %zu BED rows kept\n", n_rows);
-    timer.lap("Parsing BED");
+    if (verbose) std::fprintf(stderr, "[INFO] %zu %s rows kept\n", n_rows, ext == "bam" ? "BAM" : "BED");
+    timer.lap(ext == "bam" ? "Reading BAM" : "Parsing BED");
 
     const BlockTable t = load_or_build_block_table(args.input, gof, gff.view(), threads, verbose);
     timer.lap("Line table (image or parse)");

@@ -8,6 +8,7 @@
 //        query_features, gff_type_allowed, write_gff_match_only_by_coords, run}  commands/intersect.rs
 //   gffx::commands::depth::{DepthArgs, parse_bed_rows, run}                      commands/depth.rs (BED source)
 //   gffx::commands::coverage::{CoverageArgs, run}                                commands/coverage.rs (BED source)
+//   gffx::bam::read_rows                                                         depth.rs:297-372 / coverage.rs:125-168 (BAM source)
 // Compute (Join A, Join B) goes through include/gffx_hip.h only; there is no CPU join here.
 #pragma once
 #include <algorithm>
@@ -312,7 +313,7 @@ namespace depth {
 
 struct DepthArgs {  // depth.rs:34-72
     std::string input;                  // -i/--input
-    std::string source;                 // -s/--source (BED; BAM/SAM/CRAM need htslib: refused)
+    std::string source;                 // -s/--source (BED or BAM; SAM/CRAM need htslib: refused)
     std::optional<std::string> output;  // -o/--output
     uint32_t bin_shift = 12;            // --bin-shift (only bounds the reference's candidate lists; accepted, unused)
     size_t threads = 12;                // -t/--threads
@@ -356,7 +357,7 @@ namespace coverage {
 
 struct CoverageArgs {  // coverage.rs:37-57
     std::string input;                  // -i/--input
-    std::string source;                 // -s/--source (BED; BAM/SAM/CRAM need htslib: refused)
+    std::string source;                 // -s/--source (BED or BAM; SAM/CRAM need htslib: refused)
     std::optional<std::string> output;  // -o/--output
     size_t threads = 12;                // -t/--threads
     bool verbose = false;               // -v/--verbose
@@ -367,6 +368,14 @@ void run(const CoverageArgs &args);  // coverage.rs:487-582
 
 }  // namespace coverage
 }  // namespace commands
+
+// ---- BAM sources of depth / coverage (bam.cpp; commands/depth.rs:297-372, coverage.rs:125-168) ------------------------
+namespace bam {
+// the kept (seqid number, start, end) rows of a BAM file, flat, in file order (BGZF inflated on `device`; no htslib).
+// GFFX_BAM_CHUNK_BYTES sets the compressed bytes per device pass (default 256 MiB).  Throws Error on a bad file.
+std::vector<uint32_t> read_rows(const std::string &path, const std::unordered_map<std::string, uint32_t> &seqid_to_num, int device,
+                                bool verbose);
+}  // namespace bam
 
 // main.rs: `gffx <index|intersect|depth|coverage> ...`; returns the process exit code
 int cli_main(int argc, char **argv);

@@ -493,3 +493,91 @@ def query_features(index_data: TreeIndexData, regions, mode: int = OverlapMode.O
     out = np.ctypeslib.as_array(tp, shape=(max(n.value, 1), 3))[: n.value].copy()
     lib().gffx_hip_free_host(tp)
     return out
+
+
+# ---- BAM sources (include/gffx_hip.h "BAM sources"; device/bgzf.hip) ----------------------------------------------------
+def _u8(data: bytes):
+    buf = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, np.uint8)
+    return buf, buf.ctypes.data_as(_ffi.u8p)
+
+
+def bgzf_inflate(data: bytes, device: int = 0) -> bytes:
+    """The BGZF members of `data`, inflated on the device (one wave per member; CRC32 and ISIZE checked)."""
+    buf, ptr = _u8(data)
+    n = C.c_uint64()
+    check(lib().gffx_hip_bgzf_inflate(device, ptr, len(data), None, 0, C.byref(n)))
+    out = np.zeros(max(n.value, 1), np.uint8)
+    check(lib().gffx_hip_bgzf_inflate(device, ptr, len(data), out.ctypes.data_as(_ffi.u8p), n.value, C.byref(n)))
+    return out[: n.value].tobytes()
+
+
+def bgzf_members(data: bytes) -> List[int]:
+    """Offsets of the BGZF members of `data` (plus len(data)), by hopping their BSIZE fields (BC subfield first)."""
+    off, at = [], 0
+    while at < len(data):
+        off.append(at)
+        if len(data) - at < 18:
+            raise ValueError("truncated BGZF member at offset %d" % at)
+        at += int.from_bytes(data[at + 16:at + 18], "little") + 1
+    off.append(len(data))
+    return off
+
+
+class BamReader:
+    """gffx_hip_bam_*: the kept (seqid, start, end) rows of a BAM stream.  ref_seq[tid] = seqid number or 0xFFFFFFFF;
+    header_bytes = the BAM header's size in the decompressed stream."""
+
+    def __init__(self, ref_seq, header_bytes: int, chunk_bytes: int = 0, device: int = 0):
+        rs = _u32(ref_seq)
+        self._h = C.c_void_p()
+        check(lib().gffx_hip_bam_create(device, len(rs), _p(rs) if len(rs) else None, header_bytes, chunk_bytes, C.byref(self._h)))
+
+    def feed(self, data: bytes) -> None:
+        buf, ptr = _u8(data)
+        check(lib().gffx_hip_bam_feed(self._h, ptr, len(data)))
+
+    def finish(self) -> None:
+        check(lib().gffx_hip_bam_finish(self._h))
+
+    def rows(self) -> np.ndarray:
+        n = lib().gffx_hip_bam_rows(self._h)
+        out = np.zeros((max(n, 1), 3), np.uint32)
+        check(lib().gffx_hip_bam_copy_rows(self._h, _p(out)))
+        return out[:n]
+
+    def counts(self) -> Dict[str, int]:
+        v = [C.c_uint64() for _ in range(4)]
+        check(lib().gffx_hip_bam_counts(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("records", "unmapped", "no_seq", "kept"), (x.value for x in v)))
+
+    def stage_ms(self) -> Dict[str, float]:
+        v = [C.c_double() for _ in range(3)]
+        check(lib().gffx_hip_bam_stage_ms(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("inflate", "frame", "rows"), (x.value for x in v)))
+
+    def close(self) -> None:
+        if self._h:
+            lib().gffx_hip_bam_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bam_rows(data: bytes, ref_seq, header_bytes: int, chunk_bytes: int = 0, feed_members: int = 0, device: int = 0) -> np.ndarray:
+    """The rows of a whole BAM stream in file order.  feed_members > 0: fed that many members per call."""
+    r = BamReader(ref_seq, header_bytes, chunk_bytes, device)
+    try:
+        if feed_members > 0:
+            off = bgzf_members(data)
+            for i in range(0, len(off) - 1, feed_members):
+                r.feed(data[off[i]:off[min(i + feed_members, len(off) - 1)]])
+        else:
+            r.feed(data)
+        r.finish()
+        return r.rows()
+    finally:
+        r.close()

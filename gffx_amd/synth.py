@@ -273,3 +273,138 @@ def write_bed_fast(path: str, regions: np.ndarray, names: Sequence[str]) -> None
     subprocess.check_call([tool, "bed", tmp, path + ".names", path])
     os.remove(tmp)
     os.remove(path + ".names")
+
+
+# ---- BAM (SAM spec §4.2) in BGZF (§4.1), written with Python's zlib: test and benchmark inputs of the BAM source path ----
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+BGZF_BLOCK = 0xFF00  # htslib's uncompressed block size
+
+
+def bgzf_member(data: bytes, level: int = 6, strategy: int = 0) -> bytes:
+    """One BGZF member: a gzip member with the BC subfield (BSIZE), raw DEFLATE, CRC32, ISIZE."""
+    import struct
+    import zlib
+    c = zlib.compressobj(level, zlib.DEFLATED, -15, 8, strategy)
+    body = c.compress(data) + c.flush()
+    total = 18 + len(body) + 8
+    if total > 65536 or len(data) > 65536:
+        raise ValueError("BGZF member too large (%d bytes in, %d out)" % (len(data), total))
+    return (b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", total - 1) + body +
+            struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data)))
+
+
+def bam_header(refs: Sequence[Tuple[str, int]], text: bytes = b"") -> bytes:
+    import struct
+    out = [b"BAM\x01", struct.pack("<i", len(text)), text, struct.pack("<i", len(refs))]
+    for name, length in refs:
+        nb = name.encode() + b"\x00"
+        out += [struct.pack("<i", len(nb)), nb, struct.pack("<i", length)]
+    return b"".join(out)
+
+
+CIGAR_OPS = "MIDNSHP=X"
+
+
+def bam_record(tid: int, pos: int, flag: int = 0, cigar: Sequence[Tuple[int, int]] = ((0, 150),), name: bytes = b"r",
+               l_seq: int = 0, tags: bytes = b"", mapq: int = 60) -> bytes:
+    """One record; cigar = (op, length) pairs, op 0..8 = MIDNSHP=X."""
+    import struct
+    rn = name + b"\x00"
+    cig = b"".join(struct.pack("<I", (ln << 4) | op) for op, ln in cigar)
+    body = (struct.pack("<iiBBHHHiiii", tid, pos, len(rn), mapq, 4680, len(cigar), flag, l_seq, -1, -1, 0) + rn + cig +
+            bytes((l_seq + 1) // 2) + b"\xff" * l_seq + tags)
+    return struct.pack("<i", len(body)) + body
+
+
+def bam_end(pos: int, cigar: Sequence[Tuple[int, int]]) -> int:
+    """htslib's bam_endpos as restated in device/bgzf_core.hpp: pos + the M/D/N/=/X lengths, a sum of 0 counting as 1."""
+    rlen = sum(ln for op, ln in cigar if op in (0, 2, 3, 7, 8))
+    return pos + (rlen if rlen else 1)
+
+
+def bgzf_blocks(header: bytes, records: Sequence[bytes], layout: str = "aligned", flush_header: bool = True,
+                block: int = BGZF_BLOCK) -> List[bytes]:
+    """The uncompressed payloads of the members.  aligned: htslib's writer (a block is flushed before a record that would
+    not fit; a record larger than a block is cut into full blocks); spanning: one stream cut every `block` bytes (htsjdk)."""
+    if layout == "spanning":
+        s = header + b"".join(records)
+        return [s[i:i + block] for i in range(0, len(s), block)]
+    out, cur = [], bytearray()
+    pending = [(header, flush_header)] + [(r, False) for r in records]
+    for data, flush_after in pending:
+        if cur and len(cur) + len(data) > block:
+            out.append(bytes(cur))
+            cur = bytearray()
+        cur += data
+        while len(cur) > block:
+            out.append(bytes(cur[:block]))
+            del cur[:block]
+        if flush_after and cur:
+            out.append(bytes(cur))
+            cur = bytearray()
+    if cur:
+        out.append(bytes(cur))
+    return out
+
+
+def write_bam(path: str, header: bytes, records: Sequence[bytes], layout: str = "aligned", level: int = 6, strategy: int = 0,
+              eof: bool = True, flush_header: bool = True, block: int = BGZF_BLOCK) -> int:
+    """Writes a BAM file; returns the header's size in the decompressed stream."""
+    with open(path, "wb") as f:
+        for b in bgzf_blocks(header, records, layout, flush_header, block):
+            f.write(bgzf_member(b, level, strategy))
+        if eof:
+            f.write(BGZF_EOF)
+    return len(header)
+
+
+def bam_test_records(n: int, seed: int, refs: Sequence[Tuple[str, int]], big: bool = True) -> List[tuple]:
+    """Coordinate-sorted records with every quirk the BAM path has a rule for: (record bytes, tid, pos, flag, cigar).
+    Unmapped reads, refID -1, pos -1, every CIGAR op, all-clip and empty CIGARs, an end past 2^32, a kSmN record with
+    its CIGAR in a CG tag, and (big) one record larger than a BGZF block."""
+    import struct
+    rng = np.random.default_rng(seed)
+    out = []
+    n_ref = len(refs)
+    pos = np.sort(rng.integers(0, 2_000_000, n))
+    tids = np.sort(rng.integers(0, n_ref, n))
+    for i in range(n):
+        tid, p, flag = int(tids[i]), int(pos[i]), int(rng.choice([0, 16, 0x100, 0x400, 0x4, 0x4 | 0x10], p=[.5, .2, .1, .1, .07, .03]))
+        k = int(rng.integers(0, 20))
+        if k == 0:
+            cigar = []
+        elif k == 1:
+            cigar = [(4, 50), (1, 3), (5, 9), (6, 2)]  # S I H P only: reference length 0 -> 1
+        else:
+            cigar = [(int(rng.integers(0, 9)), int(rng.integers(1, 300))) for _ in range(int(rng.integers(1, 7)))]
+        l_seq = int(rng.integers(0, 160))
+        tags = b"NMC\x02" if rng.random() < 0.3 else b""
+        if rng.random() < 0.01:
+            tid = -1
+        if rng.random() < 0.01:
+            p = -1
+        out.append((bam_record(tid, p, flag, cigar, b"q%d" % i, l_seq, tags), tid, p, flag, cigar))
+    # an end clamped at 2^32 - 1, a kSmN placeholder, a record larger than a BGZF block
+    cig = [(3, (1 << 28) - 1)] * 10
+    out.append((bam_record(n_ref - 1, 2_000_000_000, 0, cig, b"far"), n_ref - 1, 2_000_000_000, 0, cig))
+    real = [(0, 100), (3, 5000), (0, 50)]
+    cg = b"CGBI" + struct.pack("<i", len(real)) + b"".join(struct.pack("<I", (ln << 4) | op) for op, ln in real)
+    ksmn = [(4, 150), (3, 5150)]
+    out.append((bam_record(0, 1234, 0, ksmn, b"long", 150, cg), 0, 1234, 0, ksmn))
+    if big:
+        tag = b"XXZ" + b"A" * 150000 + b"\x00"
+        out.append((bam_record(0, 777, 0, [(0, 80)], b"huge", 80, tag), 0, 777, 0, [(0, 80)]))
+    return out
+
+
+def bam_rows_definition(recs: Sequence[tuple], ref_seq: Sequence[int]) -> np.ndarray:
+    """depth.rs:335-364 restated: the (seqid, start, end) rows a list of bam_test_records keeps, in file order."""
+    rows = []
+    for _, tid, pos, flag, cigar in recs:
+        if flag & 0x4 or tid < 0 or ref_seq[tid] == 0xFFFFFFFF or pos < 0:
+            continue
+        end = bam_end(pos, cigar)
+        if end <= pos:
+            continue
+        rows.append((ref_seq[tid], min(pos, 0xFFFFFFFF), min(end, 0xFFFFFFFF)))
+    return np.array(rows, dtype=np.uint32).reshape(-1, 3)

@@ -19,6 +19,8 @@
  *     (commands/depth.rs:121-293)
  *   merge_intervals + the two-pointer walk              gffx_hip_segments_covered (`gffx coverage`, BED source)
  *     (commands/coverage.rs:92-124, :339-364)
+ *   bam::Reader records -> (chr, start, end) rows        gffx_hip_bgzf_inflate, gffx_hip_bam_* (BAM sources)
+ *     (commands/depth.rs:297-372, coverage.rs:125-168)
  *
  * Semantics (bit-exact with the reference):
  *   a root interval iv of the query's seqid is a HIT iff  iv.start < q.end && iv.end > q.start
@@ -167,6 +169,7 @@ typedef struct gffx_hip_batch gffx_hip_batch;
 typedef struct gffx_hip_lines gffx_hip_lines;
 typedef struct gffx_hip_regions gffx_hip_regions;
 typedef struct gffx_hip_depth gffx_hip_depth;
+typedef struct gffx_hip_bam gffx_hip_bam;
 
 int gffx_hip_abi_version(void);
 /* number of visible HIP devices (0 when none / no driver); never fails */
@@ -412,6 +415,37 @@ int gffx_hip_depth_copy(gffx_hip_depth *, uint64_t *depth, uint32_t *min_start, 
 int gffx_hip_segments_covered(int device, uint64_t n_seg, const uint32_t *seg_seq, const uint32_t *seg_start,
                               const uint32_t *seg_end, const uint32_t *regions, uint64_t nq, uint32_t n_seq,
                               uint32_t *covered_out);
+
+/* ---- BAM sources of `gffx depth` / `gffx coverage` (commands/depth.rs:297-427, commands/coverage.rs:125-204) --
+ * BGZF members are inflated on the device (one wave per member, device/bgzf.hip; the decoder, device/bgzf_core.hpp, is
+ * shared with the host).  A bad member fails the call with a message naming its file offset: a header that is not BGZF,
+ * a truncated member, an invalid DEFLATE stream, an ISIZE or CRC32 mismatch.
+ *
+ * gffx_hip_bgzf_inflate: the members of bgzf[0, n_bytes) into out[0, *n_out).  out == NULL: *n_out = the decompressed
+ * size (the sum of the ISIZEs), no device needed.
+ *
+ * gffx_hip_bam_*: the rows of a BAM file.  _create takes the header's size in the decompressed stream (the caller
+ * decodes the header: magic, l_text, n_ref, names) and ref_seq[tid] = the index's seqid number of reference tid, or
+ * UINT32_MAX when the index has no such seqid; chunk_bytes bounds the compressed bytes per device pass (0: 256 MiB).
+ * _feed takes whole members in file order from byte 0, any number per call; _finish fails if the file ends inside
+ * the header or inside a record.  Rows are (seqid, start, end), 3 x u32 each, in file order: a record is kept unless
+ * flag & 0x4, refID < 0, ref_seq[refID] == UINT32_MAX or pos < 0 (depth.rs:335-364); start = pos, end = bam_endpos
+ * clamped to UINT32_MAX.  ASSUMPTION (htslib's sam.c restated from memory): bam_endpos = pos + the summed lengths of the
+ * CIGAR ops M/D/N/=/X, where a sum of 0 (no CIGAR, or only I/S/H/P) counts as 1.  A malformed record (block_size < 32,
+ * l_read_name == 0, read name + CIGAR beyond block_size, refID outside [-1, n_ref)) fails the call, as bam_read1 does.
+ * _counts: records framed, unmapped ones, mapped ones whose refID is < 0 or not in the index, rows kept.
+ * _stage_ms: device time of the inflate, framing and rows kernels so far (HIP events).
+ * After an error the object only reports it again. */
+int gffx_hip_bgzf_inflate(int device, const uint8_t *bgzf, uint64_t n_bytes, uint8_t *out, uint64_t cap, uint64_t *n_out);
+int gffx_hip_bam_create(int device, uint32_t n_ref, const uint32_t *ref_seq, uint64_t header_bytes, uint64_t chunk_bytes,
+                        gffx_hip_bam **out);
+int gffx_hip_bam_feed(gffx_hip_bam *, const uint8_t *bgzf, uint64_t n_bytes);
+int gffx_hip_bam_finish(gffx_hip_bam *);
+uint64_t gffx_hip_bam_rows(const gffx_hip_bam *);
+int gffx_hip_bam_counts(const gffx_hip_bam *, uint64_t *records, uint64_t *unmapped, uint64_t *no_seq, uint64_t *kept);
+int gffx_hip_bam_stage_ms(const gffx_hip_bam *, double *inflate_ms, double *frame_ms, double *rows_ms);
+int gffx_hip_bam_copy_rows(gffx_hip_bam *, uint32_t *rows /* 3 per row */);
+void gffx_hip_bam_destroy(gffx_hip_bam *);
 
 #ifdef __cplusplus
 }

@@ -25,6 +25,10 @@ pub struct gffx_hip_batch {
 pub struct gffx_hip_depth {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct gffx_hip_bam {
+    _p: [u8; 0],
+}
 
 pub const GFFX_MODE_CONTAINED: c_int = 0; // OverlapMode::Contained       intersect.rs:75
 pub const GFFX_MODE_CONTAINS_REGION: c_int = 1; // OverlapMode::ContainsRegion  intersect.rs:76
@@ -111,6 +115,24 @@ extern "C" {
     pub fn gffx_hip_depth_accumulate(d: *mut gffx_hip_depth, b: *mut gffx_hip_batch) -> c_int;
     pub fn gffx_hip_depth_copy(d: *mut gffx_hip_depth, depth: *mut u64, min_start: *mut u32, max_end: *mut u32) -> c_int;
     pub fn gffx_hip_depth_destroy(d: *mut gffx_hip_depth);
+
+    // BAM sources (depth.rs:297-427 process_bam, coverage.rs:125-204): BGZF inflated on the device, rows (seqid, start, end)
+    pub fn gffx_hip_bgzf_inflate(device: c_int, bgzf: *const u8, n_bytes: u64, out: *mut u8, cap: u64, n_out: *mut u64) -> c_int;
+    pub fn gffx_hip_bam_create(
+        device: c_int,
+        n_ref: u32,
+        ref_seq: *const u32,
+        header_bytes: u64,
+        chunk_bytes: u64,
+        out: *mut *mut gffx_hip_bam,
+    ) -> c_int;
+    pub fn gffx_hip_bam_feed(h: *mut gffx_hip_bam, bgzf: *const u8, n_bytes: u64) -> c_int;
+    pub fn gffx_hip_bam_finish(h: *mut gffx_hip_bam) -> c_int;
+    pub fn gffx_hip_bam_rows(h: *const gffx_hip_bam) -> u64;
+    pub fn gffx_hip_bam_counts(h: *const gffx_hip_bam, records: *mut u64, unmapped: *mut u64, no_seq: *mut u64, kept: *mut u64) -> c_int;
+    pub fn gffx_hip_bam_stage_ms(h: *const gffx_hip_bam, inflate_ms: *mut f64, frame_ms: *mut f64, rows_ms: *mut f64) -> c_int;
+    pub fn gffx_hip_bam_copy_rows(h: *mut gffx_hip_bam, rows: *mut u32) -> c_int;
+    pub fn gffx_hip_bam_destroy(h: *mut gffx_hip_bam);
 }
 
 fn last_error() -> String {
