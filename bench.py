@@ -16,6 +16,12 @@ The JSON line carries, next to the contract's fields:
                         The pipeline is warmed (2 x inflight passes, synced) immediately before the timed region.  The timed
                         region is repeated --repeats times (default 5), each bracketed by barrier + synchronize; `value` is the
                         MEDIAN repeat, `repeats` lists them all.
+  dump_outputs          with --dump-outputs DIR: the results of the timed region's last pass, written as DIR/*.npy (counts, root_fids
+                        per region; the inputs are seeded, so two builds run with the same arguments can be compared file for file)
+
+A plain run does only that: it sets up, warms up, times the K steps, writes --dump-outputs and prints the line.  With --full the
+line also carries every leg below, each measured after the headline's timed region (--quick, --no-traffic and --no-cpu-baseline
+trim them):
   serial                the same K steps with ONE batch: strictly serial passes (what profiles/*kernel_stats* shows); the engine
                         takes 1024-thread blocks for such a pass (roofline inside), 512-thread blocks while several batches are in flight
   roofline              dominant kernel, HIP-event durations of serial back-to-back launches on the engine's stream
@@ -30,8 +36,6 @@ The JSON line carries, next to the contract's fields:
   join_b                Join B (k_lines_exists over a 3.4 M-line table) with the device-built region tables
   depth                 `gffx depth`'s kernel (k_depth_regions) on the same regions against a 3.4 M-line table
   cpu_baseline          the oracle's Join A on 1 thread (the reference is serial there), + all cores, + Join B on all cores
-  dump_outputs          with --dump-outputs DIR: the results of the timed region's last pass, written as DIR/*.npy (counts, root_fids
-                        per region; the inputs are seeded, so two builds run with the same arguments can be compared file for file)
 
 For N>1 (launched by torch.distributed.run, one rank per GPU) --scaling weak (default) gives every rank 1 M regions of an
 N x 1 M batch sharded by chromosome bucket (gffx_amd.shard, LPT with splitting; index replicated); --scaling strong shards
@@ -39,6 +43,7 @@ BASELINE configs[3]'s 100 M regions over the N ranks.  The only collective is th
 once per job: --exchange final-timed puts it inside the timed region (default for --scaling strong).
 
     python bench.py --gpus 1 --steps 50 --warmup 5
+    python bench.py --gpus 1 --steps 50 --warmup 5 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -93,12 +98,16 @@ def parse_args():
                     help="batches in flight in the timed region (own result buffers each).  The engine serves four or more with ONE launch "
                          "per group of up to 8 (gffx_hip_batches_run_n: 16 = two groups of 8 alternating between two streams); up to "
                          "three run pass by pass as in round 5")
-    ap.add_argument("--quick", action="store_true", help="headline + roofline + cpu_baseline only (skip the extra legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other leg: roofline (with live PMC traffic), group_launch, serial, the 10 M, cold, "
+                         "wide, mixed and sorted legs, cli_pass, t_xfer, t_e2e, join_b, depth and cpu_baseline.  Without it a run "
+                         "only sets up, warms up, times the steps, writes --dump-outputs and prints the headline line")
+    ap.add_argument("--quick", action="store_true", help="with --full: headline + roofline + cpu_baseline only (skip the extra legs)")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="do not measure roofline.traffic live (two child runs of this script under rocprofv3 --pmc, ~20 s)")
+                    help="with --full: do not measure roofline.traffic live (two child runs of this script under rocprofv3 --pmc, ~20 s)")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=8.0)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="with --full: cpu_baseline's time budget")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the timed pass computed in its last step as DIR/<name>.npy (float64, "
                          "at most 64 MB in all; see dump_outputs)")
@@ -752,8 +761,8 @@ def main():
     else:
         nq_total, pairs_total = nq, pairs
 
-    result = None
-    if rank == 0:
+    result, legs = None, {}
+    if rank == 0 and args.full:
         # the kernel variant the timed region ran (the last pass of batch 0 in it): the serial passes measured for `roofline`
         # and the PMC child are forced to the same block width
         timed_threads = run.batches[0].block_threads or None
@@ -797,6 +806,19 @@ def main():
                 traffic = live
             elif live and traffic is not None:
                 traffic["live_measurement_error"] = live["error"]
+        legs = {
+            "roofline": roofline_obj(kern, nq * (plan_largest if plan_groups else 1), pairs * (plan_largest if plan_groups else 1), out_b,
+                                     "achieved = (12 B region + 4 B count + 4 B x pairs/region) x the regions of ONE LAUNCH of the timed region / "
+                                     "its duration: serial launches back to back between one pair of HIP events on the stream they run on "
+                                     "(rank 0), at the block width of the timed region's launches.  With four batches or more in flight a launch "
+                                     "serves a group of batches (group_launch: regions_per_launch = batches_per_launch x the batch; traffic "
+                                     "is per launch as well); with fewer, one batch (round 5's launches in flight: forced to that region's grid).  "
+                                     "The resident batch is re-read by every pass: at 1 M regions (12 MB) the input stream is served by the 256 MB "
+                                     "Infinity Cache, not by HBM (immaterial at this fraction of the roofline, but it is not a cold-HBM figure)", traffic,
+                                     run.pass_us_one_event_pair, timed_threads, timed_blocks),
+            "group_launch": group_launch,
+        }
+    if rank == 0:
         result = {
             "metric": "BED overlap queries/sec vs GRCh38-scale GFF index at 1/2/4/8 MI355X",  # BASELINE.json
             "value": nq_total * n_passes / elapsed,
@@ -842,22 +864,13 @@ def main():
                 # batches read them when they were created
                 "knobs": {**ix.options(), **run.batches[0].options()},
             },
-            "roofline": roofline_obj(kern, nq * (plan_largest if plan_groups else 1), pairs * (plan_largest if plan_groups else 1), out_b,
-                                     "achieved = (12 B region + 4 B count + 4 B x pairs/region) x the regions of ONE LAUNCH of the timed region / "
-                                     "its duration: serial launches back to back between one pair of HIP events on the stream they run on "
-                                     "(rank 0), at the block width of the timed region's launches.  With four batches or more in flight a launch "
-                                     "serves a group of batches (group_launch: regions_per_launch = batches_per_launch x the batch; traffic "
-                                     "is per launch as well); with fewer, one batch (round 5's launches in flight: forced to that region's grid).  "
-                                     "The resident batch is re-read by every pass: at 1 M regions (12 MB) the input stream is served by the 256 MB "
-                                     "Infinity Cache, not by HBM (immaterial at this fraction of the roofline, but it is not a cold-HBM figure)", traffic,
-                                     run.pass_us_one_event_pair, timed_threads, timed_blocks),
-            "group_launch": group_launch,
+            **legs,  # (--full: roofline, group_launch)
         }
         if dumped is not None:
             result["dump_outputs"] = {"dir": args.dump_outputs, "files": dumped,
                                       "note": "the results of the timed region's last pass; N > 1: every rank writes its shard's "
                                               "<name>_rank<r>.npy (files: rank 0's)"}
-    if world == 1:
+    if world == 1 and args.full:
         # ---- strictly serial passes (one batch, one stream): what the committed rocprofv3 kernel stats show
         ser = Pass(engine, ix, cols, nq, 1, mode, out_flags, strategy)
         ser.size_and_warm(1)
@@ -870,7 +883,7 @@ def main():
                                                      "takes 1024-thread blocks (one per CU) for a pass of 500 000 regions or more that runs alone",
                                                      None, ser.pass_us_one_event_pair, ser.block_threads)}
         ser.close()
-    if world == 1 and not args.quick:
+    if world == 1 and args.full and not args.quick:
         # ---- the pass the CLI runs: root bitmap only (commands/intersect.rs:598-615 needs the unique roots, nothing else)
         cli = {}
         bm = Pass(engine, ix, cols, nq, 1, mode, engine.OUT_ROOT_BITMAP | engine.OUT_NO_COUNTS, strategy)  # (the CLI's flags)
@@ -1028,7 +1041,7 @@ def main():
             result["t_e2e"] = {"error": repr(exc)[:300]}
         result["join_b"] = join_b_leg(engine, synth, roots, regions, mode)
         result["depth"] = depth_leg(engine, synth, roots, ix, cols, nq)
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         # (N > 1: rank 0 times the same 1-thread leg on ITS shard, after the timed region and the exchange)
         cb = cpu_baseline(roots, regions, mode, args.cpu_seconds)
         if world > 1:
@@ -1037,7 +1050,7 @@ def main():
             cb["join_a_allcore"] = child_json([os.path.join(ROOT, "tools", "cpu_allcore.py"), str(nq), str(mode), "4"])
             cb["join_b_allcore"] = child_json([os.path.join(ROOT, "tools", "cpu_joinb_allcore.py"), str(nq), str(mode), "6"])
         result["cpu_baseline"] = cb
-    elif rank == 0:
+    elif rank == 0 and args.full:
         result["cpu_baseline"] = None
     if rank == 0:
         json_out.write(json.dumps(result) + "\n")

@@ -39,7 +39,7 @@ def _oracle_pairs(n, seed):
 
 
 def test_bench_two_ranks_weak_scaling_line():
-    line = _run_bench([])
+    line = _run_bench(["--full"])  # (roofline and cpu_baseline are --full legs)
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["unit"] == "queries/s" and line["value"] > 0
     cfg = line["config"]
     assert cfg["regions_total"] == 2_000_000

@@ -6,7 +6,7 @@
 # the box for the whole gpurun limit.  Counter passes are separate runs with --kernel-trace only (never combined with other traces).
 set -u
 TAG=$1; shift
-ARGS="--steps 20 --warmup 3 --passes-per-step 1 --repeats 1 --no-cpu-baseline --quick --inflight 1 $*"  # serial passes: per-kernel durations without overlap
+ARGS="--full --steps 20 --warmup 3 --passes-per-step 1 --repeats 1 --no-cpu-baseline --quick --inflight 1 $*"  # serial passes: per-kernel durations without overlap
 R=$(cd "$(dirname "$0")/.." && pwd)  # the checkout this script is in
 cd /tmp && export TMPDIR=/tmp
 OUT=$R/gpurun_out/$TAG
