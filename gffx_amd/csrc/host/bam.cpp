@@ -11,8 +11,7 @@
 #include "../device/bgzf_core.hpp"
 #include "gffx.hpp"
 
-namespace gffx {
-namespace bam {
+namespace gffx::bam {
 
 namespace {
 // the 28-byte empty member that ends a BGZF file (SAM spec §4.1.2)
@@ -41,12 +40,7 @@ std::vector<uint32_t> read_rows(const std::string &path, const std::unordered_ma
         if (verbose) std::fprintf(stderr, "[TIMER] [run] %s took %.3f ms\n", what, ms);
         g_run_stats.stage(what, ms);
     };
-    MappedFile f;
-    try {
-        f = MappedFile(path);
-    } catch (const Error &) {
-        throw Error("cannot open BAM file \"" + path + "\" (read without htslib)");
-    }
+    const MappedFile f = map_file_or(path, "cannot open BAM file \"" + path + "\" (read without htslib)");
     const std::string_view v = f.view();
     const uint8_t *p = reinterpret_cast<const uint8_t *>(v.data());
     const uint64_t n = v.size();
@@ -108,10 +102,9 @@ std::vector<uint32_t> read_rows(const std::string &path, const std::unordered_ma
     // the members in chunks of about chunk_bytes, through the engine
     t = clock::now();
     const uint64_t chunk = chunk_bytes_from_env();
-    gffx_hip_bam *h = nullptr;
-    if (gffx_hip_bam_create(device, n_ref, ref_seq.data(), header_bytes, chunk, &h) != GFFX_OK)
-        throw Error(std::string("gffx_hip_bam_create: ") + gffx_hip_last_error());
-    std::unique_ptr<gffx_hip_bam, void (*)(gffx_hip_bam *)> guard(h, gffx_hip_bam_destroy);
+    Handle<gffx_hip_bam, gffx_hip_bam_destroy> owner;
+    if (gffx_hip_bam_create(device, n_ref, ref_seq.data(), header_bytes, chunk, OutPtr(owner)) != GFFX_OK) hip_fail("gffx_hip_bam_create");
+    gffx_hip_bam *h = owner.get();
     auto engine_error = [&]() { return Error("BAM file \"" + path + "\": " + gffx_hip_last_error()); };
     for (size_t m = 0; m < n_members;) {
         size_t e = m + 1;
@@ -142,5 +135,4 @@ std::vector<uint32_t> read_rows(const std::string &path, const std::unordered_ma
     return rows;
 }
 
-}  // namespace bam
-}  // namespace gffx
+}  // namespace gffx::bam

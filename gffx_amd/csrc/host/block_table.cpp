@@ -7,16 +7,10 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
-#include <exception>
-#include <thread>
-
-#include <sys/stat.h>
 
 #include "gffx.hpp"
 
-namespace gffx {
-namespace commands {
-namespace depth {
+namespace gffx::commands::depth {
 
 namespace {
 
@@ -63,7 +57,6 @@ struct Chunk {  // a thread's contiguous share of the root blocks
     std::vector<uint32_t> per_block;  // kept lines of each block
     std::vector<uint32_t> groups_per_block;
     size_t n_groups = 0;
-    std::exception_ptr err;
 };
 
 void parse_block(std::string_view gff, uint64_t lo, uint64_t hi, std::vector<RawLine> &out) {
@@ -106,27 +99,6 @@ void parse_block(std::string_view gff, uint64_t lo, uint64_t hi, std::vector<Raw
     }
 }
 
-template <class F>
-void run_chunks(std::vector<Chunk> &chunks, F f) {
-    std::vector<std::thread> pool;
-    for (size_t c = 1; c < chunks.size(); ++c)
-        pool.emplace_back([&, c] {
-            try {
-                f(chunks[c]);
-            } catch (...) {
-                chunks[c].err = std::current_exception();
-            }
-        });
-    try {
-        f(chunks[0]);
-    } catch (...) {
-        chunks[0].err = std::current_exception();
-    }
-    for (auto &t : pool) t.join();
-    for (auto &c : chunks)
-        if (c.err) std::rethrow_exception(c.err);
-}
-
 }  // namespace
 
 BlockTable build_block_table(const index_loader::GofMap &gof, std::string_view gff, size_t threads) {
@@ -165,7 +137,8 @@ BlockTable build_block_table(const index_loader::GofMap &gof, std::string_view g
         }
     }
     // phase 1 (parallel): parse
-    run_chunks(chunks, [&](Chunk &ch) {
+    parallel_for(chunks.size(), chunks.size(), [&](size_t c) {  // (one thread per chunk, here and below)
+        Chunk &ch = chunks[c];
         ch.per_block.reserve(ch.b1 - ch.b0);
         for (size_t b = ch.b0; b < ch.b1; ++b) {
             const auto &g = gof.entries[blocks[b]];
@@ -226,7 +199,8 @@ BlockTable build_block_table(const index_loader::GofMap &gof, std::string_view g
         }
     }
     // phase 3a (parallel): group every block's lines by ID (stable: the first line of an ID names the group's chrom)
-    run_chunks(chunks, [&](Chunk &ch) {
+    parallel_for(chunks.size(), chunks.size(), [&](size_t c) {
+        Chunk &ch = chunks[c];
         size_t a = 0;
         ch.groups_per_block.reserve(ch.per_block.size());
         for (uint32_t n : ch.per_block) {
@@ -259,8 +233,8 @@ BlockTable build_block_table(const index_loader::GofMap &gof, std::string_view g
     t.block_line_off.resize(blocks.size() + 1);
     t.block_line_off[0] = 0;
     // phase 3b (parallel): fill the flat arrays
-    run_chunks(chunks, [&](Chunk &ch) {
-        const size_t c = static_cast<size_t>(&ch - chunks.data());
+    parallel_for(chunks.size(), chunks.size(), [&](size_t c) {
+        Chunk &ch = chunks[c];
         size_t l = line_base[c], g = group_base[c], a = 0;
         for (size_t b = 0; b < ch.per_block.size(); ++b) {
             const uint32_t n = ch.per_block[b];
@@ -298,31 +272,6 @@ void put_section(std::string &out, const T *p, size_t n) {
     while (out.size() % 8) out.push_back('\0');
 }
 }  // namespace
-
-// What an image is valid for: the .gof records (FNV-1a over every field) and the GFF's size and modification time.  A
-// same-length edit of the GFF, a re-index by the reference's own `gffx index` (it rewrites .gof) or a copied file all
-// change it; the reader then parses the GFF, as the reference does on every run (depth.rs:131-152, coverage.rs:296-337).
-uint64_t line_table_key(const std::string &gff_path, const index_loader::GofMap &gof) {
-    uint64_t h = 1469598103934665603ull;
-    auto mix = [&](uint64_t v) {
-        for (int b = 0; b < 8; ++b) {
-            h ^= (v >> (8 * b)) & 255u;
-            h *= 1099511628211ull;
-        }
-    };
-    for (const auto &g : gof.entries) {
-        mix(static_cast<uint64_t>(g.feature_id) | (static_cast<uint64_t>(g.seqid_num) << 32));
-        mix(g.start_offset);
-        mix(g.end_offset);
-    }
-    struct stat st;
-    if (::stat(gff_path.c_str(), &st) == 0) {
-        mix(static_cast<uint64_t>(st.st_size));
-        mix(static_cast<uint64_t>(st.st_mtim.tv_sec));
-        mix(static_cast<uint64_t>(st.st_mtim.tv_nsec));
-    }
-    return h;
-}
 
 void write_block_table(const std::string &path, const BlockTable &t, uint64_t gff_bytes, uint64_t gof_bytes) {
     std::string out(kMagic, 8);
@@ -422,7 +371,7 @@ bool load_block_table(const std::string &path, uint64_t gff_bytes, uint64_t gof_
 
 BlockTable load_or_build_block_table(const std::string &gff_path, const index_loader::GofMap &gof, std::string_view gff,
                                      size_t threads, bool verbose) {
-    const uint64_t gof_bytes = line_table_key(gff_path, gof);  // (the header's second word: content key since version 2)
+    const uint64_t gof_bytes = index_loader::line_table_key(gff_path, gof);  // (the header's second word: content key since version 2)
     BlockTable t;
     std::string why;
     const char *off = std::getenv("GFFX_LINE_TABLE");  // "parse" = ignore the image
@@ -434,6 +383,4 @@ BlockTable load_or_build_block_table(const std::string &gff_path, const index_lo
     return build_block_table(gof, gff, threads);
 }
 
-}  // namespace depth
-}  // namespace commands
-}  // namespace gffx
+}  // namespace gffx::commands::depth

@@ -60,14 +60,7 @@ extern "C" int gffx_host_parse_bed_file(const char *gff, const char *bed, uint32
     return guard(err, errlen, [&] {
         const auto sqs = index_loader::load_sqs(gff);
         const auto r = commands::intersect::parse_bed_file(bed, sqs.second, 5);  // (5 host threads once the file is > 1 MiB)
-        std::vector<uint32_t> flat;
-        flat.reserve(r.size() * 3);
-        for (const auto &[c, s, e] : r) {
-            flat.push_back(c);
-            flat.push_back(s);
-            flat.push_back(e);
-        }
-        *regions = dup_vec(flat);
+        *regions = dup_vec(commands::intersect::flatten(r));
         *n_regions = r.size();
     });
 }
@@ -157,14 +150,7 @@ extern "C" int gffx_host_depth_parse_bed(const char *gff, const char *bed, uint3
     return guard(err, errlen, [&] {
         const auto sqs = index_loader::load_sqs(gff);
         const auto r = commands::depth::parse_bed_rows(bed, sqs.second, 5);
-        std::vector<uint32_t> flat;
-        flat.reserve(r.size() * 3);
-        for (const auto &[c, s, e] : r) {
-            flat.push_back(c);
-            flat.push_back(s);
-            flat.push_back(e);
-        }
-        *regions = dup_vec(flat);
+        *regions = dup_vec(commands::intersect::flatten(r));
         *n_regions = r.size();
     });
 }
@@ -214,7 +200,7 @@ extern "C" int gffx_host_line_table_check(const char *gff, uint32_t threads, cha
         const MappedFile text(gff);
         commands::depth::BlockTable img;
         std::string why;
-        if (!commands::depth::load_block_table(append_suffix(gff, ".lsoa"), text.size(), commands::depth::line_table_key(gff, gof), img, why)) {
+        if (!commands::depth::load_block_table(append_suffix(gff, ".lsoa"), text.size(), index_loader::line_table_key(gff, gof), img, why)) {
             if (err && errlen) std::snprintf(err, errlen, "%s", why.c_str());
             return;
         }
@@ -237,7 +223,7 @@ extern "C" int gffx_host_all_lines_check(const char *gff, const char *types, uin
         const std::string_view data = text.view();
         ci::AllLinesView view;
         std::string why;
-        if (!view.open(append_suffix(gff, ".lall"), text.size(), commands::depth::line_table_key(gff, gof), why)) {
+        if (!view.open(append_suffix(gff, ".lall"), text.size(), index_loader::line_table_key(gff, gof), why)) {
             if (err && errlen) std::snprintf(err, errlen, "%s", why.c_str());
             return;
         }

@@ -162,7 +162,7 @@ void write_segments(const uint8_t *base, const std::vector<std::pair<uint64_t, u
         if (m != MAP_FAILED) {
             uint8_t *out = static_cast<uint8_t *>(m);
             const size_t W = std::max<size_t>(1, std::min<size_t>(threads, 32));
-            auto copy = [&](size_t t) {  // thread t takes the segments whose first byte lies in its share of the output
+            parallel_for(W, W, [&](size_t t) {  // thread t takes the segments whose first byte lies in its share of the output
                 const uint64_t lo = total * t / W, hi = total * (t + 1) / W;
                 if (populate) {
                     const uint64_t plo = lo & ~4095ull, phi = t + 1 == W ? total : hi & ~4095ull;
@@ -170,11 +170,7 @@ void write_segments(const uint8_t *base, const std::vector<std::pair<uint64_t, u
                 }
                 size_t i = static_cast<size_t>(std::lower_bound(dst.begin(), dst.end() - 1, lo) - dst.begin());
                 for (; i < seg.size() && dst[i] < hi; ++i) std::memcpy(out + dst[i], base + seg[i].first, static_cast<size_t>(seg[i].second));
-            };
-            std::vector<std::thread> pool;
-            for (size_t t = 1; t < W; ++t) pool.emplace_back(copy, t);
-            copy(0);
-            for (auto &th : pool) th.join();
+            });
             const bool bad = ::munmap(m, total) != 0;
             if (::close(fd) != 0 || bad) throw Error("write failed");
             return;
@@ -182,7 +178,7 @@ void write_segments(const uint8_t *base, const std::vector<std::pair<uint64_t, u
     }
     const size_t T = total < (32u << 20) ? 1 : std::max<size_t>(1, std::min<size_t>(threads, no_map ? 32 : 8));
     std::atomic<bool> failed{false};
-    auto work = [&](size_t t) {
+    parallel_for(T, T, [&](size_t t) {
         // thread t takes the segments whose first byte lies in its share of the output
         const uint64_t lo = total * t / T, hi = total * (t + 1) / T;
         size_t i = static_cast<size_t>(std::lower_bound(dst.begin(), dst.end() - 1, lo) - dst.begin());
@@ -201,11 +197,7 @@ void write_segments(const uint8_t *base, const std::vector<std::pair<uint64_t, u
                 left -= static_cast<uint64_t>(w);
             }
         }
-    };
-    std::vector<std::thread> pool;
-    for (size_t t = 1; t < T; ++t) pool.emplace_back(work, t);
-    work(0);
-    for (auto &th : pool) th.join();
+    });
     const bool bad_close = ::close(fd) != 0;
     if (failed || bad_close) throw Error("write failed");
 }

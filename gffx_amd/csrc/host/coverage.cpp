@@ -12,13 +12,9 @@
 
 #include "gffx.hpp"
 
-namespace gffx {
-namespace commands {
-namespace coverage {
+namespace gffx::commands::coverage {
 
 namespace {
-
-[[noreturn]] void hip_fail(const char *what) { throw Error(std::string(what) + ": " + gffx_hip_last_error()); }
 
 using Span = std::pair<uint32_t, uint32_t>;
 
@@ -56,46 +52,32 @@ uint64_t covered(const std::vector<Span> &cov, uint32_t a, uint32_t b) {  // cov
 void run(const CoverageArgs &args) {
     const bool verbose = args.verbose;
     StageTimer timer{verbose};
-    std::string ext;  // coverage.rs:520-541: dispatch on the source's extension
-    {
-        const size_t slash = args.source.find_last_of('/');
-        const std::string base = slash == std::string::npos ? args.source : args.source.substr(slash + 1);
-        const size_t dot = base.find_last_of('.');
-        if (dot != std::string::npos && dot > 0) ext = base.substr(dot + 1);
-        for (char &c : ext) c = static_cast<char>(std::tolower(static_cast<unsigned char>(c)));
-    }
     const index_loader::GofMap gof = index_loader::load_gof(args.input);  // :501
-    MappedFile gff;
-    try {
-        gff = MappedFile(args.input);  // :502-503
-    } catch (const Error &) {
-        throw Error("Cannot open GFF file: \"" + args.input + "\"");
-    }
+    const MappedFile gff = map_file_or(args.input, "Cannot open GFF file: \"" + args.input + "\"");  // :502-503
     DeviceWarmup warm(args.device);  // (the runtime comes up beside the loaders and the BED parser)
     TreeIndexData index_data = TreeIndexData::load_tree_index(args.input);  // :511
-    if (ext == "sam" || ext == "cram")
-        throw Error("SAM/CRAM sources need htslib, which this build does not carry; use a .bam or .bed source");
-    if (ext != "bed" && ext != "bam")
-        throw Error("Unsupported file type: \"" + args.source + "\". Expected .bam/.sam/.cram or .bed");  // :535-540
-    std::vector<intersect::Region> regions;
-    if (ext == "bam") {  // coverage.rs:125-168: the same (chr, start, end) rows, from BAM records
-        warm.wait();
-        const std::vector<uint32_t> flat = bam::read_rows(args.source, index_data.seqid_to_num, args.device, verbose);
-        regions.reserve(flat.size() / 3);
-        for (size_t i = 0; i + 2 < flat.size(); i += 3) regions.emplace_back(flat[i], flat[i + 1], flat[i + 2]);
-    } else {
-        regions = depth::parse_bed_rows(args.source, index_data.seqid_to_num, capped_threads(args.threads));  // :230-256
-    }
-    if (verbose) std::fprintf(stderr, "[INFO] %zu %s rows kept\n", regions.size(), ext == "bam" ? "BAM" : "BED");
-    timer.lap(ext == "bam" ? "Loading index + reading BAM" : "Loading index + parsing BED");
+    const depth::SourceKind kind = depth::source_kind(args.source);  // coverage.rs:520-541
+    const bool bam = kind == depth::SourceKind::Bam;
+    // the kept rows as flat (seqid number, start, end) words, from the source to the device (there is always a first piece)
+    std::vector<std::vector<uint32_t>> part =
+        depth::read_source_rows(kind, args.source, index_data.seqid_to_num, capped_threads(args.threads), args.device, verbose, warm);
+    std::vector<uint32_t> flat = std::move(part[0]);
+    size_t words = flat.size();
+    for (size_t p = 1; p < part.size(); ++p) words += part[p].size();
+    flat.reserve(words);
+    for (size_t p = 1; p < part.size(); ++p) flat.insert(flat.end(), part[p].begin(), part[p].end());
+    part.clear();
+    const size_t n_regions = flat.size() / 3;
+    if (verbose) std::fprintf(stderr, "[INFO] %zu %s rows kept\n", n_regions, bam ? "BAM" : "BED");
+    timer.lap(bam ? "Loading index + reading BAM" : "Loading index + parsing BED");
 
     std::string out = "id\tchr\tstart\tend\tbreadth\tfraction\n";  // :463
     size_t written = 0;
-    if (!regions.empty()) {
+    if (n_regions) {
         // which roots are hit (by_root's key set, coverage.rs:258-268): Join A's unique-root output
         warm.wait();
         const std::vector<uint32_t> hit_roots =
-            intersect::query_unique_roots(index_data, regions, intersect::OverlapMode::Overlap, false, verbose, args.device);
+            intersect::query_unique_roots(index_data, flat.data(), n_regions, intersect::OverlapMode::Overlap, false, verbose, args.device);
         timer.lap("Join A on the device (root bitmap)");
         const depth::BlockTable t = depth::load_or_build_block_table(args.input, gof, gff.view(), capped_threads(args.threads), verbose);
         timer.lap("Line table (image or parse)");
@@ -156,15 +138,9 @@ void run(const CoverageArgs &args) {
                          segs.size(), segs.size() - seg_seq.size());
         timer.lap("Segments of the hit blocks");
         // device: covered bases of the segments inside their root, under the union of all regions of the seqid
-        std::vector<uint32_t> flat(3 * regions.size());
-        for (size_t i = 0; i < regions.size(); ++i) {
-            flat[3 * i] = std::get<0>(regions[i]);
-            flat[3 * i + 1] = std::get<1>(regions[i]);
-            flat[3 * i + 2] = std::get<2>(regions[i]);
-        }
         std::vector<uint32_t> cov_fast(std::max<size_t>(seg_seq.size(), 1), 0);
         if (gffx_hip_segments_covered(args.device, seg_seq.size(), seg_seq.data(), seg_start.data(), seg_end.data(), flat.data(),
-                                      regions.size(), n_seq, cov_fast.data()) != GFFX_OK)
+                                      n_regions, n_seq, cov_fast.data()) != GFFX_OK)
             hip_fail("gffx_hip_segments_covered");
         timer.lap("Covered bases on the device (union build, upload, kernel, D2H)");
         // host: the segments that stick out of their root, against the root's own merged list (coverage.rs:401)
@@ -183,10 +159,10 @@ void run(const CoverageArgs &args) {
             auto it = root_cov.find(b);
             if (it == root_cov.end()) {
                 std::vector<Span> hit;
-                for (const auto &rg : regions)
+                for (const uint32_t *rg = flat.data(); rg < flat.data() + 3 * n_regions; rg += 3)
                     for (const auto &iv : ivs[block_fid[b]])
-                        if (std::get<0>(rg) == std::get<0>(iv) && std::get<1>(iv) < std::get<2>(rg) && std::get<2>(iv) > std::get<1>(rg)) {
-                            hit.emplace_back(std::get<1>(rg), std::get<2>(rg));  // a region once per root (coverage.rs:263-266)
+                        if (rg[0] == std::get<0>(iv) && std::get<1>(iv) < rg[2] && std::get<2>(iv) > rg[1]) {
+                            hit.emplace_back(rg[1], rg[2]);  // a region once per root (coverage.rs:263-266)
                             break;
                         }
                 it = root_cov.emplace(b, merge_intervals(std::move(hit))).first;
@@ -251,6 +227,4 @@ void run(const CoverageArgs &args) {
     g_run_stats.write("coverage", timer.total());
 }
 
-}  // namespace coverage
-}  // namespace commands
-}  // namespace gffx
+}  // namespace gffx::commands::coverage

@@ -5,25 +5,18 @@
 //   write_depth_results    depth.rs:515-546   "id\tchr\tstart\tend\tdepth" rows
 // The reference re-parses a root's byte block for every batch that touches it; here every block is
 // parsed ONCE into the device line table (include/gffx_hip.h "gffx depth"), the regions stream through
-// Join A in batches, and k_depth_regions accumulates per (block, ID) group.  BAM/SAM/CRAM sources need
-// htslib, which this build does not carry: they are refused with a clear message.
+// Join A in batches, and k_depth_regions accumulates per (block, ID) group.  (SAM/CRAM sources need htslib: refused.)
 #include <algorithm>
+#include <cctype>
 #include <cstdio>
-#include <thread>
-
-#include <atomic>
 #include <cstring>
 
 #include "fast_fields.hpp"
 #include "gffx.hpp"
 
-namespace gffx {
-namespace commands {
-namespace depth {
+namespace gffx::commands::depth {
 
 namespace {
-
-[[noreturn, maybe_unused]] void hip_fail(const char *what) { throw Error(std::string(what) + ": " + gffx_hip_last_error()); }
 
 std::string_view trim_end_unicode_ws(std::string_view s) {  // str::trim_end()
     for (;;) {
@@ -142,12 +135,7 @@ void parse_rows_chunk(std::string_view d, size_t pos, size_t z, const std::unord
 // (cut at line starts and parsed on up to `threads` host threads; part[c] = the rows of the c-th cut as flat triples, file order)
 std::vector<std::vector<uint32_t>> parse_bed_rows_flat(const std::string &bed_path, const std::unordered_map<std::string, uint32_t> &seqid_to_num,
                                                        size_t threads) {
-    MappedFile f;
-    try {
-        f = MappedFile(bed_path);
-    } catch (const Error &) {
-        throw Error("No such file or directory (os error 2)");  // File::open(bed_path)? (depth.rs:441)
-    }
+    const MappedFile f = map_file_or(bed_path, "No such file or directory (os error 2)");  // File::open(bed_path)? (depth.rs:441)
     const std::string_view d = f.view();
     ShortNameTable short_names;
     short_names.build(seqid_to_num);
@@ -157,74 +145,61 @@ std::vector<std::vector<uint32_t>> parse_bed_rows_flat(const std::string &bed_pa
     const std::vector<size_t> cut = intersect::line_chunks(d, parts);
     const size_t n = cut.size() - 1;
     std::vector<std::vector<uint32_t>> part(n);
-    std::atomic<size_t> next{0};
-    auto work = [&] {
-        for (;;) {
-            const size_t c = next.fetch_add(1);
-            if (c >= n) return;
-            part[c].reserve((cut[c + 1] - cut[c]) / 8);
-            parse_rows_chunk(d, cut[c], cut[c + 1], seqid_to_num, short_names, part[c]);
-        }
-    };
-    std::vector<std::thread> pool;
-    for (size_t t = 1; t < workers && t < n; ++t) pool.emplace_back(work);
-    work();
-    for (auto &t : pool) t.join();
+    parallel_for(n, workers, [&](size_t c) {
+        part[c].reserve((cut[c + 1] - cut[c]) / 8);
+        parse_rows_chunk(d, cut[c], cut[c + 1], seqid_to_num, short_names, part[c]);
+    });
     return part;
 }
 
 std::vector<intersect::Region> parse_bed_rows(const std::string &bed_path,
                                               const std::unordered_map<std::string, uint32_t> &seqid_to_num, size_t threads) {
-    const std::vector<std::vector<uint32_t>> part = parse_bed_rows_flat(bed_path, seqid_to_num, threads);
-    size_t total = 0;
-    for (const auto &v : part) total += v.size() / 3;
-    std::vector<intersect::Region> out;
-    out.reserve(total);
-    for (const auto &v : part)
-        for (size_t i = 0; i + 2 < v.size(); i += 3) out.emplace_back(v[i], v[i + 1], v[i + 2]);
-    return out;
+    return intersect::regions_of(parse_bed_rows_flat(bed_path, seqid_to_num, threads));
+}
+
+SourceKind source_kind(const std::string &path) {
+    const size_t slash = path.rfind('/');
+    const std::string base = slash == std::string::npos ? path : path.substr(slash + 1);
+    const size_t dot = base.find_last_of('.');
+    std::string ext;
+    if (dot != std::string::npos && dot > 0) ext = base.substr(dot + 1);
+    for (char &c : ext) c = static_cast<char>(std::tolower(static_cast<unsigned char>(c)));
+    if (ext == "sam" || ext == "cram")
+        throw Error("SAM/CRAM sources need htslib, which this build does not carry; use a .bam or .bed source");
+    if (ext != "bed" && ext != "bam")
+        throw Error("Unsupported file type: \"" + path + "\". Expected .bam/.sam/.cram or .bed");  // depth.rs:597-600, coverage.rs:535-540
+    return ext == "bam" ? SourceKind::Bam : SourceKind::Bed;
+}
+
+std::vector<std::vector<uint32_t>> read_source_rows(SourceKind kind, const std::string &path,
+                                                    const std::unordered_map<std::string, uint32_t> &seqid_to_num, size_t threads,
+                                                    int device, bool verbose, DeviceWarmup &warm) {
+    if (kind == SourceKind::Bed) return parse_bed_rows_flat(path, seqid_to_num, threads);  // depth.rs:450-495, coverage.rs:230-256
+    warm.wait();  // depth.rs:297-372, coverage.rs:125-168: the same (chr, start, end) rows, from BAM records
+    std::vector<std::vector<uint32_t>> part;
+    part.push_back(bam::read_rows(path, seqid_to_num, device, verbose));
+    return part;
 }
 
 void run(const DepthArgs &args) {
     const bool verbose = args.verbose;
     StageTimer timer{verbose};
-    // depth.rs:590-601: dispatch on the source's extension
-    std::string ext;
-    {
-        const size_t slash = args.source.find_last_of('/');
-        const std::string base = slash == std::string::npos ? args.source : args.source.substr(slash + 1);
-        const size_t dot = base.find_last_of('.');
-        if (dot != std::string::npos && dot > 0) ext = base.substr(dot + 1);
-        for (char &c : ext) c = static_cast<char>(std::tolower(static_cast<unsigned char>(c)));
-    }
     DeviceWarmup warm(args.device);  // (the runtime comes up beside the loaders and the BED parser)
     const index_loader::GofMap gof = index_loader::load_gof(args.input);  // :563
-    MappedFile gff;
-    try {
-        gff = MappedFile(args.input);  // :564-565
-    } catch (const Error &) {
-        throw Error("Cannot open GFF file: \"" + args.input + "\"");
-    }
+    const MappedFile gff = map_file_or(args.input, "Cannot open GFF file: \"" + args.input + "\"");  // :564-565
     TreeIndexData index_data = TreeIndexData::load_tree_index(args.input);  // :573
-    if (ext == "sam" || ext == "cram")
-        throw Error("SAM/CRAM sources need htslib, which this build does not carry; use a .bam or .bed source");
-    if (ext != "bed" && ext != "bam")
-        throw Error("Unsupported file type: \"" + args.source + "\". Expected .bam/.sam/.cram or .bed");  // :597-600
+    const SourceKind kind = source_kind(args.source);  // depth.rs:590-601
+    const bool bam = kind == SourceKind::Bam;
     timer.lap("Loading index");
     const size_t threads = capped_threads(args.threads);
     // the kept rows as flat triples, one vector per parsed piece (file order); part_row[p] = rows before piece p
-    std::vector<std::vector<uint32_t>> part;
-    if (ext == "bam") {  // depth.rs:297-372: the same (chr, start, end) rows, from BAM records
-        warm.wait();
-        part.push_back(bam::read_rows(args.source, index_data.seqid_to_num, args.device, verbose));
-    } else {
-        part = parse_bed_rows_flat(args.source, index_data.seqid_to_num, threads);
-    }
+    const std::vector<std::vector<uint32_t>> part =
+        read_source_rows(kind, args.source, index_data.seqid_to_num, threads, args.device, verbose, warm);
     std::vector<size_t> part_row(part.size() + 1, 0);
     for (size_t p = 0; p < part.size(); ++p) part_row[p + 1] = part_row[p] + part[p].size() / 3;
     const size_t n_rows = part_row.back();
-    if (verbose) std::fprintf(stderr, "[INFO] %zu %s rows kept\n", n_rows, ext == "bam" ? "BAM" : "BED");
-    timer.lap(ext == "bam" ? "Reading BAM" : "Parsing BED");
+    if (verbose) std::fprintf(stderr, "[INFO] %zu %s rows kept\n", n_rows, bam ? "BAM" : "BED");
+    timer.lap(bam ? "Reading BAM" : "Parsing BED");
 
     const BlockTable t = load_or_build_block_table(args.input, gof, gff.view(), threads, verbose);
     timer.lap("Line table (image or parse)");
@@ -236,72 +211,47 @@ void run(const DepthArgs &args) {
         // regions, so any partition of the rows gives the same rows out: depth.rs:264-291 merges its own batches the same
         // way); index and line table are replicated; one host thread drives each device.
         warm.wait();
-        const int visible = gffx_hip_device_count();
-        if (visible <= 0) throw Error("no HIP device visible (the engine has no CPU fallback)");
-        const size_t D = static_cast<size_t>(std::max(1, args.gpus));
-        std::vector<int> dev(D);
-        if (args.device < 0 || args.device >= visible)
-            throw Error("device " + std::to_string(args.device) + " out of range (" + std::to_string(visible) + " visible)");
-        for (size_t d = 0; d < D; ++d) dev[d] = (args.device + static_cast<int>(d)) % visible;  // (only the additional logical devices wrap)
-        bool distinct = true;
-        for (size_t d = 1; d < D; ++d)
-            for (size_t e = 0; e < d; ++e) distinct &= dev[d] != dev[e];
-        if (D > 1 && !distinct)
-            std::fprintf(stderr, "[WARN] --gpus %zu with %d visible device(s): logical devices share GPUs (no RCCL exchange)\n", D, visible);
-        index_data.ensure_device(dev[0]);
+        DeviceSet devs = DeviceSet::resolve(args.device, args.gpus);
+        const size_t D = devs.size();
+        index_data.ensure_device(devs[0]);
         struct PerDevice {
-            gffx_hip_index *ix = nullptr;  // clone (owned) unless it is the first device's
-            bool own_ix = false;
-            gffx_hip_depth *dt = nullptr;
-            gffx_hip_batch *b[2] = {nullptr, nullptr};
-            gffx_hip_regions *store = nullptr;  // two pinned staging buffers + a ring of two batch slots in HBM
+            DepthHandle dt;
+            RegionsHandle store;  // two pinned staging buffers + a ring of two batch slots in HBM
+            BatchHandle b[2];
             std::vector<uint64_t> depth;
             std::vector<uint32_t> mn, mx;
             uint64_t rows = 0;
-            std::string error;
-            ~PerDevice() {
-                for (gffx_hip_batch *x : b)
-                    if (x) gffx_hip_batch_destroy(x);
-                if (store) gffx_hip_regions_destroy(store);
-                if (dt) gffx_hip_depth_destroy(dt);
-                if (own_ix && ix) gffx_hip_index_destroy(ix);
-            }
         };
         std::vector<PerDevice> pd(D);
         // regions stream through Join A in batches (the reference's BATCH_SIZE, depth.rs:24, only bounds memory:
         // every merge is min / max / sum)
         const size_t kBatch = 4u << 20;
         const size_t cap = std::min(n_rows, kBatch);
-        auto device_work = [&](size_t d) {
+        // (one thread per device; a device's failure is an Error of its thread: the first device's in the list is reported)
+        parallel_for(D, D, [&](size_t d) {
             PerDevice &P = pd[d];
-            auto fail_hip = [&](const char *what) { P.error = std::string(what) + ": " + gffx_hip_last_error(); };
-            P.ix = index_data.device_index;
-            if (dev[d] != dev[0]) {
-                if (gffx_hip_index_clone(index_data.device_index, dev[d], &P.ix) != GFFX_OK) return fail_hip("gffx_hip_index_clone");
-                P.own_ix = true;
-            }
-            if (gffx_hip_depth_create(dev[d], n_groups, static_cast<uint32_t>(t.block_line_off.size() - 1), t.block_line_off.data(),
+            gffx_hip_index *ix = devs.index_on(d, index_data.device_index.get());
+            if (gffx_hip_depth_create(devs[d], n_groups, static_cast<uint32_t>(t.block_line_off.size() - 1), t.block_line_off.data(),
                                       t.line_start.data(), t.line_end.data(), t.line_group.data(),
-                                      static_cast<uint32_t>(t.block_of_fid.size()), t.block_of_fid.data(), &P.dt) != GFFX_OK)
-                return fail_hip("gffx_hip_depth_create");
-            if (gffx_hip_regions_create(dev[d], 0, cap, 0, &P.store) != GFFX_OK) return fail_hip("gffx_hip_regions_create");
+                                      static_cast<uint32_t>(t.block_of_fid.size()), t.block_of_fid.data(), OutPtr(P.dt)) != GFFX_OK)
+                hip_fail("gffx_hip_depth_create");
+            if (gffx_hip_regions_create(devs[d], 0, cap, 0, OutPtr(P.store)) != GFFX_OK) hip_fail("gffx_hip_regions_create");
             for (int k = 0; k < 2; ++k)
-                if (gffx_hip_batch_create(P.ix, cap, &P.b[k]) != GFFX_OK) return fail_hip("gffx_hip_batch_create");
+                if (gffx_hip_batch_create(ix, cap, OutPtr(P.b[k])) != GFFX_OK) hip_fail("gffx_hip_batch_create");
             // Batch i goes through staging buffer / batch i & 1: while its rows cross PCIe and Join A runs on them, the host
             // waits for batch i - 1 and adds its depth, then fills the other staging buffer.  (One batch at a time was 19 ms per
             // 4 M rows, nearly all of it the flat copy and the pageable upload.)
-            auto finish = [&](int k) -> bool {
-                if (gffx_hip_batch_wait(P.b[k]) != GFFX_OK) return fail_hip("query_features"), false;
-                if (gffx_hip_depth_accumulate(P.dt, P.b[k]) != GFFX_OK) return fail_hip("gffx_hip_depth_accumulate"), false;
-                return true;
+            auto finish = [&](int k) {
+                if (gffx_hip_batch_wait(P.b[k].get()) != GFFX_OK) hip_fail("query_features");
+                if (gffx_hip_depth_accumulate(P.dt.get(), P.b[k].get()) != GFFX_OK) hip_fail("gffx_hip_depth_accumulate");
             };
             const size_t fill_threads = std::max<size_t>(1, std::min<size_t>(threads / D, 8));
             size_t i = 0;
             for (size_t a = d * kBatch; a < n_rows; a += D * kBatch, ++i) {
                 const int k = static_cast<int>(i & 1);
                 const size_t n = std::min(kBatch, n_rows - a);
-                if (gffx_hip_regions_wait_staging(P.store, k) != GFFX_OK) return fail_hip("wait_staging");
-                uint32_t *stage = gffx_hip_regions_staging(P.store, k);
+                if (gffx_hip_regions_wait_staging(P.store.get(), k) != GFFX_OK) hip_fail("wait_staging");
+                uint32_t *stage = gffx_hip_regions_staging(P.store.get(), k);
                 // rows [a, a + n) of the file: the tails / heads of the pieces they lie in, copied by a few threads
                 struct Move {
                     const uint32_t *src;
@@ -315,41 +265,21 @@ void run(const DepthArgs &args) {
                         moves.push_back({part[p].data() + 3 * (from + x), done + x, std::min<size_t>(take - x, 1u << 18)});
                     done += take;
                 }
-                std::atomic<size_t> next_move{0};
-                auto fill = [&] {
-                    for (;;) {
-                        const size_t m = next_move.fetch_add(1);
-                        if (m >= moves.size()) return;
-                        std::memcpy(stage + 3 * moves[m].at, moves[m].src, moves[m].rows * 12);
-                    }
-                };
-                {
-                    std::vector<std::thread> pool;
-                    for (size_t w = 1; w < fill_threads && w < moves.size(); ++w) pool.emplace_back(fill);
-                    fill();
-                    for (auto &th : pool) th.join();
-                }
-                if (gffx_hip_regions_append(P.store, k, n) != GFFX_OK) return fail_hip("regions_append");
-                if (gffx_hip_batch_set_regions_store(P.b[k], P.store, k, 0, n) != GFFX_OK) return fail_hip("set_regions_store");
-                if (gffx_hip_batch_run(P.b[k], GFFX_MODE_OVERLAP, 0, GFFX_OUT_FIDS | GFFX_OUT_OFFSETS, GFFX_STRATEGY_AUTO) != GFFX_OK)
-                    return fail_hip("gffx_hip_batch_run");
-                if (i > 0 && !finish(1 - k)) return;
+                parallel_for(moves.size(), fill_threads,
+                             [&](size_t m) { std::memcpy(stage + 3 * moves[m].at, moves[m].src, moves[m].rows * 12); });
+                if (gffx_hip_regions_append(P.store.get(), k, n) != GFFX_OK) hip_fail("regions_append");
+                if (gffx_hip_batch_set_regions_store(P.b[k].get(), P.store.get(), k, 0, n) != GFFX_OK) hip_fail("set_regions_store");
+                if (gffx_hip_batch_run(P.b[k].get(), GFFX_MODE_OVERLAP, 0, GFFX_OUT_FIDS | GFFX_OUT_OFFSETS, GFFX_STRATEGY_AUTO) != GFFX_OK)
+                    hip_fail("gffx_hip_batch_run");
+                if (i > 0) finish(1 - k);
                 P.rows += n;
             }
-            if (i > 0 && !finish(static_cast<int>((i - 1) & 1))) return;
+            if (i > 0) finish(static_cast<int>((i - 1) & 1));
             P.depth.assign(std::max<size_t>(n_groups, 1), 0);
             P.mn.assign(std::max<size_t>(n_groups, 1), 0xFFFFFFFFu);
             P.mx.assign(std::max<size_t>(n_groups, 1), 0);
-            if (gffx_hip_depth_copy(P.dt, P.depth.data(), P.mn.data(), P.mx.data()) != GFFX_OK) return fail_hip("gffx_hip_depth_copy");
-        };
-        {
-            std::vector<std::thread> pool;
-            for (size_t d = 1; d < D; ++d) pool.emplace_back(device_work, d);
-            device_work(0);
-            for (auto &th : pool) th.join();
-        }
-        for (size_t d = 0; d < D; ++d)
-            if (!pd[d].error.empty()) throw Error(pd[d].error);
+            if (gffx_hip_depth_copy(P.dt.get(), P.depth.data(), P.mn.data(), P.mx.data()) != GFFX_OK) hip_fail("gffx_hip_depth_copy");
+        });
         std::vector<uint64_t> counts(2 * D, 0);
         for (size_t d = 0; d < D; ++d) {  // merge: sum of depths, min / max of the extents
             const PerDevice &P = pd[d];
@@ -361,21 +291,8 @@ void run(const DepthArgs &args) {
                 counts[2 * d + 1] += P.depth[g];
             }
         }
-        if (D > 1) {  // the exchange step: per-device {rows, group hits}, all-gathered over RCCL when the devices are distinct
-            std::vector<uint64_t> gathered(2 * D * D, 0);
-            // (the rows are complete on the host by now: a failing exchange is a warning, not the loss of the run)
-            bool exchanged = false;
-            if (distinct) {
-                if (gffx_hip_allgather_counts(static_cast<int>(D), dev.data(), counts.data(), gathered.data()) != GFFX_OK)
-                    std::fprintf(stderr, "[WARN] hit-count all-gather over RCCL failed: %s\n", gffx_hip_last_error());
-                else
-                    exchanged = true;
-            }
-            if (verbose)
-                for (size_t d = 0; d < D; ++d)
-                    std::fprintf(stderr, "[INFO] device %d: %llu BED rows, %llu group hits%s\n", dev[d], (unsigned long long)counts[2 * d],
-                                 (unsigned long long)counts[2 * d + 1], exchanged ? " (all-gathered over RCCL)" : "");
-        }
+        // the exchange step: per-device {rows, group hits} (the rows out are complete on the host by now)
+        if (D > 1) devs.exchange_counts(counts, "BED rows", "group hits", verbose, /*adopt_gathered=*/false);
     }
     timer.lap("Join A + depth on the device (uploads, kernels, results D2H)");
     // merge the groups of an ID (depth.rs:264-291): min start, max end, summed depth; chrom from the first
@@ -431,6 +348,4 @@ void run(const DepthArgs &args) {
     g_run_stats.write("depth", timer.total());
 }
 
-}  // namespace depth
-}  // namespace commands
-}  // namespace gffx
+}  // namespace gffx::commands::depth

@@ -1,5 +1,5 @@
 // fast_fields.hpp -- the fields of a plain BED row eight bytes at a time (little-endian words): the row parsers of
-// `intersect` (host/intersect.cpp::parse_bed_chunk, intersect.rs:201-230) and `depth` / `coverage`
+// `intersect` (host/bed_parse.cpp::parse_bed_chunk, intersect.rs:201-230) and `depth` / `coverage`
 // (host/depth.cpp::parse_rows_chunk, depth.rs:450-495) try this shape first -- a name of 1-7 bytes, TAB, 1-9 digits, TAB,
 // 1-9 digits -- and fall back to their byte loops, which implement the reference's rules in full, for anything else.
 #pragma once

@@ -6,6 +6,7 @@
 //   gffx::TreeIndexData                                                          utils/tree_index.rs
 //   gffx::commands::intersect::{OverlapMode, IntersectArgs, parse_region, parse_bed_file,
 //        query_features, gff_type_allowed, write_gff_match_only_by_coords, run}  commands/intersect.rs
+//        (intersect.cpp, bed_parse.cpp, shard.cpp, join_a_stream.cpp, match_lines.cpp)
 //   gffx::commands::depth::{DepthArgs, parse_bed_rows, run}                      commands/depth.rs (BED source)
 //   gffx::commands::coverage::{CoverageArgs, run}                                commands/coverage.rs (BED source)
 //   gffx::bam::read_rows                                                         depth.rs:297-372 / coverage.rs:125-168 (BAM source)
@@ -24,7 +25,8 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../../include/gffx_hip.h"
+#include "device_set.hpp"
+#include "parallel.hpp"
 #include "text.hpp"
 
 namespace gffx {
@@ -87,14 +89,10 @@ template <typename F>
 void append_rows_parallel(std::string &out, size_t n, size_t threads, F &&format_row) {
     const size_t parts = n < 20000 ? 1 : std::max<size_t>(1, std::min<size_t>(threads, 64));
     std::vector<std::string> piece(parts);
-    auto work = [&](size_t p) {
+    parallel_for(parts, parts, [&](size_t p) {
         std::string &s = piece[p];
         for (size_t i = n * p / parts; i < n * (p + 1) / parts; ++i) format_row(i, s);
-    };
-    std::vector<std::thread> pool;
-    for (size_t p = 1; p < parts; ++p) pool.emplace_back(work, p);
-    work(0);
-    for (auto &t : pool) t.join();
+    });
     size_t total = out.size();
     for (const auto &s : piece) total += s.size();
     out.reserve(total);
@@ -165,6 +163,8 @@ class GofMap {  // gof.rs:20-93
 };
 
 GofMap load_gof(const std::string &gff);  // gof.rs:95-128
+// what the line-table images `<gff>.lsoa` / `<gff>.lall` are valid for: FNV-1a of the .gof records + the GFF's size and mtime
+uint64_t line_table_key(const std::string &gff_path, const GofMap &gof);
 
 struct RootInterval {  // utils/tree.rs:5-10 Interval<u32>
     uint32_t start, end, root_fid;
@@ -181,13 +181,7 @@ struct TreeIndexData {
     std::unordered_map<std::string, uint32_t> seqid_to_num;
     std::vector<std::string> num_to_seqid;
     std::vector<uint32_t> chr_offsets, start, end, root_fid;  // builder order inside a seqid
-    gffx_hip_index *device_index = nullptr;                   // created lazily by ensure_device()
-
-    TreeIndexData() = default;
-    TreeIndexData(const TreeIndexData &) = delete;
-    TreeIndexData &operator=(const TreeIndexData &) = delete;
-    TreeIndexData(TreeIndexData &&o) noexcept;
-    ~TreeIndexData();
+    IndexHandle device_index;                                 // created lazily by ensure_device()
 
     // tree_index.rs:21-34: .sqs + .rit/.rix (layout unpinned, see index_loader.cpp); when the images are
     // absent or do not parse, the interval lists are rebuilt from .gof + the root lines of the GFF
@@ -224,6 +218,9 @@ std::vector<Region> parse_bed_file(const std::string &bed_path, const std::unord
 std::vector<uint32_t> parse_bed_file_chunked(const std::string &bed_path, const std::unordered_map<std::string, uint32_t> &seqid_map,
                                              size_t threads, size_t chunk_bytes);  // :201-230
 std::vector<size_t> line_chunks(std::string_view d, size_t parts);  // cut points at line starts (parallel parsers)
+// Region tuples <-> flat (chr, start, end) words, the layout the device reads (the words in pieces, in order)
+std::vector<uint32_t> flatten(const std::vector<Region> &regions);
+std::vector<Region> regions_of(const std::vector<std::vector<uint32_t>> &pieces);
 
 // intersect.rs:105-169 on the device: one (root_fid, iv.start, iv.end) per kept pair.
 std::vector<Region> query_features(TreeIndexData &index_data, const std::vector<Region> &regions,
@@ -231,6 +228,8 @@ std::vector<Region> query_features(TreeIndexData &index_data, const std::vector<
 // What run() needs from Join A: the unique root fids (intersect.rs:598-615), via the root bitmap.
 std::vector<uint32_t> query_unique_roots(TreeIndexData &index_data, const std::vector<Region> &regions,
                                          OverlapMode mode, bool invert, bool verbose, int device = 0);
+std::vector<uint32_t> query_unique_roots(TreeIndexData &index_data, const uint32_t *flat, uint64_t n_regions, OverlapMode mode,
+                                         bool invert, bool verbose, int device = 0);  // the regions as flat (chr, start, end) words
 
 bool gff_type_allowed(std::string_view line, const std::vector<std::string> &allow);  // :80-102
 
@@ -299,7 +298,7 @@ struct StreamResult {
     std::vector<uint64_t> per_device;  // {regions, kept pairs} per logical device: with --gpus N on N distinct devices what the RCCL
     bool exchanged = false;            // all-gather RETURNED (exchanged), otherwise the host's own counts
     std::string knobs = "{}";          // GFFX_HIP_* knobs of the index / the batches that were not at their defaults
-    gffx_hip_regions *store = nullptr; // keep_store: all regions, on the first device (the caller destroys it)
+    RegionsHandle store;               // keep_store: all regions, on the first device
 };
 StreamResult stream_unique_roots(TreeIndexData &index_data, const std::string &bed_path, OverlapMode mode, bool invert, bool verbose,
                                  size_t threads, int device, int n_gpus, bool keep_store);
@@ -328,6 +327,12 @@ std::vector<intersect::Region> parse_bed_rows(const std::string &bed_path,
 // ... as flat (seqid number, start, end) words, one vector per parsed piece of the file, in file order
 std::vector<std::vector<uint32_t>> parse_bed_rows_flat(const std::string &bed_path, const std::unordered_map<std::string, uint32_t> &seqid_to_num,
                                                        size_t threads = 1);
+enum class SourceKind { Bed, Bam };
+SourceKind source_kind(const std::string &path);  // depth.rs:590-601 / coverage.rs:520-541: by the extension, any letter case; others: Error
+// the kept rows of a .bed (on `threads` host threads) or .bam (inflated on `device` once `warm` is through), flat, in pieces, in file order
+std::vector<std::vector<uint32_t>> read_source_rows(SourceKind kind, const std::string &path,
+                                                    const std::unordered_map<std::string, uint32_t> &seqid_to_num, size_t threads,
+                                                    int device, bool verbose, DeviceWarmup &warm);
 struct BlockTable {  // the device line table (include/gffx_hip.h "gffx depth") + what names the groups
     std::vector<uint64_t> block_line_off{0};
     std::vector<uint32_t> line_start, line_end, line_group, block_of_fid;
@@ -342,8 +347,7 @@ struct BlockTable {  // the device line table (include/gffx_hip.h "gffx depth") 
 // depth.rs:131-152 on every root block (the LAST .gof record of a root_fid): the lines that carry an ID
 BlockTable build_block_table(const index_loader::GofMap &gof, std::string_view gff, size_t threads = 1);
 // the same table as a flat image `<gff>.lsoa` (written by `gffx index`; block_table.cpp has the layout)
-// (gof_key = line_table_key(): FNV-1a of the .gof records + the GFF's size and mtime)
-uint64_t line_table_key(const std::string &gff_path, const index_loader::GofMap &gof);
+// (gof_key = index_loader::line_table_key())
 void write_block_table(const std::string &path, const BlockTable &t, uint64_t gff_bytes, uint64_t gof_key);
 bool load_block_table(const std::string &path, uint64_t gff_bytes, uint64_t gof_key, BlockTable &t, std::string &why);
 BlockTable load_or_build_block_table(const std::string &gff_path, const index_loader::GofMap &gof, std::string_view gff,

@@ -4,6 +4,8 @@
 #include <cstdlib>
 #include <functional>
 
+#include <sys/stat.h>
+
 #include "gffx.hpp"
 
 namespace gffx {
@@ -11,12 +13,7 @@ namespace index_loader {
 
 std::pair<std::vector<std::string>, std::unordered_map<std::string, uint32_t>> load_sqs(const std::string &gff) {
     const std::string path = append_suffix(gff, ".sqs");
-    MappedFile f;
-    try {
-        f = MappedFile(path);
-    } catch (const Error &) {
-        throw Error("Failed to open SQS file: \"" + path + "\"");
-    }
+    const MappedFile f = map_file_or(path, "Failed to open SQS file: \"" + path + "\"");
     std::vector<std::string> id_to_name;  // BufRead::lines(): strips "\n" and "\r\n"
     const std::string_view d = f.view();
     size_t a = 0;
@@ -59,12 +56,7 @@ std::vector<Block> GofMap::roots_to_offsets(const std::vector<uint32_t> &roots, 
 
 GofMap load_gof(const std::string &gff) {
     const std::string path = append_suffix(gff, ".gof");
-    MappedFile f;
-    try {
-        f = MappedFile(path);
-    } catch (const Error &) {
-        throw Error("Failed to mmap " + path);
-    }
+    const MappedFile f = map_file_or(path, "Failed to mmap " + path);
     constexpr size_t kRec = 24;
     if (f.size() % kRec != 0)  // gof.rs:103-110
         throw Error("Corrupted GOF (" + path + "): length " + std::to_string(f.size()) + " not multiple of 24");
@@ -84,17 +76,7 @@ GofMap load_gof(const std::string &gff) {
 // by the reference (no Rust toolchain here), so the caller falls back to the .gof route when an
 // image does not parse.  Validations and messages follow tree_index.rs:54-79.
 std::vector<std::vector<RootInterval>> load_region_index(const std::string &rit_path, const std::string &rix_path) {
-    MappedFile rit, rix;
-    try {
-        rit = MappedFile(rit_path);
-    } catch (const Error &) {
-        throw Error("open " + rit_path);
-    }
-    try {
-        rix = MappedFile(rix_path);
-    } catch (const Error &) {
-        throw Error("open " + rix_path);
-    }
+    const MappedFile rit = map_file_or(rit_path, "open " + rit_path), rix = map_file_or(rix_path, "open " + rix_path);
     // serde_json: Vec<u64> -- '[' ws (digits (ws ',' ws digits)*)? ws ']'
     std::vector<uint64_t> offsets;
     {
@@ -181,18 +163,32 @@ std::vector<std::vector<RootInterval>> load_region_index(const std::string &rit_
     return trees;
 }
 
+// What an image is valid for: the .gof records (FNV-1a over every field) and the GFF's size and modification time.  A
+// same-length edit of the GFF, a re-index by the reference's own `gffx index` (it rewrites .gof) or a copied file all
+// change it; the reader then parses the GFF, as the reference does on every run (depth.rs:131-152, coverage.rs:296-337).
+uint64_t line_table_key(const std::string &gff_path, const GofMap &gof) {
+    uint64_t h = 1469598103934665603ull;
+    auto mix = [&](uint64_t v) {
+        for (int b = 0; b < 8; ++b) {
+            h ^= (v >> (8 * b)) & 255u;
+            h *= 1099511628211ull;
+        }
+    };
+    for (const auto &g : gof.entries) {
+        mix(static_cast<uint64_t>(g.feature_id) | (static_cast<uint64_t>(g.seqid_num) << 32));
+        mix(g.start_offset);
+        mix(g.end_offset);
+    }
+    struct stat st;
+    if (::stat(gff_path.c_str(), &st) == 0) {
+        mix(static_cast<uint64_t>(st.st_size));
+        mix(static_cast<uint64_t>(st.st_mtim.tv_sec));
+        mix(static_cast<uint64_t>(st.st_mtim.tv_nsec));
+    }
+    return h;
+}
+
 }  // namespace index_loader
-
-TreeIndexData::TreeIndexData(TreeIndexData &&o) noexcept
-    : seqid_to_num(std::move(o.seqid_to_num)), num_to_seqid(std::move(o.num_to_seqid)),
-      chr_offsets(std::move(o.chr_offsets)), start(std::move(o.start)), end(std::move(o.end)),
-      root_fid(std::move(o.root_fid)), device_index(o.device_index) {
-    o.device_index = nullptr;
-}
-
-TreeIndexData::~TreeIndexData() {
-    if (device_index) gffx_hip_index_destroy(device_index);
-}
 
 namespace {
 
@@ -343,9 +339,8 @@ TreeIndexData TreeIndexData::load_tree_index(const std::string &gff) {
 void TreeIndexData::ensure_device(int device) {
     if (device_index) return;
     const uint32_t n_chr = static_cast<uint32_t>(chr_offsets.size() - 1);
-    const int rc = gffx_hip_index_create(n_chr, chr_offsets.data(), start.data(), end.data(), root_fid.data(),
-                                         device, &device_index);
-    if (rc != GFFX_OK) throw Error(std::string("gffx_hip_index_create: ") + gffx_hip_last_error());
+    if (gffx_hip_index_create(n_chr, chr_offsets.data(), start.data(), end.data(), root_fid.data(), device, OutPtr(device_index)) != GFFX_OK)
+        hip_fail("gffx_hip_index_create");
 }
 
 }  // namespace gffx

@@ -7,7 +7,7 @@
 // every line of the file and writes the result as a flat little-endian image `<gff>.lall`; a run maps it, finds the lines of a
 // hit block by binary search on the line starts and copies {start, end, seqid} to the device -- no text is touched before the
 // kept lines are written.  -T becomes a compare of type numbers.
-//   header   "GFFXLALL", u32 version, u32 0, u64 gff bytes, u64 content key (block_table.cpp::line_table_key),
+//   header   "GFFXLALL", u32 version, u32 0, u64 gff bytes, u64 content key (index_loader::line_table_key),
 //            u64 lines, u32 seqid names, u32 type names, u64 name bytes
 //   arrays   ls[u64]  line start | len[u32]  bytes to the next line start (the '\n' included when there is one) |
 //            start[u32], end[u32]  raw columns 4 / 5 | seq[u32]  number of the line's column-1 string | type[u32]  number of its
@@ -18,16 +18,13 @@
 // A stale or damaged image (sizes, key, offsets not ascending, numbers out of range) is not used: the run parses the text.
 #include <algorithm>
 #include <cstring>
-#include <thread>
 #include <unordered_map>
 
 #include <sys/mman.h>
 
 #include "gffx.hpp"
 
-namespace gffx {
-namespace commands {
-namespace intersect {
+namespace gffx::commands::intersect {
 
 namespace {
 constexpr char kMagic[8] = {'G', 'F', 'F', 'X', 'L', 'A', 'L', 'L'};
@@ -62,7 +59,7 @@ AllLines build_all_lines(std::string_view gff, size_t threads) {
         cut[t] = (p == 0) ? 0 : (nl == std::string_view::npos ? gff.size() : nl + 1);
     }
     std::vector<Part> parts(T);
-    auto work = [&](size_t t) {
+    parallel_for(T, T, [&](size_t t) {
         Part &P = parts[t];
         // (std::string keys: the local tables are tiny -- tens of seqids and types)
         std::unordered_map<std::string, uint32_t> seq_map, type_map;
@@ -123,13 +120,7 @@ AllLines build_all_lines(std::string_view gff, size_t threads) {
             }
             pos = nl;
         }
-    };
-    {
-        std::vector<std::thread> pool;
-        for (size_t t = 1; t < T; ++t) pool.emplace_back(work, t);
-        work(0);
-        for (auto &th : pool) th.join();
-    }
+    });
     AllLines A;
     std::unordered_map<std::string, uint32_t> seq_all, type_all;
     size_t n = 0;
@@ -263,6 +254,4 @@ bool AllLinesView::block_lines(uint64_t s, uint64_t e, uint64_t &lo, uint64_t &h
     return true;
 }
 
-}  // namespace intersect
-}  // namespace commands
-}  // namespace gffx
+}  // namespace gffx::commands::intersect

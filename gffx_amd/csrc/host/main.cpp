@@ -266,7 +266,7 @@ int run_index_cli(int argc, char **argv) {
         // defines (the eight side-cars above) stands.
         try {
             const auto t = commands::depth::build_block_table(gof, text.view(), std::min(hw ? hw : 1u, 12u));
-            commands::depth::write_block_table(append_suffix(input, ".lsoa"), t, text.size(), commands::depth::line_table_key(input, gof));
+            commands::depth::write_block_table(append_suffix(input, ".lsoa"), t, text.size(), index_loader::line_table_key(input, gof));
             if (verbose) std::printf("Line table image: %zu lines in %zu blocks.\n", t.line_start.size(), t.block_line_off.size() - 1);
         } catch (const Error &e) {
             std::fprintf(stderr, "[WARN] line table image %s not written: %s\n", append_suffix(input, ".lsoa").c_str(), e.what());
@@ -275,7 +275,7 @@ int run_index_cli(int argc, char **argv) {
         // ... and the all-line table `<gff>.lall` of intersect's per-line mode (line_index.cpp)
         try {
             const auto all = commands::intersect::build_all_lines(text.view(), std::min(hw ? hw : 1u, 12u));
-            commands::intersect::write_all_lines(append_suffix(input, ".lall"), all, text.size(), commands::depth::line_table_key(input, gof));
+            commands::intersect::write_all_lines(append_suffix(input, ".lall"), all, text.size(), index_loader::line_table_key(input, gof));
             if (verbose) std::printf("All-line table: %zu lines, %zu seqid names, %zu types.\n", all.ls.size(), all.seq_names.size(), all.type_names.size());
         } catch (const Error &e) {
             std::fprintf(stderr, "[WARN] all-line table %s not written: %s\n", append_suffix(input, ".lall").c_str(), e.what());

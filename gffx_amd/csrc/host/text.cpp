@@ -11,6 +11,14 @@
 
 namespace gffx {
 
+MappedFile map_file_or(const std::string &path, const std::string &error) {
+    try {
+        return MappedFile(path);
+    } catch (const Error &) {
+        throw Error(error);
+    }
+}
+
 MappedFile::MappedFile(const std::string &path) {
     int fd = ::open(path.c_str(), O_RDONLY);
     if (fd < 0) throw Error("Failed to open file: \"" + path + "\": " + std::strerror(errno));

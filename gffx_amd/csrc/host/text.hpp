@@ -34,6 +34,7 @@ class MappedFile {
     size_t n_ = 0;
     bool mapped_ = false;
 };
+MappedFile map_file_or(const std::string &path, const std::string &error);  // the file mapped, or Error(error)
 
 bool utf8_valid(std::string_view s);                 // std::str::from_utf8(..).is_ok()
 size_t unicode_ws_len(const char *p, size_t n);      // bytes of a White_Space char at p, else 0

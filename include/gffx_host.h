@@ -24,7 +24,7 @@ int gffx_host_load_tree_index(const char *gff, uint32_t *n_chr, uint32_t **chr_o
 int gffx_host_parse_bed_file(const char *gff, const char *bed, uint32_t **regions, uint64_t *n_regions,
                              char *err, size_t errlen);
 /* the same rows through the chunked parser of the streaming CLI (chunks of chunk_bytes cut at line starts, four pieces per
- * thread on persistent workers, recycled row buffers): host/intersect.cpp::stream_unique_roots' producer, without a device */
+ * thread on persistent workers, recycled row buffers): host/join_a_stream.cpp::stream_unique_roots' producer, without a device */
 int gffx_host_parse_bed_file_chunked(const char *gff, const char *bed, uint32_t threads, uint64_t chunk_bytes, uint32_t **regions,
                                      uint64_t *n_regions, char *err, size_t errlen);
 /* The host half of `gffx intersect --gpus n_dev` without a device (stream_unique_roots' parser pool + per-chunk bucket scatter):

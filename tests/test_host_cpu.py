@@ -513,6 +513,43 @@ def test_streaming_parser_chunks_pool_and_recycled_buffers(host, tmp_path, monke
     assert b"12x" in e.value
 
 
+def test_an_error_on_a_parser_worker_thread_is_the_first_bad_row_not_the_end_of_the_process(host, tmp_path, monkeypatch):
+    """A parse error thrown on a worker thread of either fan-out (parallel_for under gffx_host_parse_bed_file, the persistent
+    pool under gffx_host_parse_bed_file_chunked) comes back as an error return that names the FIRST bad row in file order,
+    whichever piece fails first in time; the process lives on and parses the mended file."""
+    monkeypatch.setenv("GFFX_TREE_INDEX", "gof")
+    gff, roots = _make_gff(tmp_path, 6)
+    assert _build(host, gff)[0] == 0
+    rows = synth.synth_bed(120_000, seed=9, chroms=synth.SMALL2, width=(1, 50000), edge_frac=0.05, roots=roots)
+    good = ["%s\t%d\t%d" % (("chr1", "chr2")[c], s, e) for c, s, e in rows.tolist()]
+    bad = list(good)
+    # (with 4, 5 or 32 pieces these rows lie in different pieces: several workers throw, the pieces before the first parse clean)
+    for k, name in ((0.45, "firstbad"), (0.65, "secondbad"), (0.85, "thirdbad"), (0.99, "fourthbad")):
+        bad[int(k * len(bad))] = "chr1\t%s\t5" % name
+    bed = str(tmp_path / "bad.bed")
+    open(bed, "w").write("\n".join(bad) + "\n")
+    assert os.path.getsize(bed) > (1 << 20)
+    host.gffx_host_parse_bed_file_chunked.restype = C.c_int
+    host.gffx_host_parse_bed_file_chunked.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint64, C.POINTER(u32p), u64p, C.c_char_p, C.c_size_t]
+    pr, nr = u32p(), C.c_uint64()
+
+    def refused(rc, e):
+        return rc == -1 and b"firstbad" in e.value and not any(x in e.value for x in (b"secondbad", b"thirdbad", b"fourthbad"))
+
+    e = _err()
+    assert refused(host.gffx_host_parse_bed_file(gff.encode(), bed.encode(), C.byref(pr), C.byref(nr), e, len(e)), e), e.value
+    for threads in (1, 8):
+        for chunk in (1 << 30, 1 << 19):  # the whole file as one chunk of 4 x threads pieces; several chunks
+            e = _err()
+            assert refused(host.gffx_host_parse_bed_file_chunked(gff.encode(), bed.encode(), threads, chunk, C.byref(pr), C.byref(nr), e, len(e)),
+                           e), (threads, chunk, e.value)
+    open(bed, "w").write("\n".join(good) + "\n")
+    e = _err()
+    assert host.gffx_host_parse_bed_file(gff.encode(), bed.encode(), C.byref(pr), C.byref(nr), e, len(e)) == 0, e.value
+    assert nr.value == len(good)
+    host.gffx_host_free(pr)
+
+
 def test_multi_device_scatter_of_bed_chunks_equals_the_shard_plan(host, tmp_path, monkeypatch):
     """The host half of `gffx intersect --gpus N` without a device (gffx_host_shard_bed_file = the parser pool + scatter_chunk_by_bucket,
     the code stream_unique_roots runs per chunk): one chunk -> device d receives exactly regions[shard_rows(regions, N, d)]

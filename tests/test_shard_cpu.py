@@ -119,7 +119,7 @@ def test_two_rank_gloo_allgather_matches_single_process():
 
 
 def test_cpp_plan_of_the_cli_equals_the_python_plan():
-    """`gffx intersect --gpus N` shards every BED chunk with the C++ port of plan_shards (host/intersect.cpp)."""
+    """`gffx intersect --gpus N` shards every BED chunk with the C++ port of plan_shards (host/shard.cpp)."""
     import ctypes as C
     import os
 
