@@ -512,13 +512,22 @@ def bgzf_inflate(data: bytes, device: int = 0) -> bytes:
 
 
 def bgzf_members(data: bytes) -> List[int]:
-    """Offsets of the BGZF members of `data` (plus len(data)), by hopping their BSIZE fields (BC subfield first)."""
+    """Offsets of the BGZF members of `data` (plus len(data)), by hopping their BSIZE fields (the BC subfield, wherever it
+    stands among the extra subfields)."""
     off, at = [], 0
     while at < len(data):
         off.append(at)
         if len(data) - at < 18:
             raise ValueError("truncated BGZF member at offset %d" % at)
-        at += int.from_bytes(data[at + 16:at + 18], "little") + 1
+        sub, end, bsize = at + 12, at + 12 + int.from_bytes(data[at + 10:at + 12], "little"), None
+        while sub + 4 <= min(end, len(data)):
+            slen = int.from_bytes(data[sub + 2:sub + 4], "little")
+            if data[sub:sub + 2] == b"BC" and slen == 2:
+                bsize = int.from_bytes(data[sub + 4:sub + 6], "little")
+            sub += 4 + slen
+        if bsize is None:
+            raise ValueError("no BC subfield in the BGZF member at offset %d" % at)
+        at += bsize + 1
     off.append(len(data))
     return off
 

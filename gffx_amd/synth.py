@@ -408,3 +408,32 @@ def bam_rows_definition(recs: Sequence[tuple], ref_seq: Sequence[int]) -> np.nda
             continue
         rows.append((ref_seq[tid], min(pos, 0xFFFFFFFF), min(end, 0xFFFFFFFF)))
     return np.array(rows, dtype=np.uint32).reshape(-1, 3)
+
+
+def bam_sized_record(size: int, tid: int, pos: int, name: bytes, seed: int = 0) -> tuple:
+    """A record of exactly `size` bytes, the block_size field included: a long read whose bulk is one Z tag of random bases."""
+    cigar = [(0, 5000), (2, 7), (0, 300)]
+    fixed = len(bam_record(tid, pos, 0, cigar, name, 0, b"XXZ\x00"))
+    assert size >= fixed
+    bases = np.frombuffer(b"ACGT", np.uint8)[np.random.default_rng(seed).integers(0, 4, size - fixed)].tobytes()
+    rec = bam_record(tid, pos, 0, cigar, name, 0, b"XXZ" + bases + b"\x00")
+    assert len(rec) == size
+    return (rec, tid, pos, 0, cigar)
+
+
+LONG_READ_GROUPS = ((BGZF_BLOCK, 1), (BGZF_BLOCK + 1, 2), (2 * BGZF_BLOCK, 3), (300_000, 2), (1_000_000, 1), (BGZF_BLOCK, 3),
+                    (1_000_000, 2), (BGZF_BLOCK + 1, 1), (300_000, 3))
+
+
+def bam_long_read_records(n: int, seed: int, refs: Sequence[Tuple[str, int]], groups=LONG_READ_GROUPS) -> List[tuple]:
+    """A long-read file's records: the n + 2 ordinary records of bam_test_records(big=False) and, spread evenly between them,
+    groups of back-to-back records of exactly the given sizes (size in bytes with the block_size field, records in the group):
+    one block, one block + 1, two blocks, 0.3 MB and 1 MB."""
+    base = bam_test_records(n, seed, refs, big=False)
+    out, step = [], len(base) // (len(groups) + 1)
+    for g, (size, count) in enumerate(groups):
+        out += base[g * step:(g + 1) * step]
+        _, tid, pos, _, _ = out[-1]
+        tid, pos = max(tid, 0), max(pos, 0)
+        out += [bam_sized_record(size, tid, pos + k, b"long%d.%d" % (g, k), seed * 1000 + g * 10 + k) for k in range(count)]
+    return out + base[len(groups) * step:]

@@ -1,6 +1,7 @@
 """BAM sources on the GPU: k_bgzf_inflate == zlib, the rows of k_bam_rows == the Python restatement of depth.rs:335-364, and
 `gffx depth|coverage -s x.bam` == the oracle's answer for a BED of the same rows (the reference joins both sources the same
-way: depth.rs:462-498 against :335-372, coverage.rs:245-262 against :157-190)."""
+way: depth.rs:462-498 against :335-372, coverage.rs:245-262 against :157-190).  Every file here is written through zlib;
+tests/test_deflate_streams_gpu.py adds streams of another encoder, tests/test_bam_shapes_gpu.py files of many members and long reads."""
 import os
 import subprocess
 import zlib

@@ -1,7 +1,8 @@
 """The BGZF / DEFLATE / BAM-record decoder shared by the host and k_bgzf_inflate / k_bam_rows (device/bgzf_core.hpp), built
 for the host under AddressSanitizer + UndefinedBehaviorSanitizer (tools/bgzf_check.cpp): equal to zlib on every level and
 strategy, corrupt members rejected with a status and no sanitizer report, record framing and bam_endpos equal to a Python
-restatement on both block layouts.  No GPU."""
+restatement on both block layouts.  No GPU.  tests/test_deflate_streams_cpu.py adds the streams zlib's encoder does not write
+(15-bit codes, libdeflate-style block headers) and the framing of long-read files."""
 import os
 import struct
 import subprocess
