@@ -93,6 +93,16 @@ SIGNATURES = {
     "gffx_hip_lines_copy_dirs": (C.c_int, [vp, u64p, u32p, u32p]),
     "gffx_hip_lines_copy_degenerate": (C.c_int, [vp, u64p, u64p, u32p]),
     "gffx_hip_segments_covered": (C.c_int, [C.c_int, C.c_uint64, u32p, u32p, u32p, u32p, C.c_uint64, C.c_uint32, u32p]),
+    "gffx_hip_union_create": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(vp)]),
+    "gffx_hip_union_add_host": (C.c_int, [vp, u32p, C.c_uint64]),
+    "gffx_hip_union_add_store": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64]),
+    "gffx_hip_union_add_spans": (C.c_int, [vp, u64p, u32p, u32p]),
+    "gffx_hip_union_finish": (C.c_int, [vp]),
+    "gffx_hip_union_n_spans": (C.c_uint64, [vp]),
+    "gffx_hip_union_copy_spans": (C.c_int, [vp, u64p, u32p, u32p, u64p]),
+    "gffx_hip_union_segments_covered": (C.c_int, [vp, C.c_uint64, u32p, u32p, u32p, u32p]),
+    "gffx_hip_union_stats": (C.c_int, [vp, C.POINTER(C.c_double), u64p, u64p]),
+    "gffx_hip_union_destroy": (None, [vp]),
     "gffx_hip_depth_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, u64p, u32p, u32p, u32p, C.c_uint32, u32p,
                                         C.POINTER(vp)]),
     "gffx_hip_depth_destroy": (None, [vp]),

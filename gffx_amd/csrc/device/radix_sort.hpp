@@ -142,7 +142,8 @@ __global__ __launch_bounds__(kHistThreads) void k_radix_hist(const uint32_t *rec
 
 // exclusive scan of each pass's 256 bins (block p = pass p); same_byte[p] = 1 when one bin holds all n records
 // block n_passes (launched only with a top digit): lut[] = exclusive scan of the per-seqid digit counts, ok = they fit 256
-__global__ __launch_bounds__(256) void k_radix_scan(uint32_t *hist, unsigned long long n, uint32_t *same_byte, SortNote note, SortTop top, uint32_t n_passes,
+// (static: the one kernel here that is no template, and two translation units include this header)
+static __global__ __launch_bounds__(256) void k_radix_scan(uint32_t *hist, unsigned long long n, uint32_t *same_byte, SortNote note, SortTop top, uint32_t n_passes,
                                                     uint32_t limit0) {
     __shared__ uint32_t s_w[4];
     if (blockIdx.x == n_passes) {  // thread c = value c of word 0

@@ -5,10 +5,19 @@
 //   write_breadth_results       coverage.rs:452-485   "id\tchr\tstart\tend\tbreadth\tfraction"
 // The per-root merged coverage is only needed for segments that stick out of their root's interval; for a segment
 // inside it, any region that overlaps the segment hits the root, so the union of ALL regions of the seqid gives the
-// same covered bases -- that part runs on the device for every segment at once (gffx_hip_segments_covered).  The
-// rare other segments are evaluated here against the root's own list, exactly as the reference does.
+// same covered bases.  ONE pass over the rows serves both: they go to the devices in batches (round robin with --gpus N,
+// one host thread per device, each batch uploaded once into a region store), Join A sets the root bitmap from the resident
+// rows and gffx_hip_union_add_store folds the same rows into the device's union.  The bitmaps are OR-ed on the host, the
+// other devices' spans (they are small) are folded into device 0's union, and the segments are evaluated once there.
+// The rare segments that stick out need the root's OWN merged list.  Which roots can have such a segment is a property of
+// the GFF alone (a line of the block outside the root's one interval), so a second, small index of just those roots rides
+// along: Join A with root_fids + offsets over the same resident batches pairs rows with them, the host gathers the paired
+// rows per root and merges them -- exactly the reference's list (coverage.rs:258-268, :401), with work proportional to the
+// pairs instead of rows x such blocks.
 #include <algorithm>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 
 #include "gffx.hpp"
 
@@ -47,6 +56,16 @@ uint64_t covered(const std::vector<Span> &cov, uint32_t a, uint32_t b) {  // cov
     return t;
 }
 
+size_t batch_rows_from_env() {  // GFFX_COVERAGE_BATCH_ROWS (gffx.hpp)
+    const char *e = std::getenv("GFFX_COVERAGE_BATCH_ROWS");
+    if (e && *e) {
+        char *end = nullptr;
+        const unsigned long long v = std::strtoull(e, &end, 10);
+        if (end && !*end && v > 0) return static_cast<size_t>(std::min<unsigned long long>(v, 1ull << 28));
+    }
+    return 4u << 20;
+}
+
 }  // namespace
 
 void run(const CoverageArgs &args) {
@@ -58,28 +77,20 @@ void run(const CoverageArgs &args) {
     TreeIndexData index_data = TreeIndexData::load_tree_index(args.input);  // :511
     const depth::SourceKind kind = depth::source_kind(args.source);  // coverage.rs:520-541
     const bool bam = kind == depth::SourceKind::Bam;
-    // the kept rows as flat (seqid number, start, end) words, from the source to the device (there is always a first piece)
-    std::vector<std::vector<uint32_t>> part =
-        depth::read_source_rows(kind, args.source, index_data.seqid_to_num, capped_threads(args.threads), args.device, verbose, warm);
-    std::vector<uint32_t> flat = std::move(part[0]);
-    size_t words = flat.size();
-    for (size_t p = 1; p < part.size(); ++p) words += part[p].size();
-    flat.reserve(words);
-    for (size_t p = 1; p < part.size(); ++p) flat.insert(flat.end(), part[p].begin(), part[p].end());
-    part.clear();
-    const size_t n_regions = flat.size() / 3;
+    const size_t threads = capped_threads(args.threads);
+    // the kept rows as flat (seqid number, start, end) words, one vector per parsed piece (file order); part_row[p] = rows before piece p
+    const std::vector<std::vector<uint32_t>> part =
+        depth::read_source_rows(kind, args.source, index_data.seqid_to_num, threads, args.device, verbose, warm);
+    std::vector<size_t> part_row(part.size() + 1, 0);
+    for (size_t p = 0; p < part.size(); ++p) part_row[p + 1] = part_row[p] + part[p].size() / 3;
+    const size_t n_regions = part_row.back();
     if (verbose) std::fprintf(stderr, "[INFO] %zu %s rows kept\n", n_regions, bam ? "BAM" : "BED");
     timer.lap(bam ? "Loading index + reading BAM" : "Loading index + parsing BED");
 
     std::string out = "id\tchr\tstart\tend\tbreadth\tfraction\n";  // :463
     size_t written = 0;
     if (n_regions) {
-        // which roots are hit (by_root's key set, coverage.rs:258-268): Join A's unique-root output
-        warm.wait();
-        const std::vector<uint32_t> hit_roots =
-            intersect::query_unique_roots(index_data, flat.data(), n_regions, intersect::OverlapMode::Overlap, false, verbose, args.device);
-        timer.lap("Join A on the device (root bitmap)");
-        const depth::BlockTable t = depth::load_or_build_block_table(args.input, gof, gff.view(), capped_threads(args.threads), verbose);
+        const depth::BlockTable t = depth::load_or_build_block_table(args.input, gof, gff.view(), threads, verbose);
         timer.lap("Line table (image or parse)");
         // the tree intervals of every root_fid (several when root lines share an ID)
         const uint32_t n_seq = static_cast<uint32_t>(index_data.chr_offsets.size() - 1);
@@ -87,6 +98,200 @@ void run(const CoverageArgs &args) {
         for (uint32_t c = 0; c < n_seq; ++c)
             for (uint32_t i = index_data.chr_offsets[c]; i < index_data.chr_offsets[c + 1]; ++i)
                 ivs[index_data.root_fid[i]].emplace_back(c, index_data.start[i], index_data.end[i]);
+        std::vector<uint32_t> block_fid(t.block_line_off.size() - 1, 0xFFFFFFFFu);
+        for (uint32_t f = 0; f < t.block_of_fid.size(); ++f)
+            if (t.block_of_fid[f] != 0xFFFFFFFFu) block_fid[t.block_of_fid[f]] = f;
+        // Roots that CAN have a segment outside their interval: every block but those whose root has one interval that holds
+        // all lines of the block (a superset of the blocks the exact test below finds: a segment is a union of lines).
+        std::vector<uint8_t> side_fid(t.block_of_fid.size(), 0);
+        for (uint32_t b = 0; b + 1 < t.block_line_off.size(); ++b) {
+            if (block_fid[b] == 0xFFFFFFFFu) continue;
+            const auto it = ivs.find(block_fid[b]);
+            if (it == ivs.end()) continue;  // (no interval: never hit)
+            bool all_inside = it->second.size() == 1;
+            if (all_inside) {
+                const uint32_t rs = std::get<1>(it->second[0]), re = std::get<2>(it->second[0]);
+                for (uint64_t l = t.block_line_off[b]; l < t.block_line_off[b + 1] && all_inside; ++l)
+                    all_inside = t.line_start[l] >= rs && t.line_end[l] <= re;
+            }
+            if (!all_inside) side_fid[block_fid[b]] = 1;
+        }
+        std::vector<uint32_t> side_off(n_seq + 1, 0), side_start, side_end, side_root;
+        for (uint32_t c = 0; c < n_seq; ++c) {
+            for (uint32_t i = index_data.chr_offsets[c]; i < index_data.chr_offsets[c + 1]; ++i) {
+                const uint32_t f = index_data.root_fid[i];
+                if (f < side_fid.size() && side_fid[f]) {
+                    side_start.push_back(index_data.start[i]);
+                    side_end.push_back(index_data.end[i]);
+                    side_root.push_back(f);
+                }
+            }
+            side_off[c + 1] = static_cast<uint32_t>(side_start.size());
+        }
+        const bool have_side = !side_start.empty();
+
+        // --gpus N: the rows go to the devices in batches, round robin (the root bitmap is an OR and the union does not depend
+        // on how the rows are grouped, so any partition gives the same rows out); one host thread drives each device
+        warm.wait();
+        DeviceSet devs = DeviceSet::resolve(args.device, args.gpus);
+        const size_t D = devs.size();
+        index_data.ensure_device(devs[0]);
+        gffx_hip_index *ix0 = index_data.device_index.get();
+        const uint64_t n_words = (gffx_hip_index_n_roots(ix0) + 63) / 64 + 1;
+        using RootRows = std::unordered_map<uint32_t, std::vector<Span>>;  // root_fid -> the rows that hit it
+        struct PerDevice {
+            RegionsHandle store;  // two pinned staging buffers + a ring of two batch slots in HBM
+            BatchHandle b[2], c[2];  // Join A on the index (root bitmap) / on the index of the roots above (pairs)
+            IndexHandle side;
+            UnionHandle u;
+            std::vector<uint64_t> words;
+            RootRows root_rows;
+            std::vector<uint64_t> u_off;
+            std::vector<uint32_t> us, ue;
+            uint64_t rows = 0, spans = 0, side_pairs = 0;
+            double union_ms = 0;
+        };
+        std::vector<PerDevice> pd(D);
+        const size_t kBatch = batch_rows_from_env();
+        const size_t cap = std::min(n_regions, kBatch);
+        parallel_for(D, D, [&](size_t d) {
+            PerDevice &P = pd[d];
+            gffx_hip_index *ix = devs.index_on(d, ix0);
+            if (have_side &&
+                gffx_hip_index_create(n_seq, side_off.data(), side_start.data(), side_end.data(), side_root.data(), devs[d], OutPtr(P.side)) != GFFX_OK)
+                hip_fail("gffx_hip_index_create");
+            if (gffx_hip_union_create(devs[d], n_seq, OutPtr(P.u)) != GFFX_OK) hip_fail("gffx_hip_union_create");
+            if (gffx_hip_regions_create(devs[d], 0, cap, 0, OutPtr(P.store)) != GFFX_OK) hip_fail("gffx_hip_regions_create");
+            for (int k = 0; k < 2; ++k) {
+                if (gffx_hip_batch_create(ix, cap, OutPtr(P.b[k])) != GFFX_OK) hip_fail("gffx_hip_batch_create");
+                if (have_side && gffx_hip_batch_create(P.side.get(), cap, OutPtr(P.c[k])) != GFFX_OK) hip_fail("gffx_hip_batch_create");
+            }
+            P.words.assign(n_words, 0);
+            bool used[2] = {false, false};
+            size_t rows_in[2] = {0, 0};
+            std::vector<uint32_t> counts, fids;
+            std::vector<uint64_t> offsets;
+            // Batch i goes through staging buffer / batches i & 1 (depth.cpp).  finish(k): the passes over slot k are through; the
+            // rows paired with a root of the side index are gathered from staging buffer k, which still holds the batch.
+            auto finish = [&](int k) {
+                if (gffx_hip_batch_wait(P.b[k].get()) != GFFX_OK) hip_fail("query_features");
+                if (!have_side) return;
+                if (gffx_hip_batch_wait(P.c[k].get()) != GFFX_OK) hip_fail("query_features");
+                const uint64_t total = gffx_hip_batch_total_hits(P.c[k].get());
+                if (!total) return;
+                const size_t n = rows_in[k];
+                counts.resize(n), offsets.resize(n + 1), fids.resize(total);
+                if (gffx_hip_batch_copy_counts(P.c[k].get(), counts.data()) != GFFX_OK) hip_fail("copy_counts");
+                if (gffx_hip_batch_copy_offsets(P.c[k].get(), offsets.data()) != GFFX_OK) hip_fail("copy_offsets");
+                if (gffx_hip_batch_copy_fids(P.c[k].get(), fids.data()) != GFFX_OK) hip_fail("copy_fids");
+                const uint32_t *stage = gffx_hip_regions_staging(P.store.get(), k);
+                for (size_t j = 0; j < n; ++j) {
+                    if (!counts[j]) continue;
+                    uint32_t *f = fids.data() + offsets[j], *fe = f + counts[j];
+                    std::sort(f, fe);  // a region once per root (coverage.rs:263-266), also when root lines share an ID
+                    fe = std::unique(f, fe);
+                    for (; f < fe; ++f) P.root_rows[*f].emplace_back(stage[3 * j + 1], stage[3 * j + 2]);
+                }
+                P.side_pairs += total;
+            };
+            const size_t fill_threads = std::max<size_t>(1, std::min<size_t>(threads / D, 8));
+            size_t i = 0;
+            for (size_t a = d * kBatch; a < n_regions; a += D * kBatch, ++i) {
+                const int k = static_cast<int>(i & 1);
+                const size_t n = std::min(kBatch, n_regions - a);
+                if (gffx_hip_regions_wait_staging(P.store.get(), k) != GFFX_OK) hip_fail("wait_staging");
+                uint32_t *stage = gffx_hip_regions_staging(P.store.get(), k);
+                // rows [a, a + n) of the file: the tails / heads of the pieces they lie in, copied by a few threads
+                struct Move {
+                    const uint32_t *src;
+                    size_t at, rows;
+                };
+                std::vector<Move> moves;
+                size_t p = static_cast<size_t>(std::upper_bound(part_row.begin(), part_row.end(), a) - part_row.begin()) - 1;
+                for (size_t done = 0; done < n; ++p) {
+                    const size_t from = a + done - part_row[p], take = std::min(n - done, part_row[p + 1] - (a + done));
+                    for (size_t x = 0; x < take; x += 1u << 18)
+                        moves.push_back({part[p].data() + 3 * (from + x), done + x, std::min<size_t>(take - x, 1u << 18)});
+                    done += take;
+                }
+                parallel_for(moves.size(), fill_threads,
+                             [&](size_t m) { std::memcpy(stage + 3 * moves[m].at, moves[m].src, moves[m].rows * 12); });
+                if (gffx_hip_regions_append(P.store.get(), k, n) != GFFX_OK) hip_fail("regions_append");  // the batch's ONE upload
+                if (gffx_hip_batch_set_regions_store(P.b[k].get(), P.store.get(), k, 0, n) != GFFX_OK) hip_fail("set_regions_store");
+                const uint32_t flags = static_cast<uint32_t>(GFFX_OUT_ROOT_BITMAP) | static_cast<uint32_t>(GFFX_OUT_NO_COUNTS) |
+                                       (used[k] ? static_cast<uint32_t>(GFFX_OUT_BITMAP_KEEP) : 0u);  // (the bitmap accumulates across batches)
+                if (gffx_hip_batch_run(P.b[k].get(), GFFX_MODE_OVERLAP, 0, flags, GFFX_STRATEGY_AUTO) != GFFX_OK) hip_fail("gffx_hip_batch_run");
+                if (have_side) {
+                    if (gffx_hip_batch_set_regions_store(P.c[k].get(), P.store.get(), k, 0, n) != GFFX_OK) hip_fail("set_regions_store");
+                    if (gffx_hip_batch_run(P.c[k].get(), GFFX_MODE_OVERLAP, 0, GFFX_OUT_FIDS | GFFX_OUT_OFFSETS, GFFX_STRATEGY_AUTO) != GFFX_OK)
+                        hip_fail("gffx_hip_batch_run");
+                }
+                used[k] = true;
+                rows_in[k] = n;
+                // the same resident rows into the union (on the union's own stream, beside Join A; returns when they are read)
+                if (gffx_hip_union_add_store(P.u.get(), P.store.get(), k, 0, n) != GFFX_OK) hip_fail("gffx_hip_union_add_store");
+                if (i > 0) finish(1 - k);
+                P.rows += n;
+            }
+            if (i > 0) finish(static_cast<int>((i - 1) & 1));
+            std::vector<uint64_t> tmp(n_words, 0);
+            for (int k = 0; k < 2; ++k) {
+                if (!used[k]) continue;
+                if (gffx_hip_batch_copy_root_bitmap(P.b[k].get(), tmp.data(), tmp.size()) != GFFX_OK) hip_fail("copy_root_bitmap");
+                for (size_t w = 0; w < n_words; ++w) P.words[w] |= tmp[w];
+            }
+            P.spans = gffx_hip_union_n_spans(P.u.get());
+            if (d > 0) {  // the spans travel to device 0's union
+                if (gffx_hip_union_finish(P.u.get()) != GFFX_OK) hip_fail("gffx_hip_union_finish");
+                P.u_off.assign(n_seq + 1, 0);
+                P.us.assign(std::max<uint64_t>(P.spans, 1), 0);
+                P.ue.assign(std::max<uint64_t>(P.spans, 1), 0);
+                if (gffx_hip_union_copy_spans(P.u.get(), P.u_off.data(), P.us.data(), P.ue.data(), nullptr) != GFFX_OK) hip_fail("gffx_hip_union_copy_spans");
+            }
+            if (gffx_hip_union_stats(P.u.get(), &P.union_ms, nullptr, nullptr) != GFFX_OK) hip_fail("gffx_hip_union_stats");
+        });
+        // merge over the devices: OR of the bitmaps, the spans into device 0's union
+        std::vector<uint64_t> words(n_words, 0);
+        for (const PerDevice &P : pd)
+            for (size_t w = 0; w < n_words; ++w) words[w] |= P.words[w];
+        std::vector<uint32_t> hit_roots;  // by_root's key set (coverage.rs:258-268), ascending and unique
+        {
+            const uint64_t n_roots = gffx_hip_index_n_roots(ix0);
+            const uint32_t *sorted_fids = gffx_hip_index_sorted_fids(ix0);
+            for (uint64_t i = 0; i < n_roots; ++i)
+                if (words[i >> 6] >> (i & 63) & 1) hit_roots.push_back(sorted_fids[i]);
+            std::sort(hit_roots.begin(), hit_roots.end());
+            hit_roots.erase(std::unique(hit_roots.begin(), hit_roots.end()), hit_roots.end());
+        }
+        gffx_hip_union *U = pd[0].u.get();
+        for (size_t d = 1; d < D; ++d)
+            if (gffx_hip_union_add_spans(U, pd[d].u_off.data(), pd[d].us.data(), pd[d].ue.data()) != GFFX_OK) hip_fail("gffx_hip_union_add_spans");
+        if (gffx_hip_union_finish(U) != GFFX_OK) hip_fail("gffx_hip_union_finish");
+        const uint64_t union_spans = gffx_hip_union_n_spans(U);
+        double union_ms = 0;
+        uint64_t side_pairs = 0;
+        std::vector<uint64_t> counts(2 * D, 0);
+        std::string per_device = "[";
+        for (size_t d = 0; d < D; ++d) {
+            counts[2 * d] = pd[d].rows, counts[2 * d + 1] = pd[d].spans;
+            union_ms += pd[d].union_ms;
+            side_pairs += pd[d].side_pairs;
+            per_device += std::string(d ? ", " : "") + "{\"rows\": " + std::to_string(pd[d].rows) + ", \"spans\": " + std::to_string(pd[d].spans) + "}";
+        }
+        per_device += "]";
+        // the exchange step: per-device {rows, spans} (bitmaps and spans are complete on the host by now)
+        if (D > 1) devs.exchange_counts(counts, "rows", "union spans", verbose, /*adopt_gathered=*/false);
+        if (verbose)
+            std::fprintf(stderr, "[INFO] rows uploaded once: %llu bytes for %zu rows; union of %llu spans (sort + span kernels %.3f ms); %llu pairs with roots that can have outside segments\n",
+                         12ull * n_regions, n_regions, (unsigned long long)union_spans, union_ms, (unsigned long long)side_pairs);
+        g_run_stats.count("gpus", static_cast<double>(D));
+        g_run_stats.count("rows", static_cast<double>(n_regions));
+        g_run_stats.count("upload_bytes", 12.0 * static_cast<double>(n_regions));
+        g_run_stats.count("union_spans", static_cast<double>(union_spans));
+        g_run_stats.count("union_kernels_ms", union_ms);
+        g_run_stats.extra("devices", per_device);
+        timer.lap("Join A + union build on the device (one upload per batch, kernels, bitmaps and spans D2H)");
+
         // per (block, ID) group of the hit blocks: the union of its lines as disjoint segments, and its extent
         struct Seg {
             uint32_t group, start, end;
@@ -96,9 +301,6 @@ void run(const CoverageArgs &args) {
         std::vector<uint32_t> seg_seq, seg_start, seg_end;  // the device's share
         std::vector<uint32_t> g_min(t.group_id.size(), 0xFFFFFFFFu), g_max(t.group_id.size(), 0);
         std::vector<uint8_t> g_hit(t.group_id.size(), 0);
-        std::vector<uint32_t> block_fid(t.block_line_off.size() - 1, 0xFFFFFFFFu);
-        for (uint32_t f = 0; f < t.block_of_fid.size(); ++f)
-            if (t.block_of_fid[f] != 0xFFFFFFFFu) block_fid[t.block_of_fid[f]] = f;
         std::vector<uint32_t> hit_blocks;
         for (uint32_t fid : hit_roots)
             if (fid < t.block_of_fid.size() && t.block_of_fid[fid] != 0xFFFFFFFFu) hit_blocks.push_back(t.block_of_fid[fid]);
@@ -137,13 +339,13 @@ void run(const CoverageArgs &args) {
             std::fprintf(stderr, "[INFO] %zu hit blocks, %zu segments (%zu evaluated on the host)\n", hit_blocks.size(),
                          segs.size(), segs.size() - seg_seq.size());
         timer.lap("Segments of the hit blocks");
-        // device: covered bases of the segments inside their root, under the union of all regions of the seqid
+        // device 0: covered bases of the segments inside their root, under the union of all regions of the seqid
         std::vector<uint32_t> cov_fast(std::max<size_t>(seg_seq.size(), 1), 0);
-        if (gffx_hip_segments_covered(args.device, seg_seq.size(), seg_seq.data(), seg_start.data(), seg_end.data(), flat.data(),
-                                      n_regions, n_seq, cov_fast.data()) != GFFX_OK)
-            hip_fail("gffx_hip_segments_covered");
-        timer.lap("Covered bases on the device (union build, upload, kernel, D2H)");
-        // host: the segments that stick out of their root, against the root's own merged list (coverage.rs:401)
+        if (gffx_hip_union_segments_covered(U, seg_seq.size(), seg_seq.data(), seg_start.data(), seg_end.data(), cov_fast.data()) != GFFX_OK)
+            hip_fail("gffx_hip_union_segments_covered");
+        timer.lap("Covered bases on the device (segments H2D, kernel, D2H)");
+        // host: the segments that stick out of their root, against the root's own merged list (coverage.rs:401) -- the rows
+        // Join A paired with the root on the side index, from all devices
         std::vector<uint64_t> breadth(t.group_id.size(), 0);
         std::unordered_map<uint32_t, std::vector<Span>> root_cov;  // block -> merged regions that hit its root
         std::vector<uint32_t> group_block(t.group_id.size(), 0);
@@ -158,13 +360,13 @@ void run(const CoverageArgs &args) {
             const uint32_t b = group_block[sg.group];
             auto it = root_cov.find(b);
             if (it == root_cov.end()) {
+                const uint32_t fid = block_fid[b];
+                if (!(fid < side_fid.size() && side_fid[fid])) throw Error("coverage: a segment outside its root in a block that has none");
                 std::vector<Span> hit;
-                for (const uint32_t *rg = flat.data(); rg < flat.data() + 3 * n_regions; rg += 3)
-                    for (const auto &iv : ivs[block_fid[b]])
-                        if (rg[0] == std::get<0>(iv) && std::get<1>(iv) < rg[2] && std::get<2>(iv) > rg[1]) {
-                            hit.emplace_back(rg[1], rg[2]);  // a region once per root (coverage.rs:263-266)
-                            break;
-                        }
+                for (PerDevice &P : pd) {
+                    const auto rr = P.root_rows.find(fid);
+                    if (rr != P.root_rows.end()) hit.insert(hit.end(), rr->second.begin(), rr->second.end());
+                }
                 it = root_cov.emplace(b, merge_intervals(std::move(hit))).first;
             }
             breadth[sg.group] += covered(it->second, sg.start, sg.end);
@@ -196,7 +398,7 @@ void run(const CoverageArgs &args) {
                 r.b += breadth[g];
             }
         }
-        append_rows_parallel(out, order.size(), capped_threads(args.threads), [&](size_t k, std::string &o) {  // coverage.rs:465-473
+        append_rows_parallel(out, order.size(), threads, [&](size_t k, std::string &o) {  // coverage.rs:465-473
             const uint32_t i = order[k];
             const Row &r = rows[i];
             const uint64_t length = r.e > r.s ? r.e - r.s : 0;

@@ -366,8 +366,11 @@ struct CoverageArgs {  // coverage.rs:37-57
     size_t threads = 12;                // -t/--threads
     bool verbose = false;               // -v/--verbose
     int device = 0;                     // --device (addition)
+    int gpus = 1;                       // --gpus (addition: the BED or BAM rows in batches over N MI355X, bitmaps and unions merged)
 };
 
+// GFFX_COVERAGE_BATCH_ROWS sets the rows per device batch (default 4 Mi rows; a positive decimal number, anything else is
+// ignored): it bounds the staging buffers and the union's folds, and results never depend on it.
 void run(const CoverageArgs &args);  // coverage.rs:487-582
 
 }  // namespace coverage

@@ -130,7 +130,9 @@ const char *kCoverageUsage =
     "  -o, --output <FILE>      Output file (stdout if not provided)\n"
     "  -t, --threads <NUM>      Number of threads for parallel processing [default: 12]\n"
     "  -v, --verbose            Enable verbose output\n"
-    "      --device <N>         HIP device to run on [default: 0]\n";
+    "      --device <N>         HIP device to run on [default: 0]\n"
+    "      --gpus <N>           Spread the BED or BAM rows over N devices [default: 1]\n"
+    "      --stats-json <FILE>  Write the run's stage timers and counts as one JSON object\n";
 
 const char *kIndexUsage =
     "Usage: gffx index [OPTIONS] --input <INPUT>\n\nOptions:\n"
@@ -214,7 +216,7 @@ int run_depth_cli(int argc, char **argv) {
 int run_coverage_cli(int argc, char **argv) {
     static const std::vector<OptSpec> specs = {{'i', "input", true},   {'s', "source", true},   {'o', "output", true},
                                                {'t', "threads", true}, {'v', "verbose", false}, {0, "device", true},
-                                               {0, "stats-json", true}, {'h', "help", false}};
+                                               {0, "gpus", true},      {0, "stats-json", true}, {'h', "help", false}};
     const auto o = parse_opts(argc, argv, 2, specs);
     if (o.count("help")) {
         std::fputs(kCoverageUsage, stdout);
@@ -230,6 +232,7 @@ int run_coverage_cli(int argc, char **argv) {
     if (o.count("threads")) a.threads = parse_size(o.at("threads")[0], "--threads <NUM>");
     a.verbose = o.count("verbose") > 0;
     if (o.count("device")) a.device = static_cast<int>(parse_size(o.at("device")[0], "--device <N>"));
+    if (o.count("gpus")) a.gpus = static_cast<int>(std::max<size_t>(1, std::min<size_t>(64, parse_size(o.at("gpus")[0], "--gpus <N>"))));
     if (o.count("stats-json")) g_run_stats.path = o.at("stats-json")[0];
     commands::coverage::run(a);
     return 0;

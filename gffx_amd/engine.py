@@ -441,6 +441,66 @@ def segments_covered(seg_seq, seg_start, seg_end, regions, n_seq: int, device: i
     return out[: len(q)]
 
 
+class RegionUnion:
+    """merge_intervals (commands/coverage.rs:92-109) over all rows added, per seqid, built on the device: sorted, disjoint,
+    non-touching spans.  Any grouping of the rows into ``add`` calls gives the same spans."""
+
+    def __init__(self, n_seq: int, device: int = 0):
+        self.n_seq = int(n_seq)
+        self._h = C.c_void_p()
+        check(lib().gffx_hip_union_create(device, self.n_seq, C.byref(self._h)))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().gffx_hip_union_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, rows) -> None:
+        r = _u32(rows).reshape(-1, 3)
+        check(lib().gffx_hip_union_add_host(self._h, _p(r), r.shape[0]))
+
+    def add_store(self, store_handle, k: int, first: int, n_rows: int) -> None:
+        check(lib().gffx_hip_union_add_store(self._h, store_handle, k, first, n_rows))
+
+    def add_spans(self, u_off, us, ue) -> None:
+        o = np.ascontiguousarray(u_off, dtype=np.uint64)
+        a, b = _u32(us), _u32(ue)
+        check(lib().gffx_hip_union_add_spans(self._h, o.ctypes.data_as(u64p), _p(a), _p(b)))
+
+    def finish(self) -> None:
+        check(lib().gffx_hip_union_finish(self._h))
+
+    @property
+    def n_spans(self) -> int:
+        return int(lib().gffx_hip_union_n_spans(self._h))
+
+    def spans(self):
+        """(u_off, us, ue, pb) after ``finish``."""
+        n = self.n_spans
+        o = np.zeros(self.n_seq + 1, dtype=np.uint64)
+        a, b = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+        p = np.zeros(max(n, 1), dtype=np.uint64)
+        check(lib().gffx_hip_union_copy_spans(self._h, o.ctypes.data_as(u64p), _p(a), _p(b), p.ctypes.data_as(u64p)))
+        return o, a[:n], b[:n], p[:n]
+
+    def segments_covered(self, seg_seq, seg_start, seg_end) -> np.ndarray:
+        q, s, e = _u32(seg_seq), _u32(seg_start), _u32(seg_end)
+        out = np.zeros(max(len(q), 1), dtype=np.uint32)
+        check(lib().gffx_hip_union_segments_covered(self._h, len(q), _p(q), _p(s), _p(e), _p(out)))
+        return out[: len(q)]
+
+    def stats(self) -> Dict[str, float]:
+        ms, rows, folds = C.c_double(0), C.c_uint64(0), C.c_uint64(0)
+        check(lib().gffx_hip_union_stats(self._h, C.byref(ms), C.byref(rows), C.byref(folds)))
+        return {"kernel_ms": ms.value, "rows": rows.value, "folds": folds.value}
+
+
 def run_batches(batches: Sequence["QueryBatch"], mode: int = OverlapMode.Overlap, invert: bool = False, out_flags: int = OUT_FIDS,
                 strategy: int = STRATEGY_AUTO, n_passes: Optional[int] = None) -> None:
     """gffx_hip_batches_run_n: pass i over batches[i % len(batches)], enqueued by ONE call.  Distinct batches of one index that

@@ -17,7 +17,7 @@
  *     (commands/intersect.rs:500-521)
  *   compute_hit_depth / compute_root_depth              gffx_hip_depth_* (`gffx depth`, BED source)
  *     (commands/depth.rs:121-293)
- *   merge_intervals + the two-pointer walk              gffx_hip_segments_covered (`gffx coverage`, BED source)
+ *   merge_intervals + the two-pointer walk              gffx_hip_segments_covered, gffx_hip_union_* (`gffx coverage`)
  *     (commands/coverage.rs:92-124, :339-364)
  *   bam::Reader records -> (chr, start, end) rows        gffx_hip_bgzf_inflate, gffx_hip_bam_* (BAM sources)
  *     (commands/depth.rs:297-372, coverage.rs:125-168)
@@ -170,6 +170,7 @@ typedef struct gffx_hip_lines gffx_hip_lines;
 typedef struct gffx_hip_regions gffx_hip_regions;
 typedef struct gffx_hip_depth gffx_hip_depth;
 typedef struct gffx_hip_bam gffx_hip_bam;
+typedef struct gffx_hip_union gffx_hip_union;
 
 int gffx_hip_abi_version(void);
 /* number of visible HIP devices (0 when none / no driver); never fails */
@@ -415,6 +416,35 @@ int gffx_hip_depth_copy(gffx_hip_depth *, uint64_t *depth, uint32_t *min_start, 
 int gffx_hip_segments_covered(int device, uint64_t n_seg, const uint32_t *seg_seq, const uint32_t *seg_start,
                               const uint32_t *seg_end, const uint32_t *regions, uint64_t nq, uint32_t n_seq,
                               uint32_t *covered_out);
+
+/* ---- union builder: merge_intervals (commands/coverage.rs:92-109) over all rows of a run, on the device --
+ * A union holds, per seqid, the rows added so far merged into sorted, disjoint, non-touching spans: sort by start, merge while
+ * s <= current end (touching rows merge).  Rows are (seqid, start, end) with seqid < n_seq (else GFFX_E_CHR_RANGE) and
+ * start < end (else GFFX_E_INVALID); n_seq may exceed 256.  Every _add sorts its rows together with the spans so far by
+ * (seqid, start) on the device and rebuilds the spans; the spans are the connected components of the rows, so ANY grouping of the
+ * rows into _add calls, and spans exchanged between unions with _add_spans, give the same spans bit for bit.  Device memory is
+ * bounded by the spans plus one internal fold of rows, not by the rows added; the host keeps nothing per row.
+ *   _add_host    rows in host memory (copied through a pinned staging buffer inside), any number of calls
+ *   _add_store   rows [first, first + n_rows) of the chunk last appended to a region store from staging buffer k: no second
+ *                upload.  The call returns when the rows have been read.
+ *   _add_spans   the spans of another union as _copy_spans gives them (u_off: n_seq + 1 entries)
+ *   _finish      builds pb (covered bases of the seqid's spans before this one), u_off and the directory; the union is
+ *                queryable afterwards.  A later _add makes it unfinished again.
+ *   _copy_spans  after _finish: u_off (n_seq + 1), us / ue / pb (_n_spans entries each); any pointer may be NULL
+ *   _segments_covered  after _finish: as gffx_hip_segments_covered, against the union's spans
+ *   _stats       HIP-event milliseconds of the sort and span kernels so far, rows added, device folds run
+ * After an error the object only reports it again. */
+int gffx_hip_union_create(int device, uint32_t n_seq, gffx_hip_union **out);
+int gffx_hip_union_add_host(gffx_hip_union *, const uint32_t *rows /* 3 per row */, uint64_t n_rows);
+int gffx_hip_union_add_store(gffx_hip_union *, const gffx_hip_regions *, int k, uint64_t first, uint64_t n_rows);
+int gffx_hip_union_add_spans(gffx_hip_union *, const uint64_t *u_off, const uint32_t *us, const uint32_t *ue);
+int gffx_hip_union_finish(gffx_hip_union *);
+uint64_t gffx_hip_union_n_spans(const gffx_hip_union *);
+int gffx_hip_union_copy_spans(gffx_hip_union *, uint64_t *u_off, uint32_t *us, uint32_t *ue, uint64_t *pb);
+int gffx_hip_union_segments_covered(gffx_hip_union *, uint64_t n_seg, const uint32_t *seg_seq, const uint32_t *seg_start,
+                                    const uint32_t *seg_end, uint32_t *covered_out);
+int gffx_hip_union_stats(const gffx_hip_union *, double *kernel_ms, uint64_t *rows, uint64_t *folds);
+void gffx_hip_union_destroy(gffx_hip_union *);
 
 /* ---- BAM sources of `gffx depth` / `gffx coverage` (commands/depth.rs:297-427, commands/coverage.rs:125-204) --
  * BGZF members are inflated on the device (one wave per member, device/bgzf.hip; the decoder, device/bgzf_core.hpp, is

@@ -29,6 +29,10 @@ pub struct gffx_hip_depth {
 pub struct gffx_hip_bam {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct gffx_hip_union {
+    _p: [u8; 0],
+}
 
 pub const GFFX_MODE_CONTAINED: c_int = 0; // OverlapMode::Contained       intersect.rs:75
 pub const GFFX_MODE_CONTAINS_REGION: c_int = 1; // OverlapMode::ContainsRegion  intersect.rs:76
@@ -133,6 +137,18 @@ extern "C" {
     pub fn gffx_hip_bam_stage_ms(h: *const gffx_hip_bam, inflate_ms: *mut f64, frame_ms: *mut f64, rows_ms: *mut f64) -> c_int;
     pub fn gffx_hip_bam_copy_rows(h: *mut gffx_hip_bam, rows: *mut u32) -> c_int;
     pub fn gffx_hip_bam_destroy(h: *mut gffx_hip_bam);
+    // the union of all rows of a run, built on the device (merge_intervals, coverage.rs:92-109); any grouping of the rows gives the same spans
+    pub fn gffx_hip_union_create(device: c_int, n_seq: u32, out: *mut *mut gffx_hip_union) -> c_int;
+    pub fn gffx_hip_union_add_host(u: *mut gffx_hip_union, rows: *const u32, n_rows: u64) -> c_int;
+    pub fn gffx_hip_union_add_store(u: *mut gffx_hip_union, r: *const gffx_hip_regions, k: c_int, first: u64, n_rows: u64) -> c_int;
+    pub fn gffx_hip_union_add_spans(u: *mut gffx_hip_union, u_off: *const u64, us: *const u32, ue: *const u32) -> c_int;
+    pub fn gffx_hip_union_finish(u: *mut gffx_hip_union) -> c_int;
+    pub fn gffx_hip_union_n_spans(u: *const gffx_hip_union) -> u64;
+    pub fn gffx_hip_union_copy_spans(u: *mut gffx_hip_union, u_off: *mut u64, us: *mut u32, ue: *mut u32, pb: *mut u64) -> c_int;
+    pub fn gffx_hip_union_segments_covered(u: *mut gffx_hip_union, n_seg: u64, seg_seq: *const u32, seg_start: *const u32,
+                                           seg_end: *const u32, covered_out: *mut u32) -> c_int;
+    pub fn gffx_hip_union_stats(u: *const gffx_hip_union, kernel_ms: *mut f64, rows: *mut u64, folds: *mut u64) -> c_int;
+    pub fn gffx_hip_union_destroy(u: *mut gffx_hip_union);
 }
 
 fn last_error() -> String {
