@@ -862,6 +862,8 @@ extern "C" int gffx_hip_batch_kernel_ms(gffx_hip_batch *b, int kernel_id, double
 // the cost of an event pair per launch (which adds ~3 us to a ~18 us kernel)
 extern "C" uint32_t gffx_hip_batch_block_threads(const gffx_hip_batch *b) { return b ? b->win_threads : 0; }
 extern "C" uint32_t gffx_hip_batch_block_count(const gffx_hip_batch *b) { return b ? b->win_blocks : 0; }
+extern "C" uint32_t gffx_hip_batch_block_share(const gffx_hip_batch *b) { return b ? b->win_share : 0; }
+extern "C" uint32_t gffx_hip_batch_filter_level(const gffx_hip_batch *b) { return b ? b->win_filter_level : 0; }
 extern "C" int gffx_hip_batch_wide_form(const gffx_hip_batch *b) { return b && b->wide ? 1 : 0; }
 
 extern "C" int gffx_hip_batch_timed_runs(gffx_hip_batch *b, int mode, int invert, uint32_t out_flags, int strategy, uint32_t n,
@@ -889,7 +891,8 @@ extern "C" int gffx_hip_batch_timed_runs(gffx_hip_batch *b, int mode, int invert
 // the windows strategy TOGETHER -- one launch per group of up to kPairMaxSubs batches (engine_windows.hip: run_windows_group) --
 // whenever every batch of the group resolves to the same kernel; anything else runs pass by pass as before (plan_groups below says
 // how the passes are cut into groups).
-static int run_group(gffx_hip_batch *const *bs, uint32_t n, int mode, int invert, uint32_t out_flags, int strategy, int which_stream) {
+static int run_group(gffx_hip_batch *const *bs, uint32_t n, int mode, int invert, uint32_t out_flags, int strategy, int which_stream,
+                     bool alternating = false) {
     bool launch[kPairMaxSubs];
     bool all = n >= 2;
     for (uint32_t t = 0; t < n; ++t) {
@@ -904,7 +907,7 @@ static int run_group(gffx_hip_batch *const *bs, uint32_t n, int mode, int invert
         }
         all = all && launch[t];
     }
-    if (all && windows_groupable(bs, n)) return run_windows_group(bs, n, which_stream);
+    if (all && windows_groupable(bs, n)) return run_windows_group(bs, n, which_stream, alternating);
     for (uint32_t t = 0; t < n; ++t)
         if (launch[t]) {
             const int rc = batch_launch_run(bs[t]);
@@ -963,7 +966,7 @@ extern "C" int gffx_hip_batches_run_n(gffx_hip_batch *const *batches, uint32_t n
         const uint32_t c = (uint32_t)(chunk % plan.cycle);
         const uint32_t n = (uint32_t)std::min<uint64_t>(plan.size[c], n_passes - i);
         for (uint32_t t = 0; t < n; ++t) bs[t] = batches[(i + t) % n_batches];
-        const int rc = run_group(bs, n, mode, invert, out_flags, strategy, (int)(c % plan.streams));
+        const int rc = run_group(bs, n, mode, invert, out_flags, strategy, (int)(c % plan.streams), plan.cycle == 2 && plan.streams == 2);
         if (rc) return rc;
         i += n;
     }

@@ -287,8 +287,83 @@ static bool build_window_ranks(uint32_t n_chr, const uint32_t *chr_offsets, cons
     return ok;
 }
 
-// Coverage filter of the window index (gffx_device.hpp): the smallest cell size whose bitmap fits GFFX_HIP_WIN_FILTER_KB
-// (default 24 KB of LDS per block; 48 KB measured 1.5 % faster at 10 M regions, 1.5 % slower at 1 M), but never so small that a region the lines answer (width <= wmax) spans more than 32 cells.
+// Coverage filter of the window index (gffx_device.hpp), two levels.  The COARSE one: the smallest cell size whose bitmap fits
+// GFFX_HIP_WIN_FILTER_KB (default 24 KB: it fits beside the strips of every pair pass), but never so small that a region the lines
+// answer (width <= wmax) spans more than 31 cells.  The FINE one (build_window_filter_fine): the smallest cell below the coarse
+// one's, under the same 31-cell rule, whose bitmap fits GFFX_HIP_WIN_FILTER_FINE_KB and the LDS a 1024-thread pair pass has left
+// beside its strips (windows_filter_room) -- for the launches with room for it (run_windows_pass takes the finest filter that fits).
+static uint64_t filter_cells(const uint32_t *chr_offsets, const std::vector<uint32_t> &h_start, const std::vector<uint4> &h_aux, uint32_t c,
+                             uint32_t sh) {
+    const uint32_t lo = chr_offsets[c], hi = chr_offsets[c + 1];
+    if (hi == lo) return 0;
+    const uint64_t max_pos = std::max<uint64_t>(std::max(h_aux[hi - 1].x, h_aux[hi - 1].y), h_start[hi - 1]);  // (starts ascend)
+    return (max_pos >> sh) + 1;
+}
+// the smallest shift at which a region of width <= wmax touches <= (wmax >> sh) + 2 <= 31 cells (the kernel tests 31)
+static uint32_t filter_min_shift(uint32_t n_chr, const std::vector<uint4> &win_meta) {
+    uint32_t wmax_all = 1;
+    for (uint32_t c = 0; c < n_chr; c++) wmax_all = std::max(wmax_all, win_meta[c].w);
+    uint32_t sh = 0;
+    while (sh < 31 && ((uint64_t)wmax_all >> sh) + 2 > 31) sh++;
+    return sh;
+}
+// words of the bitmap with every seqid's cells rounded up to whole words (+ the spare word, staged 16 bytes at a time)
+static uint64_t filter_words(uint32_t n_chr, const uint32_t *chr_offsets, const std::vector<uint32_t> &h_start, const std::vector<uint4> &h_aux,
+                             uint32_t sh) {
+    uint64_t tot = 0;
+    for (uint32_t c = 0; c < n_chr; c++) tot += (filter_cells(chr_offsets, h_start, h_aux, c, sh) + 31) / 32;
+    return (tot + 1 + 3) / 4 * 4;
+}
+// The bitmap at cells of 2^sh bp.  `fold_words` > 0: the bitmap is that many words too long for its place -- the seqids with the
+// fewest cells then get no words of their own: their bits are ORed over the first words of the seqid with the most (a set bit
+// costs a line read, never a pair: the filter stays exact on "clear = no hit"; a folded seqid and its host answer a few lines more
+// than they had to).  false: not that many words can be folded (at most the host's own).
+static bool fill_window_filter(uint32_t n_chr, const uint32_t *chr_offsets, const std::vector<uint32_t> &h_start, const std::vector<uint4> &h_aux,
+                               uint32_t sh, uint64_t fold_words, std::vector<uint32_t> &bits, std::vector<uint2> &fmeta) {
+    fmeta.assign(n_chr + 1, make_uint2(0, 0));
+    bits.clear();
+    std::vector<uint64_t> nc(n_chr);
+    std::vector<uint32_t> by_size;
+    for (uint32_t c = 0; c < n_chr; c++) {
+        nc[c] = filter_cells(chr_offsets, h_start, h_aux, c, sh);
+        if (nc[c]) by_size.push_back(c);
+    }
+    std::stable_sort(by_size.begin(), by_size.end(), [&](uint32_t a, uint32_t b) { return nc[a] < nc[b]; });
+    std::vector<char> folded(n_chr, 0);
+    uint64_t host_room = by_size.empty() ? 0 : (nc[by_size.back()] + 31) / 32, moved = 0;
+    for (size_t k = 0; moved < fold_words && k + 1 < by_size.size(); k++) {
+        const uint64_t w = (nc[by_size[k]] + 31) / 32;
+        if (moved + w > host_room) break;
+        folded[by_size[k]] = 1;
+        moved += w;
+    }
+    if (moved < fold_words) return false;
+    for (uint32_t c = 0; c < n_chr; c++) {  // the seqids with words of their own, in order
+        if (!nc[c] || folded[c]) continue;
+        fmeta[c] = make_uint2((uint32_t)bits.size() * 32u, (uint32_t)nc[c]);
+        bits.resize(bits.size() + (nc[c] + 31) / 32, 0u);
+    }
+    uint32_t at = by_size.empty() ? 0u : fmeta[by_size.back()].x;
+    for (uint32_t c = 0; c < n_chr; c++) {  // ... the folded ones side by side over the host's first words
+        if (!folded[c]) continue;
+        fmeta[c] = make_uint2(at, (uint32_t)nc[c]);
+        at += (uint32_t)((nc[c] + 31) / 32) * 32u;
+    }
+    for (uint32_t c = 0; c < n_chr; c++) {
+        const uint32_t lo = chr_offsets[c], hi = chr_offsets[c + 1], base = fmeta[c].x;
+        for (uint32_t i = lo; i < hi; i++) {
+            // a region keeps the root only if start < qe && end > qs: it then holds a base of [start, end) -- or, for an EMPTY
+            // interval (end == start: the reference keeps it when qs < start < qe), the base `start`.  (end < start is outside
+            // the domain: the reference's IntervalTree::build never terminates on one, tree.rs:48-50.)
+            const uint64_t a = (uint64_t)h_start[i] >> sh, b = h_aux[i].x > h_start[i] ? ((uint64_t)h_aux[i].x - 1) >> sh : a;
+            for (uint64_t x = a; x <= b && x < nc[c]; x++) bits[(base + x) >> 5] |= 1u << ((base + x) & 31);
+        }
+    }
+    bits.push_back(0u);                           // (the kernel reads word pairs)
+    while (bits.size() & 3u) bits.push_back(0u);  // (... and stages the bitmap 16 bytes at a time)
+    return true;
+}
+
 static void build_window_filter(uint32_t n_chr, const uint32_t *chr_offsets, const std::vector<uint32_t> &h_start,
                                 const std::vector<uint4> &h_aux, const std::vector<uint4> &win_meta, std::vector<uint32_t> &bits,
                                 std::vector<uint2> &fmeta, uint32_t &fshift, const Knobs<IK__COUNT> &K) {
@@ -297,40 +372,43 @@ static void build_window_filter(uint32_t n_chr, const uint32_t *chr_offsets, con
     fshift = 0;
     const uint64_t budget_bits = (uint64_t)K.v[IK_WIN_FILTER_KB] * 1024 * 8;
     if (!budget_bits) return;
-    auto cells_of = [&](uint32_t c, uint32_t sh) -> uint64_t {
-        const uint32_t lo = chr_offsets[c], hi = chr_offsets[c + 1];
-        if (hi == lo) return 0;
-        const uint64_t max_pos = std::max<uint64_t>(std::max(h_aux[hi - 1].x, h_aux[hi - 1].y), h_start[hi - 1]);  // (starts ascend)
-        return (max_pos >> sh) + 1;
-    };
-    uint32_t wmax_all = 1;
-    for (uint32_t c = 0; c < n_chr; c++) wmax_all = std::max(wmax_all, win_meta[c].w);
-    uint32_t sh = 0;
-    while (sh < 31 && ((uint64_t)wmax_all >> sh) + 2 > 31) sh++;  // a region of width <= wmax touches <= (wmax >> sh) + 2 cells (the kernel tests 31)
+    uint32_t sh = filter_min_shift(n_chr, win_meta);
     for (; sh < 32; sh++) {
         uint64_t tot = 0;
-        for (uint32_t c = 0; c < n_chr; c++) tot += (cells_of(c, sh) + 31) / 32 * 32;
+        for (uint32_t c = 0; c < n_chr; c++) tot += (filter_cells(chr_offsets, h_start, h_aux, c, sh) + 31) / 32 * 32;
         if (tot <= budget_bits) break;
     }
     if (sh >= 32) return;
     fshift = sh;
-    for (uint32_t c = 0; c < n_chr; c++) {
-        const uint32_t lo = chr_offsets[c], hi = chr_offsets[c + 1];
-        const uint64_t nc = cells_of(c, sh);
-        if (!nc) continue;
-        const uint32_t base = (uint32_t)bits.size() * 32u;
-        fmeta[c] = make_uint2(base, (uint32_t)nc);
-        bits.resize(bits.size() + (nc + 31) / 32, 0u);
-        for (uint32_t i = lo; i < hi; i++) {
-            // a region keeps the root only if start < qe && end > qs: it then holds a base of [start, end) -- or, for an EMPTY
-            // interval (end == start: the reference keeps it when qs < start < qe), the base `start`.  (end < start is outside
-            // the domain: the reference's IntervalTree::build never terminates on one, tree.rs:48-50.)
-            const uint64_t a = (uint64_t)h_start[i] >> sh, b = h_aux[i].x > h_start[i] ? ((uint64_t)h_aux[i].x - 1) >> sh : a;
-            for (uint64_t x = a; x <= b && x < nc; x++) bits[(base + x) >> 5] |= 1u << ((base + x) & 31);
+    fill_window_filter(n_chr, chr_offsets, h_start, h_aux, sh, 0, bits, fmeta);
+}
+
+// The fine level: the smallest cell below the coarse one's (`coarse_shift`; the index has a coarse filter) whose bitmap takes at
+// most `room_bytes` -- with up to an eighth of its words folded away where it misses by that little: on a GRCh38-sized index the
+// 2^13 bitmap (46.0 KB) is about 2 KB more than a 1024-thread pair pass has left, and folding the four shortest seqids closes
+// that.  No such cell (or a budget of 0): bits stays empty, the index has the coarse filter alone.
+static void build_window_filter_fine(uint32_t n_chr, const uint32_t *chr_offsets, const std::vector<uint32_t> &h_start,
+                                     const std::vector<uint4> &h_aux, const std::vector<uint4> &win_meta, uint32_t coarse_shift,
+                                     uint64_t room_bytes, std::vector<uint32_t> &bits, std::vector<uint2> &fmeta, uint32_t &fshift,
+                                     const Knobs<IK__COUNT> &K) {
+    fmeta.assign(n_chr + 1, make_uint2(0, 0));
+    bits.clear();
+    fshift = 0;
+    const uint64_t room_words = std::min<uint64_t>((uint64_t)K.v[IK_WIN_FILTER_FINE_KB] * 1024, room_bytes) / 4;
+    for (uint32_t sh = filter_min_shift(n_chr, win_meta); sh < coarse_shift; sh++) {
+        const uint64_t words = filter_words(n_chr, chr_offsets, h_start, h_aux, sh);
+        const uint64_t over = words > room_words ? words - room_words : 0;
+        if (over > words / 8) continue;
+        if (!fill_window_filter(n_chr, chr_offsets, h_start, h_aux, sh, over, bits, fmeta)) continue;
+        if (bits.size() > room_words) {  // (the folded seqids' words are whole: the padding may differ by a word or two)
+            bits.clear();
+            continue;
         }
+        fshift = sh;
+        return;
     }
-    bits.push_back(0u);                           // (the kernel reads word pairs)
-    while (bits.size() & 3u) bits.push_back(0u);  // (... and stages the bitmap 16 bytes at a time)
+    fmeta.assign(n_chr + 1, make_uint2(0, 0));
+    bits.clear();
 }
 
 }  // namespace gffx
@@ -531,6 +609,13 @@ extern "C" int gffx_hip_index_create(uint32_t n_chr, const uint32_t *chr_offsets
     std::vector<uint32_t> win_filter;
     std::vector<uint2> win_fmeta;
     build_window_filter(n_chr, chr_offsets, h_start, h_aux, win_meta, win_filter, win_fmeta, ix->win_fshift, ix->knobs);
+    // ... and the fine level, for the launches with room for it: its own bitmap, and its own copy of the seqid records (the kernels
+    // take the filter's first bit from the record: only .w differs)
+    std::vector<uint32_t> win_filter_fine;
+    std::vector<uint2> win_fmeta_fine;
+    if (!win_filter.empty())
+        build_window_filter_fine(n_chr, chr_offsets, h_start, h_aux, win_meta, ix->win_fshift, windows_filter_room(n_chr, ix->win_swords),
+                                 win_filter_fine, win_fmeta_fine, ix->win_fshift_fine, ix->knobs);
     // the kernel's seqid record: {first window, windows, shift | wmax << 8, first filter bit}
     // (a seqid without windows AND without roots -- and the extra record -- answers "fits, but beyond my last window" for every
     //  sane row: wmax = 2^24 - 1, no windows; only its empty / reversed / absurdly wide rows reach the sweep, which returns at once)
@@ -540,6 +625,13 @@ extern "C" int gffx_hip_index_create(uint32_t n_chr, const uint32_t *chr_offsets
                                : make_uint4(win_meta[c].x, win_meta[c].y, win_meta[c].z | (win_meta[c].w << 8), win_fmeta[c].x);
     }
     ix->win_fwords = (uint32_t)win_filter.size();
+    ix->win_fwords_fine = (uint32_t)win_filter_fine.size();
+    std::vector<uint4> win_meta_fine;
+    if (ix->win_fwords_fine) {
+        win_meta_fine = win_meta;
+        for (uint32_t c = 0; c < n_chr; c++)
+            if (chr_offsets[c + 1] != chr_offsets[c]) win_meta_fine[c].w = win_fmeta_fine[c].x;
+    }
 
     // Partitioned strategy: cells of 2^cshift bp (<= kMaxCells in total, >= 1 per seqid) merged into
     // tiles of <= kTileEntries entries; per tile a 1024-bin u16 directory over start (gffx_device.hpp).
@@ -636,7 +728,8 @@ extern "C" int gffx_hip_index_create(uint32_t n_chr, const uint32_t *chr_offsets
         (rc = dev_upload(&ix->d_win_meta, win_meta)) ||
         (rc = upload_line_tables(ix.get(), win, win_pos, win_wide, sub_at, sub_lines, sub_lines_pos, wide_at, wide_sub, &win_all_bytes)) ||
         (rc = dev_upload(&ix->d_win_spill, win_spill)) ||
-        (rc = dev_upload(&ix->d_win_filter, win_filter)) || (rc = dev_upload(&ix->d_win_splittab, win_splittab)) ||
+        (rc = dev_upload(&ix->d_win_filter, win_filter)) || (rc = dev_upload(&ix->d_win_filter_fine, win_filter_fine)) ||
+        (rc = dev_upload(&ix->d_win_meta_fine, win_meta_fine)) || (rc = dev_upload(&ix->d_win_splittab, win_splittab)) ||
         (rc = dev_upload(&ix->d_root_fids, root_fids)) || (rc = dev_upload(&ix->d_root_ends, root_ends)) ||
         (rc = dev_upload(&ix->d_cell_base, cell_base)) || (rc = dev_upload(&ix->d_cell_tile, cell_tile)) ||
         (rc = dev_upload(&ix->d_tile_meta, tile_meta)) || (rc = dev_upload(&ix->d_tile_aux, tile_aux)) ||
@@ -647,6 +740,7 @@ extern "C" int gffx_hip_index_create(uint32_t n_chr, const uint32_t *chr_offsets
     auto bytes = [](const auto &v) { return std::max<size_t>(v.size(), 1) * sizeof(v[0]); };
     ix->array_bytes = {bytes(h_start),   bytes(h_aux),     bytes(chr_meta),   bytes(bins),
                        bytes(win_meta),  win_all_bytes,     bytes(win_spill), bytes(win_filter),
+                       bytes(win_filter_fine), bytes(win_meta_fine),
                        bytes(win_splittab), bytes(root_fids), bytes(root_ends),
                        bytes(cell_base), bytes(cell_tile), bytes(tile_meta),  bytes(tile_aux),  bytes(tile_bins), bytes(tile_desc)};
     ix->win_range_ok = ix->win_range_ok && ix->win_all_ok();  // (the mixed form addresses the three line tables through one descriptor)
@@ -698,6 +792,8 @@ extern "C" void gffx_hip_index_destroy(gffx_hip_index *ix) {
     (void)hipFree(ix->d_win_all);  // (d_win, d_win_pos, d_win_wide point into it)
     (void)hipFree(ix->d_win_spill);
     (void)hipFree(ix->d_win_filter);
+    (void)hipFree(ix->d_win_filter_fine);
+    (void)hipFree(ix->d_win_meta_fine);
     (void)hipFree(ix->d_win_splittab);
     (void)hipFree(ix->d_root_fids);
     (void)hipFree(ix->d_root_ends);

@@ -50,20 +50,21 @@ struct KnobDef {
     const char *name;
     long dflt, lo, hi;
 };
-enum IndexKnob { IK_WIN_PER_ENTRY, IK_SLOT_WMAX, IK_WIN_MAX_LINES, IK_WIN_SPLIT, IK_WIN_FILTER_KB, IK_BINS_PER_ENTRY, IK__COUNT };
+enum IndexKnob { IK_WIN_PER_ENTRY, IK_SLOT_WMAX, IK_WIN_MAX_LINES, IK_WIN_SPLIT, IK_WIN_FILTER_KB, IK_BINS_PER_ENTRY, IK_WIN_FILTER_FINE_KB, IK__COUNT };
 constexpr KnobDef kIndexKnobs[IK__COUNT] = {{"GFFX_HIP_WIN_PER_ENTRY", 2, 1, 16},         {"GFFX_HIP_SLOT_WMAX", 16384, 1, 1 << 30},
                                             {"GFFX_HIP_WIN_MAX_LINES", 1l << 25, 64, 1l << 25}, {"GFFX_HIP_WIN_SPLIT", 1, 0, 1},
-                                            {"GFFX_HIP_WIN_FILTER_KB", 24, 0, 120},         {"GFFX_HIP_BINS_PER_ENTRY", 2, 1, 64}};
+                                            {"GFFX_HIP_WIN_FILTER_KB", 24, 0, 120},         {"GFFX_HIP_BINS_PER_ENTRY", 2, 1, 64},
+                                            {"GFFX_HIP_WIN_FILTER_FINE_KB", 48, 0, 120}};
 enum BatchKnob {
     BK_AUTO_STRATEGY, BK_FUSED_BLOCKS, BK_BITMAP_BLOCKS, BK_JOIN_BLOCKS, BK_MAX_BLOCKS, BK_PARTITION_BUDGET_MB, BK_WIDTH_SAMPLE, BK_WIN_THREADS,
-    BK_WIN_WIDE, BK_GROUP, BK_TICKETS, BK__COUNT
+    BK_WIN_WIDE, BK_GROUP, BK_TICKETS, BK_WIN_FILTER, BK__COUNT
 };
 constexpr KnobDef kBatchKnobs[BK__COUNT] = {{"GFFX_HIP_AUTO_STRATEGY", 0, 0, 5},   {"GFFX_HIP_FUSED_BLOCKS", 0, 0, 65535},
                                             {"GFFX_HIP_BITMAP_BLOCKS", 0, 0, 8192}, {"GFFX_HIP_JOIN_BLOCKS", 512, 1, 65535},
                                             {"GFFX_HIP_MAX_BLOCKS", 2048, 1, 8192}, {"GFFX_HIP_PARTITION_BUDGET_MB", 12 * 1024, 1, 256 * 1024},
                                             {"GFFX_HIP_WIDTH_SAMPLE", 1, 0, 1},     {"GFFX_HIP_WIN_THREADS", 0, 0, 1024},
                                             {"GFFX_HIP_WIN_WIDE", 1, 0, 2},          {"GFFX_HIP_GROUP", 2, 0, 3},
-                                            {"GFFX_HIP_TICKETS", 4, 0, 4}};
+                                            {"GFFX_HIP_TICKETS", 4, 0, 4},           {"GFFX_HIP_WIN_FILTER", 0, 0, 2}};
 template <int N>
 struct Knobs {
     long v[N];
@@ -148,6 +149,10 @@ struct gffx_hip_index {
     uint32_t n_win = 0;
     uint32_t *d_win_filter = nullptr;
     uint32_t win_fwords = 0, win_fshift = 0;
+    // the fine level of the coverage filter (engine_index.hip): its bitmap, and a copy of the seqid records with ITS first bits in .w
+    uint32_t *d_win_filter_fine = nullptr;
+    uint4 *d_win_meta_fine = nullptr;
+    uint32_t win_fwords_fine = 0, win_fshift_fine = 0;  // 0 words: the index has the coarse filter alone
     uint32_t *d_win_splittab = nullptr;  // split windows (k_join_pairs): one bit per window; their sub-lines follow the lines in d_win / d_win_pos
     uint32_t win_swords = 0;
     uint4 *d_win_wide = nullptr;  // the wide form's lines: {coordinates x 4 | rank, list-tail header, 0, 0}, both levels (into d_win_all)
@@ -182,6 +187,7 @@ struct gffx_hip_index {
     std::vector<void **> arrays() {
         return {(void **)&d_start,     (void **)&d_aux,       (void **)&d_chr_meta,   (void **)&d_bins,       (void **)&d_win_meta,   (void **)&d_win_all,
                 (void **)&d_win_spill, (void **)&d_win_filter,
+                (void **)&d_win_filter_fine, (void **)&d_win_meta_fine,
                 (void **)&d_win_splittab, (void **)&d_root_fids, (void **)&d_root_ends,
                 (void **)&d_cell_base,
                 (void **)&d_cell_tile, (void **)&d_tile_meta, (void **)&d_tile_aux,   (void **)&d_tile_bins,  (void **)&d_tile_desc};
@@ -289,6 +295,8 @@ struct gffx_hip_batch {
     bool ran = false, waited = false;
     uint32_t win_threads = 0;  // block width of the last windows pair pass (gffx_hip_batch_block_threads)
     uint32_t win_blocks = 0;   // ... and its grid (gffx_hip_batch_block_count)
+    uint32_t win_share = 0;    // ... the batch's own blocks of that grid (a launch that serves a group: gffx_hip_batch_block_share)
+    uint32_t win_filter_level = 0;  // coverage filter of the last windows launch: 0 none, 1 coarse, 2 fine (gffx_hip_batch_filter_level)
     int others = 0;            // at the last run: how many OTHER batches of the index had passes in flight
     bool others_busy = false;  // at the last run: another batch of the index had passes in flight (co-resident kernels)
     bool busy = false;  // counted in ix->busy_batches: a pass was enqueued since the last stream synchronisation
@@ -322,9 +330,13 @@ struct WidthSample {
 void sample_widths(WidthSample &w, uint64_t rows, uint64_t step, const uint32_t *chr, const uint32_t *start, const uint32_t *end, size_t stride,
                    const std::vector<uint32_t> &h_wmax);
 int run_windows(gffx_hip_batch *b);  // engine_windows.hip
+// bytes of LDS a 1024-thread pair pass (no per-region offsets) has left for a coverage filter beside the split bitmap, the seqid
+// records and its strips: what the index sizes its fine filter to
+uint32_t windows_filter_room(uint32_t n_chr, uint32_t swords);
 // one launch per pass kind for ALL the batches (same index, mode, invert, flags, form; every one with regions; prepared by
-// batch_prepare_run), on a stream of the index
-int run_windows_group(gffx_hip_batch *const *bs, uint32_t n, int which_stream);
+// batch_prepare_run), on a stream of the index.  `alternating`: the launch is one of TWO groups that gffx_hip_batches_run_n alternates
+// between on two streams (the next launch on the other stream is queued behind this one: engine_windows.hip, `slots`)
+int run_windows_group(gffx_hip_batch *const *bs, uint32_t n, int which_stream, bool alternating);
 bool windows_groupable(gffx_hip_batch *const *bs, uint32_t n);
 int windows_pack_roots(gffx_hip_batch *b);
 int batch_own_stream(gffx_hip_batch *b);       // engine_batch.hip: the batch's own stream, behind whatever ran for the batch elsewhere

@@ -59,13 +59,18 @@ __global__ void k_expand_pairs(const uint32_t *start, const uint4 *aux, uint32_t
 
 // dynamic LDS: coverage filter + split bitmap + seqid records, and for the pair passes header + strips + parked offsets +
 // per-thread strips
-static uint32_t pairs_lds_bytes(const gffx_hip_index *ix, uint32_t threads, bool roots, uint32_t keep_words, uint32_t fwords, uint32_t swords,
+static uint32_t pairs_lds_bytes(uint32_t n_chr, uint32_t threads, bool roots, uint32_t keep_words, uint32_t fwords, uint32_t swords,
                                 bool ml, uint32_t bm_words = 0, bool wide = false) {
     const uint32_t sw4 = swords ? (swords + 4) / 4 * 4 : 0;
-    const uint32_t tables = 4 * fwords + 4 * sw4 + (ml ? (ix->n_chr + 1) * 16 : 0);
+    const uint32_t tables = 4 * fwords + 4 * sw4 + (ml ? (n_chr + 1) * 16 : 0);
     if (roots) return tables + 16 + (uint32_t)sizeof(PairTickets) + 4 * bm_words;  // (+ the block's pair count, the ticket words)
     return tables + kWaveHdrBytes + 4 * (threads / 64) * pair_depth(wide) * pair_stage_words(threads, wide) +
            4 * threads * pair_depth(wide) * keep_words + 4 * pair_stash_words(threads) * threads;
+}
+
+uint32_t gffx::windows_filter_room(uint32_t n_chr, uint32_t swords) {
+    const uint32_t rest = pairs_lds_bytes(n_chr, 1024, false, 0, 0, swords, n_chr * 16u <= kMetaLdsBytes);
+    return rest < 2 * kWinMaxLds ? (2 * kWinMaxLds - rest) / 16 * 16 : 0;
 }
 
 // Threads per block.  The waves of a pass are independent, so the block width only sets how many regions share one
@@ -82,7 +87,7 @@ static uint32_t pair_threads(const gffx_hip_batch *b, uint64_t nq_launch, bool o
 // positions in place of the root_fids (triples); 3: root pass.  `second`: a root pass behind a pair pass over the same regions (its
 // own cursor words, its own sweep counter).  Every batch gets a share of the launch's blocks in proportion to its rounds
 // (PairSub::first_block, ::n_blocks); inside a batch the rounds beyond the blocks' first ones are taken by ticket.
-static int run_windows_pass(gffx_hip_batch *const *bs, uint32_t n, hipStream_t stream, int kind, bool second) {
+static int run_windows_pass(gffx_hip_batch *const *bs, uint32_t n, hipStream_t stream, int kind, bool second, bool alternating) {
     gffx_hip_batch *b0 = bs[0];
     const gffx_hip_index *ix = b0->ix;
     const bool roots = kind == 3, pos = kind != 1;
@@ -142,8 +147,15 @@ static int run_windows_pass(gffx_hip_batch *const *bs, uint32_t n, hipStream_t s
     const uint32_t keep_words = offs ? 2u : 0u;
     // the wide form (gffx_device.hpp, "ranks"): the passes of a batch AUTO found mostly wider than the lines answer; it reads no filter
     const bool wide = b0->wide;
-    uint32_t fwords = wide ? 0u : (ix->win_fwords + 3) / 4 * 4, swords = ix->win_swords;
-    if (fwords < 4) fwords = 0;
+    const uint32_t fwords_coarse = wide || ix->win_fwords < 4 ? 0u : (ix->win_fwords + 3) / 4 * 4;
+    // The fine level is 21 KB more to stage per block on a GRCh38-sized index: it pays from four rounds per block on (10 M regions
+    // alone: 78.2 us against 80.0, the 10 M root pass 65.7 against 67.4) and costs where a block runs ONE round (1 M regions alone:
+    // 14.5 us against 14.2, its root pass 14.8 against 14.2).  GFFX_HIP_WIN_FILTER: 1 = the coarse level always, 2 = the fine one
+    // wherever it fits.
+    const long fknob = b0->knobs.v[BK_WIN_FILTER];
+    const bool fine_pays = fknob == 2 || nq_launch >= 4ull * (threads == 1024 ? 256u : 512u) * 4u * threads;
+    const uint32_t fwords_fine = wide || fknob == 1 || !fine_pays ? 0u : ix->win_fwords_fine;
+    uint32_t fwords = fwords_fine ? fwords_fine : fwords_coarse, swords = ix->win_swords;
     // What does not fit the block's LDS goes in this order: the split bitmap (lists longer than 4 are then walked from
     // win_spill), the seqid records (read through the caches instead), the coverage filter.  What is left -- header, strips,
     // parked offsets, per-thread strips -- fits by construction; checked all the same: a launch over the limit would fail, or
@@ -152,7 +164,11 @@ static int run_windows_pass(gffx_hip_batch *const *bs, uint32_t n, hipStream_t s
     // a root pass keeps the block's root bitmap in LDS (else: device atomics on the batch's bitmap); it is small and comes before
     // the tables: only when nothing else is left to shed does it go
     uint32_t bm_words = roots ? ((ix->n_roots + 31) / 32 + 3) / 4 * 4 : 0;
-    auto need = [&]() { return pairs_lds_bytes(ix, threads, roots, keep_words, fwords, swords, ml, bm_words, wide); };
+    auto need = [&]() { return pairs_lds_bytes(ix->n_chr, threads, roots, keep_words, fwords, swords, ml, bm_words, wide); };
+    // the finest coverage filter that fits with everything else in place (and pays: above): the fine one spares more regions their
+    // line read (on a GRCh38-sized index 43 % against 37 %), but never at the price of a table
+    if (need() > max_lds) fwords = fwords_coarse;
+    const bool fine = fwords_fine && fwords == fwords_fine;
     if (need() > max_lds) swords = 0;
     if (need() > max_lds) ml = false;
     if (need() > max_lds) fwords = 0;
@@ -168,10 +184,23 @@ static int run_windows_pass(gffx_hip_batch *const *bs, uint32_t n, hipStream_t s
     // batches' passes are long finished but not yet synchronised with.  A ROOT pass takes one block per CU as soon as ONE other batch
     // is in flight: 9.3 us per pass against 10.1 with two batches in flight, 7.9 against 10.0 with three, 9.7 against 11.1 with four.
     // (Callers that hand their batches over together -- gffx_hip_batches_run_n -- get one launch for all of them instead: n > 1.)
+    // A launch that serves a FULL group of eight batches, one of two groups that alternate on two streams, leaves an eighth of the
+    // slots free: 448 blocks.  The other group's launch, queued on the other stream, starts its first blocks in them at once -- its
+    // dispatch, staging and first round run under this launch instead of behind its slowest block -- and a block runs 8.7 rounds
+    // instead of 7.6.  16 batches in flight (bench.py's headline), G regions/s at 448 / 512 blocks, by regions per batch: shuffled
+    // 500 k 147.5 / 145.6, 700 k 153.1 / 150.5, 1 M 159.1 / 155.0, 1.3 M 161.7 / 160.9, 2 M 165.1 / 163.7, 4 M 170.3 / 170.2; sorted by
+    // position, where the blocks' lives differ most, 500 k 174.8 / 161.5, 1 M 188.3 / 172.5, 2 M 210.4 / 198.1, 4 M 227.5 / 219.9
+    // (profiles/r07_group_grid.txt).  Only there: groups of six lose 4 % on sorted batches at 448, groups of two 4 %
+    // (2.2 rounds per block: a third round for some), three groups on two streams 1.5 %; serial launches of one group
+    // (gffx_hip_batches_timed_runs) have nobody to leave the slots to.  The two shapes of 256 blocks lost: 256 x 1024 threads
+    // (one block per CU, the tables staged once, the fine filter in LDS) 141.9 shuffled -- 144.2 with the fine filter -- against
+    // 155.0; 256 x 512 (two launches side by side) 158.4 shuffled but 166.3 against 172.5 sorted.
     uint64_t rounds[kPairMaxSubs], total_rounds = 0;
     for (uint32_t t = 0; t < n; ++t) total_rounds += rounds[t] = (bs[t]->nq + 4ull * threads - 1) / (4ull * threads);
     const long blocks_knob = b0->knobs.v[roots ? BK_BITMAP_BLOCKS : BK_FUSED_BLOCKS];
-    const uint32_t slots = threads == 1024 ? 256u : (n == 1 && others >= (roots ? 1 : 2) && total_rounds <= 1024) ? 256u : 512u;
+    constexpr uint32_t kSlotsEighthFree = 448;
+    const bool eighth_free = n == kPairMaxSubs && alternating && !roots && total_rounds >= 4ull * kSlotsEighthFree;
+    const uint32_t slots = threads == 1024 ? 256u : (n == 1 && others >= (roots ? 1 : 2) && total_rounds <= 1024) ? 256u : eighth_free ? kSlotsEighthFree : 512u;
     const uint32_t want_grid = (uint32_t)std::min<uint64_t>(total_rounds, (uint64_t)(blocks_knob ? blocks_knob : slots));
     // every batch's share of the blocks: in proportion to its rounds, at least one, at most a block per round
     uint32_t grid = 0;
@@ -222,7 +251,8 @@ static int run_windows_pass(gffx_hip_batch *const *bs, uint32_t n, hipStream_t s
         PairSub &S = a.sub[t];
         WaveOut &o = S.out;
         const uint32_t mine = S.n_blocks;
-        if (!roots) b->win_threads = threads, b->win_blocks = n == 1 ? mine : grid;
+        if (!roots) b->win_threads = threads, b->win_blocks = n == 1 ? mine : grid, b->win_share = mine;
+        b->win_filter_level = fwords == 0 ? 0u : fine ? 2u : 1u;
         if (roots && !second) {
             b->roots_blocks = mine;
             o.sums_valid = b->sums_valid;  // (the kept pairs of a run of GFFX_OUT_BITMAP_KEEP passes add up per block: gffx_hip_batch_kept_pairs_accumulated)
@@ -256,8 +286,8 @@ static int run_windows_pass(gffx_hip_batch *const *bs, uint32_t n, hipStream_t s
         }
     }
     a.pv.lines = pos ? ix->d_win_pos : ix->d_win;
-    a.pv.meta = ix->d_win_meta;
-    a.pv.filter = ix->d_win_filter;
+    a.pv.meta = fine ? ix->d_win_meta_fine : ix->d_win_meta;
+    a.pv.filter = fine ? ix->d_win_filter_fine : ix->d_win_filter;
     a.pv.splittab = ix->d_win_splittab;
     a.pv.wide = ix->d_win_wide;
     a.pv.all = ix->d_win_all;
@@ -267,7 +297,7 @@ static int run_windows_pass(gffx_hip_batch *const *bs, uint32_t n, hipStream_t s
     a.pv.n_roots = ix->n_roots;
     a.pv.n_win = ix->n_win;
     a.pv.n_chr = ix->n_chr;
-    a.pv.fshift = ix->win_fshift;
+    a.pv.fshift = fine ? ix->win_fshift_fine : ix->win_fshift;
     a.invert = b0->invert != 0;
     a.fwords = fwords;
     a.swords = swords;
@@ -307,7 +337,7 @@ int gffx::windows_pack_roots(gffx_hip_batch *b) {
 // One pass = the pair outputs (root_fids and / or triples; offsets) and, when asked for, the roots as a pass of its own over the
 // position copy of the line table (the CLI asks for the roots alone: one pass).  Overlap + invert keeps nothing
 // (intersect.rs:156-161: invert ^ true): no kernel runs at all.  For n batches at once (same mode, invert, flags, form) on `stream`.
-static int run_windows_on(gffx_hip_batch *const *bs, uint32_t n, hipStream_t stream) {
+static int run_windows_on(gffx_hip_batch *const *bs, uint32_t n, hipStream_t stream, bool alternating = false) {
     gffx_hip_batch *b0 = bs[0];
     const bool want_bitmap = b0->flags & GFFX_OUT_ROOT_BITMAP;
     const bool want_pairs = b0->flags & (GFFX_OUT_FIDS | GFFX_OUT_TRIPLES | GFFX_OUT_OFFSETS | GFFX_OUT_OFFSETS32 | GFFX_OUT_SEGBASE);
@@ -336,11 +366,11 @@ static int run_windows_on(gffx_hip_batch *const *bs, uint32_t n, hipStream_t str
     if (b0->mode == GFFX_MODE_OVERLAP && b0->invert) return GFFX_OK;
     int rc;
     if (want_pairs || !want_bitmap) {
-        if ((rc = run_windows_pass(bs, n, stream, (b0->flags & GFFX_OUT_TRIPLES) ? 2 : 1, false))) return rc;
-        if (want_bitmap && (rc = run_windows_pass(bs, n, stream, 3, true))) return rc;
+        if ((rc = run_windows_pass(bs, n, stream, (b0->flags & GFFX_OUT_TRIPLES) ? 2 : 1, false, alternating))) return rc;
+        if (want_bitmap && (rc = run_windows_pass(bs, n, stream, 3, true, alternating))) return rc;
         return GFFX_OK;
     }
-    return run_windows_pass(bs, n, stream, 3, false);
+    return run_windows_pass(bs, n, stream, 3, false, alternating);
 }
 
 int gffx::run_windows(gffx_hip_batch *b) { return run_windows_on(&b, 1, b->stream); }
@@ -354,13 +384,13 @@ bool gffx::windows_groupable(gffx_hip_batch *const *bs, uint32_t n) {
         if (b->strategy != GFFX_STRATEGY_WINDOWS || b->nq == 0 || b->ix != bs[0]->ix || b->mode != bs[0]->mode || b->invert != bs[0]->invert ||
             b->flags != bs[0]->flags || b->wide != bs[0]->wide || b->profiling)
             return false;
-        for (int k : {BK_WIN_THREADS, BK_FUSED_BLOCKS, BK_BITMAP_BLOCKS, BK_TICKETS})
+        for (int k : {BK_WIN_THREADS, BK_FUSED_BLOCKS, BK_BITMAP_BLOCKS, BK_TICKETS, BK_WIN_FILTER})
             if (b->knobs.v[k] != bs[0]->knobs.v[k]) return false;
     }
     return true;
 }
 
-int gffx::run_windows_group(gffx_hip_batch *const *bs, uint32_t n, int which_stream) {
+int gffx::run_windows_group(gffx_hip_batch *const *bs, uint32_t n, int which_stream, bool alternating) {
     const gffx_hip_index *ix = bs[0]->ix;
     GFFX_HIP_TRY(hipSetDevice(ix->device));
     hipStream_t gs;
@@ -375,5 +405,5 @@ int gffx::run_windows_group(gffx_hip_batch *const *bs, uint32_t n, int which_str
         const int rc = batch_join_stream(bs[t], gs);
         if (rc) return rc;
     }
-    return run_windows_on(bs, n, gs);
+    return run_windows_on(bs, n, gs, alternating);
 }

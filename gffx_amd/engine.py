@@ -202,6 +202,16 @@ class QueryBatch:
         return int(lib().gffx_hip_batch_block_count(self._h))
 
     @property
+    def block_share(self) -> int:
+        """the batch's own blocks of that launch (block_count is the whole grid of a launch that serves a group of batches)"""
+        return int(lib().gffx_hip_batch_block_share(self._h))
+
+    @property
+    def filter_level(self) -> int:
+        """coverage filter of the last windows-strategy launch: 0 none, 1 the coarse level, 2 the fine one"""
+        return int(lib().gffx_hip_batch_filter_level(self._h))
+
+    @property
     def wide_form(self) -> bool:
         """the last run's pair passes took the wide form of the window kernel (regions of any width, every mode)"""
         return bool(lib().gffx_hip_batch_wide_form(self._h))

@@ -67,11 +67,15 @@
  *   GFFX_HIP_TICKETS=0..4           how a launch's blocks get their rounds: 0 a fixed stride, 1 the launch's tail by ticket, 2 every round by
  *                                   ticket, 3 only the rounds beyond the last full stride, 4 (default) the engine's choice (1 for a launch that
  *                                   serves one batch with eight or more rounds per block, else 0)
+ *   GFFX_HIP_WIN_FILTER=0|1|2       coverage filter of the window kernels: the engine's choice (default: the fine level of the index where it
+ *                                   fits the launch's LDS and the blocks run four rounds or more, else the coarse one) / the coarse level
+ *                                   only / the fine level wherever it fits
  *   GFFX_HIP_AUTO_STRATEGY=n        what GFFX_STRATEGY_AUTO resolves to (0: the engine's choice)
  *   launch sizes (0 = the engine's choice): GFFX_HIP_FUSED_BLOCKS, GFFX_HIP_BITMAP_BLOCKS; GFFX_HIP_JOIN_BLOCKS, GFFX_HIP_MAX_BLOCKS;
  *   GFFX_HIP_PARTITION_BUDGET_MB (record buffers of the partitioned strategy)
  *   index build: GFFX_HIP_SLOT_WMAX (widest region a window line answers, 16384), GFFX_HIP_WIN_PER_ENTRY, GFFX_HIP_WIN_SPLIT,
- *   GFFX_HIP_WIN_FILTER_KB, GFFX_HIP_WIN_MAX_LINES, GFFX_HIP_BINS_PER_ENTRY
+ *   GFFX_HIP_WIN_FILTER_KB (coarse coverage filter, 24), GFFX_HIP_WIN_FILTER_FINE_KB (the fine one: at most this, and at most the LDS a
+ *   1024-thread pair pass has left; 0 = none), GFFX_HIP_WIN_MAX_LINES, GFFX_HIP_BINS_PER_ENTRY
  */
 #ifndef GFFX_HIP_H
 #define GFFX_HIP_H
@@ -335,6 +339,14 @@ uint32_t gffx_hip_batch_block_threads(const gffx_hip_batch *);
  * A root pass (GFFX_OUT_ROOT_BITMAP alone) takes one block per CU as soon as ONE other batch is in flight (measured likewise).
  * The knob GFFX_HIP_FUSED_BLOCKS forces a count (GFFX_HIP_BITMAP_BLOCKS: the root passes'). */
 uint32_t gffx_hip_batch_block_count(const gffx_hip_batch *);
+/* The batch's own blocks of that launch: the whole grid for a launch that serves one batch; for a launch that serves a group of
+ * batches (gffx_hip_batches_run_n) _block_count is the launch's grid and this the batch's share of it. */
+uint32_t gffx_hip_batch_block_share(const gffx_hip_batch *);
+/* Coverage filter the batch's last windows-strategy launch staged in LDS: 0 none (the mixed form, or nothing fitted), 1 the coarse
+ * one (GFFX_HIP_WIN_FILTER_KB), 2 the fine one (GFFX_HIP_WIN_FILTER_FINE_KB).  A launch takes the fine one where it fits beside its
+ * other tables and strips and its blocks run four rounds or more (about 4 M regions: the larger bitmap is staged once per block);
+ * GFFX_HIP_WIN_FILTER=1 holds a batch's launches to the coarse one, =2 takes the fine one wherever it fits. */
+uint32_t gffx_hip_batch_filter_level(const gffx_hip_batch *);
 /* 1 when the last run's passes took the MIXED form of the window kernels (every mode, inverted or not; round 4's "wide form" is
  * its all-wide Overlap case): every region is served its own way in one launch -- a region the index lines answer (up to 16 Ki bases by default) from ONE
  * line as in the narrow form, a wider one from two index lines and two rank words, no sweep.  AUTO chooses it for a batch with

@@ -5,7 +5,7 @@
 // a brute-force scan of the roots; then the WIDE form's reading (two lines and two rank words per region of any width; every mode,
 // inverted or not: what a wide lane keeps of the line of qs and of its run, the true ends where the lines' clamped ones do not tell)
 // against the same scan.  Runs without a GPU (tests/test_window_index_cpu.py); built by the Makefile of
-// gffx_amd/csrc into gffx_amd/bin/win_index_check.     usage: win_index_check [seed]
+// gffx_amd/csrc into gffx_amd/bin/win_index_check.     usage: win_index_check [seed] | win_index_check filter
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
@@ -20,7 +20,103 @@ static bool keep(int mode, uint32_t s, uint32_t e, uint32_t qs, uint32_t qe) {
     if (mode == 1) return s <= qs && e >= qe;
     return true;
 }
+// `win_index_check filter`: the two levels of the coverage filter (engine_index.hip) against a brute-force loop over the roots.
+// Three seqids: one without roots, one with a single root that ends on a cell boundary, one with several roots, an empty interval
+// (end == start) among them.  Per level: bit x of a seqid is set exactly when a root holds a base of cell x; the cell is never so
+// small that a region of width wmax spans more than 31 cells; a fine budget of 0 gives no fine level and the same coarse one; a
+// fine level that misses its room by a little folds its shortest seqids over the longest one's words: every bit brute force sets
+// is still set (a clear bit must mean "no hit"), and the bitmap fits the room.
+static int check_filter_levels() {
+    const uint32_t n_chr = 3;
+    std::vector<uint32_t> co = {0, 0, 1, 0}, start;
+    std::vector<uint4> aux;
+    auto add = [&](uint32_t s, uint32_t e) { start.push_back(s); aux.push_back(make_uint4(e, 0, 0, (uint32_t)start.size())); };
+    add(3u << 16, 5u << 16);  // seqid 1: ends on a cell boundary at every shift up to 16
+    std::mt19937_64 rng(7);
+    std::vector<std::pair<uint32_t, uint32_t>> g;
+    for (int i = 0; i < 400; i++) {
+        const uint32_t s = rng() % 200000000u;
+        g.push_back({s, s + (uint32_t)(rng() % 60000)});
+    }
+    g.push_back({123u << 13, 123u << 13});  // empty, on a cell boundary
+    g.push_back({77777777u, 77777777u});    // empty, inside a cell
+    g.push_back({199999000u, 200000000u});
+    std::sort(g.begin(), g.end());
+    for (auto &x : g) add(x.first, x.second);
+    co[3] = (uint32_t)start.size();
+    uint32_t pm = 0;
+    for (uint32_t i = co[2]; i < co[3]; i++) aux[i].y = pm, pm = std::max(pm, aux[i].x);
+    unsigned long long n_bits = 0;
+    // exact: 1 = every bit equals brute force, 0 = every bit brute force sets is set
+    auto check = [&](const char *what, const std::vector<uint32_t> &bits, const std::vector<uint2> &fmeta, uint32_t sh, uint32_t wmax, bool exact) {
+        if ((wmax >> sh) + 2 > 31) { printf("FILTER %s: cells of 2^%u bp, a region of %u bases spans more than 31\n", what, sh, wmax); return false; }
+        if (bits.size() & 3u) { printf("FILTER %s: %zu words, not a multiple of 4\n", what, bits.size()); return false; }
+        for (uint32_t c = 0; c < n_chr; c++) {
+            if (co[c + 1] == co[c]) continue;
+            uint64_t max_pos = 0;
+            for (uint32_t i = co[c]; i < co[c + 1]; i++) max_pos = std::max<uint64_t>(max_pos, std::max(start[i], aux[i].x));
+            const uint64_t nc = (max_pos >> sh) + 1;
+            if (fmeta[c].y != nc) { printf("FILTER %s: seqid %u has %u cells, expected %llu\n", what, c, fmeta[c].y, (unsigned long long)nc); return false; }
+            for (uint64_t x = 0; x < nc; x++) {
+                bool want = false;
+                for (uint32_t i = co[c]; i < co[c + 1] && !want; i++) {
+                    const uint64_t lo = (uint64_t)x << sh, hi = lo + (1ull << sh);  // cell x = [lo, hi)
+                    want = aux[i].x > start[i] ? (start[i] < hi && aux[i].x > lo) : (start[i] >= lo && start[i] < hi);
+                }
+                const uint64_t bit = fmeta[c].x + x;
+                if ((bit >> 5) + 1 >= bits.size()) { printf("FILTER %s: seqid %u cell %llu lies beyond the bitmap\n", what, c, (unsigned long long)x); return false; }
+                const bool got = bits[bit >> 5] >> (bit & 31) & 1u;
+                if (exact ? got != want : (want && !got)) {
+                    printf("FILTER %s MISMATCH: seqid %u cell %llu (2^%u bp) is %d, brute force says %d\n", what, c, (unsigned long long)x, sh, (int)got, (int)want);
+                    return false;
+                }
+                n_bits++;
+            }
+        }
+        return true;
+    };
+    for (uint32_t wmax : {16384u, 1u << 18}) {
+        std::vector<uint4> meta(n_chr + 1, make_uint4(0, 0, 0, 0));
+        meta[1].w = 1000, meta[2].w = wmax;
+        Knobs<IK__COUNT> K;
+        for (int i = 0; i < IK__COUNT; i++) K.v[i] = kIndexKnobs[i].dflt;
+        K.v[IK_WIN_FILTER_KB] = 1;  // 8192 bits for 200 Mbp: cells of 2^15 bp
+        std::vector<uint32_t> cb, fb;
+        std::vector<uint2> cm, fm;
+        uint32_t csh = 0, fsh = 0;
+        gffx::build_window_filter(n_chr, co.data(), start, aux, meta, cb, cm, csh, K);
+        if (cb.empty() || csh != 15 || !check("coarse", cb, cm, csh, wmax, true)) { printf("FILTER coarse: shift %u, %zu words\n", csh, cb.size()); return 1; }
+        // a fine budget of 0: no fine level (and the coarse one is what it was: built above without looking at the fine knob)
+        K.v[IK_WIN_FILTER_FINE_KB] = 0;
+        gffx::build_window_filter_fine(n_chr, co.data(), start, aux, meta, csh, 1u << 20, fb, fm, fsh, K);
+        if (!fb.empty()) { printf("FILTER fine: a budget of 0 built %zu words\n", fb.size()); return 1; }
+        // room for everything: the finest cell the 31-cell rule allows, exact
+        K.v[IK_WIN_FILTER_FINE_KB] = 120;
+        gffx::build_window_filter_fine(n_chr, co.data(), start, aux, meta, csh, 1u << 20, fb, fm, fsh, K);
+        const uint32_t min_sh = wmax == 16384u ? 10u : 14u;
+        if (fb.empty() || fsh != min_sh || fb.size() * 4 > (120u << 10) || !check("fine", fb, fm, fsh, wmax, true)) { printf("FILTER fine: shift %u, %zu words\n", fsh, fb.size()); return 1; }
+        // the budget decides: 4 KB hold cells of 2^13 bp (24 415 bits), not of 2^12 (the wider wmax allows 2^14 at the least)
+        K.v[IK_WIN_FILTER_FINE_KB] = 4;
+        gffx::build_window_filter_fine(n_chr, co.data(), start, aux, meta, csh, 1u << 20, fb, fm, fsh, K);
+        if (fsh != std::max(13u, min_sh) || fb.size() * 4 > 4096 || !check("fine 4 KB", fb, fm, fsh, wmax, true)) { printf("FILTER fine 4 KB: shift %u, %zu words\n", fsh, fb.size()); return 1; }
+        // ... and so does the room: 8 bytes short of the 2^13 bitmap, the single-root seqid is folded over the long one's words
+        if (wmax == 16384u) {
+            const uint32_t whole = (uint32_t)fb.size() * 4;
+            gffx::build_window_filter_fine(n_chr, co.data(), start, aux, meta, csh, whole - 8, fb, fm, fsh, K);
+            if (fsh != 13 || fb.size() * 4 > whole - 8 || fm[1].x != fm[2].x || !check("fine, folded", fb, fm, fsh, wmax, false)) {
+                printf("FILTER fine, folded: shift %u, %zu words for a room of %u bytes\n", fsh, fb.size(), whole - 8);
+                return 1;
+            }
+            // ... and a room far too small for the next smaller cell leaves the index with the coarse filter alone
+            gffx::build_window_filter_fine(n_chr, co.data(), start, aux, meta, csh, 1024, fb, fm, fsh, K);
+            if (!fb.empty()) { printf("FILTER fine: %zu words in a room of 1024 bytes\n", fb.size()); return 1; }
+        }
+    }
+    printf("ok filter (%llu cells checked)\n", n_bits);
+    return 0;
+}
 int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "filter")) return check_filter_levels();
     uint64_t seed = argc > 1 ? atoll(argv[1]) : 1;
     unsigned long long n_checked = 0, n_split_reads = 0, n_wide = 0, n_wide_reads = 0, n_wide_tails = 0, n_cont = 0;
     std::mt19937_64 rng(seed);
