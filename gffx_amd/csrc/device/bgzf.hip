@@ -27,19 +27,9 @@
 #include <string>
 #include <vector>
 
-#include "bgzf_core.hpp"
-#include "gffx_device.hpp"
+#include "bgzf_device.hpp"
 
 namespace gffx {
-
-using u64 = unsigned long long;
-
-struct BgzfDir {  // one member of a chunk
-    u64 src;      // offset of the member in the chunk's compressed bytes
-    u64 dst;      // offset of its output in D
-    uint32_t len;    // the member's length (BSIZE + 1)
-    uint32_t isize;  // its output length (the footer's ISIZE)
-};
 
 struct ChunkResult {  // what the host reads back after a chunk (pinned)
     u64 tail;                // D[tail, N) is the unfinished record (the next chunk's carry)
@@ -61,7 +51,7 @@ struct __align__(16) InflateLds {
 };
 
 __global__ __launch_bounds__(64) void k_bgzf_inflate(const uint8_t *in, const BgzfDir *dir, uint32_t n_blocks, uint8_t *out,
-                                                     int32_t *status, ChunkResult *res) {
+                                                     int32_t *status, uint32_t *bad_block) {
     __shared__ InflateLds L;
     const uint32_t b = blockIdx.x, lane = threadIdx.x;
     if (b >= n_blocks) return;
@@ -95,7 +85,7 @@ __global__ __launch_bounds__(64) void k_bgzf_inflate(const uint8_t *in, const Bg
             if (crc != bgzf::le32(in + d.src + d.len - 8)) st = bgzf::kCrc;
         }
         status[b] = st;
-        if (st != bgzf::kOk) atomicMin(&res->bad_block, b);
+        if (st != bgzf::kOk) atomicMin(bad_block, b);
     }
 }
 
@@ -206,27 +196,8 @@ __global__ __launch_bounds__(64) void k_bam_rows(const uint8_t *D, const u64 *re
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------
-template <class T>
-struct DevArr {
-    T *p = nullptr;
-    size_t cap = 0;
-    ~DevArr() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t ensure(size_t n) {
-        if (n <= cap) return hipSuccess;
-        const size_t c = std::max(n, cap + cap / 2);  // (grow by 1.5x at least)
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const hipError_t e = hipMalloc(&p, c * sizeof(T));
-        if (e == hipSuccess) cap = c;
-        return e;
-    }
-};
-
 // walks the members of buf[0, n): their lengths and ISIZEs.  base: buf's offset in the file (for the message).
-static int walk_members(const uint8_t *buf, uint64_t n, uint64_t base, std::vector<BgzfDir> *dir) {
+int walk_members(const uint8_t *buf, uint64_t n, uint64_t base, std::vector<BgzfDir> *dir) {
     uint64_t at = 0, dst = 0;
     while (at < n) {
         uint32_t total = 0, hdr = 0;
@@ -243,7 +214,7 @@ static int walk_members(const uint8_t *buf, uint64_t n, uint64_t base, std::vect
     return GFFX_OK;
 }
 
-static int check_device(int device) {
+int check_device(int device) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess) {
         (void)hipGetLastError();
@@ -252,6 +223,15 @@ static int check_device(int device) {
     if (ndev <= 0) return fail(GFFX_E_NO_DEVICE, "no HIP device visible (the engine has no CPU fallback)");
     if (device < 0 || device >= ndev) return fail(GFFX_E_NO_DEVICE, "device %d out of range (%d visible)", device, ndev);
     return GFFX_OK;
+}
+
+void launch_bgzf_inflate(hipStream_t s, const uint8_t *in, const BgzfDir *dir, uint32_t nb, uint8_t *out, int32_t *status,
+                         uint32_t *bad_block) {
+    if (nb) hipLaunchKernelGGL(k_bgzf_inflate, dim3(nb), dim3(64), 0, s, in, dir, nb, out, status, bad_block);
+}
+
+void launch_scan(hipStream_t s, const uint32_t *in, uint32_t n, u64 *out, u64 *total) {
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, in, n, out, total);
 }
 
 }  // namespace gffx
@@ -315,8 +295,6 @@ struct gffx_hip_bam {
 };
 
 namespace {
-constexpr uint32_t kMaxBlocksPerBatch = 1u << 16;
-
 int sticky(gffx_hip_bam *h, int rc) {
     if (rc != GFFX_OK && h->error == GFFX_OK) {
         h->error = rc;
@@ -423,7 +401,7 @@ int enqueue(gffx_hip_bam *h, int k, uint32_t nb, uint64_t file_off) {
     GFFX_HIP_TRY(hipMemcpyAsync(h->seg.p, seg.data(), (n_seg + 1) * sizeof(u64), hipMemcpyHostToDevice, s));
     GFFX_HIP_TRY(hipStreamWaitEvent(s, h->copied[k], 0));
     GFFX_HIP_TRY(hipEventRecord(h->ev[0], s));
-    if (nb) hipLaunchKernelGGL(k_bgzf_inflate, dim3(nb), dim3(64), 0, s, h->in[k].p, h->dir[k].p, nb, D + C, h->status.p, res);
+    if (nb) hipLaunchKernelGGL(k_bgzf_inflate, dim3(nb), dim3(64), 0, s, h->in[k].p, h->dir[k].p, nb, D + C, h->status.p, &res->bad_block);
     GFFX_HIP_TRY(hipGetLastError());
     GFFX_HIP_TRY(hipEventRecord(h->ev[1], s));
     hipLaunchKernelGGL(k_frame_guess, dim3((n_seg + 255) / 256), dim3(256), 0, s, D, N, h->seg.p, n_seg, h->guess_end.p, h->guess_n.p, res);
@@ -592,7 +570,7 @@ extern "C" int gffx_hip_bgzf_inflate(int device, const uint8_t *bgzf, uint64_t n
     GFFX_HIP_TRY(hipMemcpy(res.p, &init, sizeof init, hipMemcpyHostToDevice));
     GFFX_HIP_TRY(hipMemcpy(in.p, bgzf, n_bytes, hipMemcpyHostToDevice));
     GFFX_HIP_TRY(hipMemcpy(dd.p, dir.data(), dir.size() * sizeof(BgzfDir), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_bgzf_inflate, dim3((uint32_t)dir.size()), dim3(64), 0, 0, in.p, dd.p, (uint32_t)dir.size(), o.p, st.p, res.p);
+    hipLaunchKernelGGL(k_bgzf_inflate, dim3((uint32_t)dir.size()), dim3(64), 0, 0, in.p, dd.p, (uint32_t)dir.size(), o.p, st.p, &res.p->bad_block);
     GFFX_HIP_TRY(hipGetLastError());
     GFFX_HIP_TRY(hipDeviceSynchronize());
     GFFX_HIP_TRY(hipMemcpy(&init, res.p, sizeof init, hipMemcpyDeviceToHost));

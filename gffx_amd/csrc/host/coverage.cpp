@@ -76,7 +76,6 @@ void run(const CoverageArgs &args) {
     DeviceWarmup warm(args.device);  // (the runtime comes up beside the loaders and the BED parser)
     TreeIndexData index_data = TreeIndexData::load_tree_index(args.input);  // :511
     const depth::SourceKind kind = depth::source_kind(args.source);  // coverage.rs:520-541
-    const bool bam = kind == depth::SourceKind::Bam;
     const size_t threads = capped_threads(args.threads);
     // the kept rows as flat (seqid number, start, end) words, one vector per parsed piece (file order); part_row[p] = rows before piece p
     const std::vector<std::vector<uint32_t>> part =
@@ -84,8 +83,8 @@ void run(const CoverageArgs &args) {
     std::vector<size_t> part_row(part.size() + 1, 0);
     for (size_t p = 0; p < part.size(); ++p) part_row[p + 1] = part_row[p] + part[p].size() / 3;
     const size_t n_regions = part_row.back();
-    if (verbose) std::fprintf(stderr, "[INFO] %zu %s rows kept\n", n_regions, bam ? "BAM" : "BED");
-    timer.lap(bam ? "Loading index + reading BAM" : "Loading index + parsing BED");
+    if (verbose) std::fprintf(stderr, "[INFO] %zu %s rows kept\n", n_regions, depth::source_label(kind));
+    timer.lap(depth::source_lap(kind, true));
 
     std::string out = "id\tchr\tstart\tend\tbreadth\tfraction\n";  // :463
     size_t written = 0;

@@ -5,7 +5,7 @@
 //   write_depth_results    depth.rs:515-546   "id\tchr\tstart\tend\tdepth" rows
 // The reference re-parses a root's byte block for every batch that touches it; here every block is
 // parsed ONCE into the device line table (include/gffx_hip.h "gffx depth"), the regions stream through
-// Join A in batches, and k_depth_regions accumulates per (block, ID) group.  (SAM/CRAM sources need htslib: refused.)
+// Join A in batches, and k_depth_regions accumulates per (block, ID) group.  (SAM sources: sam.cpp; CRAM needs htslib: refused.)
 #include <algorithm>
 #include <cctype>
 #include <cstdio>
@@ -164,20 +164,20 @@ SourceKind source_kind(const std::string &path) {
     std::string ext;
     if (dot != std::string::npos && dot > 0) ext = base.substr(dot + 1);
     for (char &c : ext) c = static_cast<char>(std::tolower(static_cast<unsigned char>(c)));
-    if (ext == "sam" || ext == "cram")
+    if (ext == "cram")
         throw Error("SAM/CRAM sources need htslib, which this build does not carry; use a .bam or .bed source");
-    if (ext != "bed" && ext != "bam")
+    if (ext != "bed" && ext != "bam" && ext != "sam")
         throw Error("Unsupported file type: \"" + path + "\". Expected .bam/.sam/.cram or .bed");  // depth.rs:597-600, coverage.rs:535-540
-    return ext == "bam" ? SourceKind::Bam : SourceKind::Bed;
+    return ext == "bam" ? SourceKind::Bam : ext == "sam" ? SourceKind::Sam : SourceKind::Bed;
 }
 
 std::vector<std::vector<uint32_t>> read_source_rows(SourceKind kind, const std::string &path,
                                                     const std::unordered_map<std::string, uint32_t> &seqid_to_num, size_t threads,
                                                     int device, bool verbose, DeviceWarmup &warm) {
     if (kind == SourceKind::Bed) return parse_bed_rows_flat(path, seqid_to_num, threads);  // depth.rs:450-495, coverage.rs:230-256
-    warm.wait();  // depth.rs:297-372, coverage.rs:125-168: the same (chr, start, end) rows, from BAM records
+    warm.wait();  // depth.rs:297-372, coverage.rs:125-168: the same (chr, start, end) rows, from BAM records or SAM lines
     std::vector<std::vector<uint32_t>> part;
-    part.push_back(bam::read_rows(path, seqid_to_num, device, verbose));
+    part.push_back(kind == SourceKind::Sam ? sam::read_rows(path, seqid_to_num, device, verbose) : bam::read_rows(path, seqid_to_num, device, verbose));
     return part;
 }
 
@@ -189,7 +189,6 @@ void run(const DepthArgs &args) {
     const MappedFile gff = map_file_or(args.input, "Cannot open GFF file: \"" + args.input + "\"");  // :564-565
     TreeIndexData index_data = TreeIndexData::load_tree_index(args.input);  // :573
     const SourceKind kind = source_kind(args.source);  // depth.rs:590-601
-    const bool bam = kind == SourceKind::Bam;
     timer.lap("Loading index");
     const size_t threads = capped_threads(args.threads);
     // the kept rows as flat triples, one vector per parsed piece (file order); part_row[p] = rows before piece p
@@ -198,8 +197,8 @@ void run(const DepthArgs &args) {
     std::vector<size_t> part_row(part.size() + 1, 0);
     for (size_t p = 0; p < part.size(); ++p) part_row[p + 1] = part_row[p] + part[p].size() / 3;
     const size_t n_rows = part_row.back();
-    if (verbose) std::fprintf(stderr, "[INFO] %zu %s rows kept\n", n_rows, bam ? "BAM" : "BED");
-    timer.lap(bam ? "Reading BAM" : "Parsing BED");
+    if (verbose) std::fprintf(stderr, "[INFO] %zu %s rows kept\n", n_rows, source_label(kind));
+    timer.lap(source_lap(kind, false));
 
     const BlockTable t = load_or_build_block_table(args.input, gof, gff.view(), threads, verbose);
     timer.lap("Line table (image or parse)");

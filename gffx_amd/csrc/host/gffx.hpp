@@ -10,6 +10,7 @@
 //   gffx::commands::depth::{DepthArgs, parse_bed_rows, run}                      commands/depth.rs (BED source)
 //   gffx::commands::coverage::{CoverageArgs, run}                                commands/coverage.rs (BED source)
 //   gffx::bam::read_rows                                                         depth.rs:297-372 / coverage.rs:125-168 (BAM source)
+//   gffx::sam::read_rows                                                         depth.rs:588-591 / coverage.rs:520-541 (SAM source)
 // Compute (Join A, Join B) goes through include/gffx_hip.h only; there is no CPU join here.
 #pragma once
 #include <algorithm>
@@ -312,7 +313,7 @@ namespace depth {
 
 struct DepthArgs {  // depth.rs:34-72
     std::string input;                  // -i/--input
-    std::string source;                 // -s/--source (BED or BAM; SAM/CRAM need htslib: refused)
+    std::string source;                 // -s/--source (BED, BAM or SAM; CRAM is not supported)
     std::optional<std::string> output;  // -o/--output
     uint32_t bin_shift = 12;            // --bin-shift (only bounds the reference's candidate lists; accepted, unused)
     size_t threads = 12;                // -t/--threads
@@ -327,9 +328,18 @@ std::vector<intersect::Region> parse_bed_rows(const std::string &bed_path,
 // ... as flat (seqid number, start, end) words, one vector per parsed piece of the file, in file order
 std::vector<std::vector<uint32_t>> parse_bed_rows_flat(const std::string &bed_path, const std::unordered_map<std::string, uint32_t> &seqid_to_num,
                                                        size_t threads = 1);
-enum class SourceKind { Bed, Bam };
+enum class SourceKind { Bed, Bam, Sam };
+inline const char *source_label(SourceKind k) { return k == SourceKind::Bed ? "BED" : k == SourceKind::Bam ? "BAM" : "SAM"; }
+// the stage timer's name for reading the source: a BED file is parsed on the host, BAM and SAM are read on the device
+inline const char *source_lap(SourceKind k, bool with_index) {
+    switch (k) {
+        case SourceKind::Bam: return with_index ? "Loading index + reading BAM" : "Reading BAM";
+        case SourceKind::Sam: return with_index ? "Loading index + reading SAM" : "Reading SAM";
+        default: return with_index ? "Loading index + parsing BED" : "Parsing BED";
+    }
+}
 SourceKind source_kind(const std::string &path);  // depth.rs:590-601 / coverage.rs:520-541: by the extension, any letter case; others: Error
-// the kept rows of a .bed (on `threads` host threads) or .bam (inflated on `device` once `warm` is through), flat, in pieces, in file order
+// the kept rows of a .bed (on `threads` host threads), a .bam or a .sam (read on `device` once `warm` is through), flat, in pieces, in file order
 std::vector<std::vector<uint32_t>> read_source_rows(SourceKind kind, const std::string &path,
                                                     const std::unordered_map<std::string, uint32_t> &seqid_to_num, size_t threads,
                                                     int device, bool verbose, DeviceWarmup &warm);
@@ -361,12 +371,12 @@ namespace coverage {
 
 struct CoverageArgs {  // coverage.rs:37-57
     std::string input;                  // -i/--input
-    std::string source;                 // -s/--source (BED or BAM; SAM/CRAM need htslib: refused)
+    std::string source;                 // -s/--source (BED, BAM or SAM; CRAM is not supported)
     std::optional<std::string> output;  // -o/--output
     size_t threads = 12;                // -t/--threads
     bool verbose = false;               // -v/--verbose
     int device = 0;                     // --device (addition)
-    int gpus = 1;                       // --gpus (addition: the BED or BAM rows in batches over N MI355X, bitmaps and unions merged)
+    int gpus = 1;                       // --gpus (addition: the BED, BAM or SAM rows in batches over N MI355X, bitmaps and unions merged)
 };
 
 // GFFX_COVERAGE_BATCH_ROWS sets the rows per device batch (default 4 Mi rows; a positive decimal number, anything else is
@@ -383,6 +393,16 @@ namespace bam {
 std::vector<uint32_t> read_rows(const std::string &path, const std::unordered_map<std::string, uint32_t> &seqid_to_num, int device,
                                 bool verbose);
 }  // namespace bam
+
+// ---- SAM sources of depth / coverage (sam.cpp; commands/depth.rs:588-591, coverage.rs:520-541) --------------------------
+namespace sam {
+// the kept (seqid number, start, end) rows of a SAM file, flat, in file order (lines, fields and CIGARs read on `device`;
+// no htslib).  Sniffed by content: plain text, BGZF-compressed text, or BAM (handed to bam::read_rows).
+// GFFX_SAM_CHUNK_BYTES sets the fed bytes per device pass (default 64 MiB).  Throws Error on a bad file; every message
+// ends in "(read without htslib)".
+std::vector<uint32_t> read_rows(const std::string &path, const std::unordered_map<std::string, uint32_t> &seqid_to_num, int device,
+                                bool verbose);
+}  // namespace sam
 
 // main.rs: `gffx <index|intersect|depth|coverage> ...`; returns the process exit code
 int cli_main(int argc, char **argv);

@@ -90,8 +90,8 @@ const char *kTopUsage =
     "Usage: gffx <COMMAND>\n\nCommands:\n"
     "  index      Build index for GFF file\n"
     "  intersect  Extract models by a region or regions from a BED file (MI355X engine)\n"
-    "  depth      Compute coverage depth across genomic features from a BED or BAM file (MI355X engine)\n"
-    "  coverage   Compute coverage breadth across genomic features from a BED or BAM file (MI355X engine)\n"
+    "  depth      Compute coverage depth across genomic features from a BED, BAM or SAM file (MI355X engine)\n"
+    "  coverage   Compute coverage breadth across genomic features from a BED, BAM or SAM file (MI355X engine)\n"
     "  help       Print this message\n";
 
 const char *kIntersectUsage =
@@ -115,23 +115,23 @@ const char *kIntersectUsage =
 const char *kDepthUsage =
     "Usage: gffx depth [OPTIONS] --input <FILE> --source <SOURCE>\n\nOptions:\n"
     "  -i, --input <FILE>           Input GFF file path\n"
-    "  -s, --source <SOURCE>        Input source (BED or BAM; SAM/CRAM are not supported by this build)\n"
+    "  -s, --source <SOURCE>        Input source (BED, BAM or SAM; CRAM is not supported)\n"
     "  -o, --output <FILE>          Output file (stdout if not provided)\n"
     "      --bin-shift <BIN_SHIFT>  Bin width parameter (2^k bp) [default: 12]\n"
     "  -t, --threads <THREADS>      Number of threads for parallel processing [default: 12]\n"
     "  -v, --verbose                Enable verbose output\n"
     "      --device <N>             HIP device to run on [default: 0]\n"
-    "      --gpus <N>               Spread the BED or BAM rows over N devices [default: 1]\n";
+    "      --gpus <N>               Spread the BED, BAM or SAM rows over N devices [default: 1]\n";
 
 const char *kCoverageUsage =
     "Usage: gffx coverage [OPTIONS] --input <FILE> --source <SOURCE>\n\nOptions:\n"
     "  -i, --input <FILE>       Input GFF file path\n"
-    "  -s, --source <SOURCE>    Input source (BED or BAM; SAM/CRAM are not supported by this build)\n"
+    "  -s, --source <SOURCE>    Input source (BED, BAM or SAM; CRAM is not supported)\n"
     "  -o, --output <FILE>      Output file (stdout if not provided)\n"
     "  -t, --threads <NUM>      Number of threads for parallel processing [default: 12]\n"
     "  -v, --verbose            Enable verbose output\n"
     "      --device <N>         HIP device to run on [default: 0]\n"
-    "      --gpus <N>           Spread the BED or BAM rows over N devices [default: 1]\n"
+    "      --gpus <N>           Spread the BED, BAM or SAM rows over N devices [default: 1]\n"
     "      --stats-json <FILE>  Write the run's stage timers and counts as one JSON object\n";
 
 const char *kIndexUsage =

@@ -660,3 +660,78 @@ def bam_rows(data: bytes, ref_seq, header_bytes: int, chunk_bytes: int = 0, feed
         return r.rows()
     finally:
         r.close()
+
+
+# ---- SAM sources (include/gffx_hip.h "SAM sources"; device/sam.hip) ----------------------------------------------------
+class SamReader:
+    """gffx_hip_sam_*: the kept (seqid, start, end) rows of a SAM stream, plain text or BGZF-compressed (bgzf=True).
+    names = the SN values of the header's @SQ lines in order, ref_seq[tid] = seqid number or 0xFFFFFFFF;
+    header_bytes = the offset of the first line that does not begin with '@' in the (inflated) text."""
+
+    def __init__(self, names, ref_seq, header_bytes: int, chunk_bytes: int = 0, bgzf: bool = False, device: int = 0):
+        nb = [n if isinstance(n, bytes) else str(n).encode() for n in names]
+        rs = _u32(ref_seq)
+        if len(nb) != len(rs):
+            raise ValueError("names and ref_seq differ in length")
+        off = np.zeros(len(nb) + 1, np.uint64)
+        off[1:] = np.cumsum([len(n) for n in nb], dtype=np.uint64) if nb else 0
+        self._h = C.c_void_p()
+        check(lib().gffx_hip_sam_create(device, len(nb), b"".join(nb), off.ctypes.data_as(_ffi.u64p), _p(rs) if len(rs) else None,
+                                        header_bytes, chunk_bytes, int(bool(bgzf)), C.byref(self._h)))
+
+    def feed(self, data: bytes) -> None:
+        buf, ptr = _u8(data)
+        check(lib().gffx_hip_sam_feed(self._h, ptr, len(data)))
+
+    def finish(self) -> None:
+        check(lib().gffx_hip_sam_finish(self._h))
+
+    def rows(self) -> np.ndarray:
+        n = lib().gffx_hip_sam_rows(self._h)
+        out = np.zeros((max(n, 1), 3), np.uint32)
+        check(lib().gffx_hip_sam_copy_rows(self._h, _p(out)))
+        return out[:n]
+
+    def counts(self) -> Dict[str, int]:
+        v = [C.c_uint64() for _ in range(4)]
+        check(lib().gffx_hip_sam_counts(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("lines", "unmapped", "no_seq", "kept"), (x.value for x in v)))
+
+    def stage_ms(self) -> Dict[str, float]:
+        v = [C.c_double() for _ in range(3)]
+        check(lib().gffx_hip_sam_stage_ms(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("inflate", "lines", "rows"), (x.value for x in v)))
+
+    def close(self) -> None:
+        if self._h:
+            lib().gffx_hip_sam_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def sam_rows(data: bytes, names, ref_seq, header_bytes: int, chunk_bytes: int = 0, bgzf: bool = False, feed_bytes: int = 0,
+             feed_members: int = 0, device: int = 0, counts: Optional[dict] = None) -> np.ndarray:
+    """The rows of a whole SAM stream in file order.  feed_bytes > 0: plain text fed in pieces of that many bytes;
+    feed_members > 0: BGZF fed that many members per call.  counts: filled with SamReader.counts()."""
+    r = SamReader(names, ref_seq, header_bytes, chunk_bytes, bgzf, device)
+    try:
+        if bgzf and feed_members > 0:
+            off = bgzf_members(data)
+            for i in range(0, len(off) - 1, feed_members):
+                r.feed(data[off[i]:off[min(i + feed_members, len(off) - 1)]])
+        elif not bgzf and feed_bytes > 0:
+            for i in range(0, len(data), feed_bytes):
+                r.feed(data[i:i + feed_bytes])
+        else:
+            r.feed(data)
+        r.finish()
+        if counts is not None:
+            counts.update(r.counts())
+        return r.rows()
+    finally:
+        r.close()

@@ -437,3 +437,83 @@ def bam_long_read_records(n: int, seed: int, refs: Sequence[Tuple[str, int]], gr
         tid, pos = max(tid, 0), max(pos, 0)
         out += [bam_sized_record(size, tid, pos + k, b"long%d.%d" % (g, k), seed * 1000 + g * 10 + k) for k in range(count)]
     return out + base[len(groups) * step:]
+
+
+# ---- SAM text (SAM spec §1.3, §1.4): test and benchmark inputs of the SAM source path -----------------------------------
+def sam_header(refs: Sequence[Tuple[str, int]], text: bytes = b"") -> bytes:
+    """@HD, one @SQ line per reference in order, then `text` (further complete header lines, e.g. @CO)."""
+    return b"@HD\tVN:1.6\tSO:coordinate\n" + b"".join(b"@SQ\tSN:%s\tLN:%d\n" % (n.encode(), ln) for n, ln in refs) + text
+
+
+def sam_cigar(cigar) -> bytes:
+    """(op, length) pairs as text; no pairs: `*`.  bytes pass through (a test's malformed CIGAR)."""
+    if isinstance(cigar, bytes):
+        return cigar
+    return b"".join(b"%d%s" % (ln, CIGAR_OPS[op].encode()) for op, ln in cigar) or b"*"
+
+
+def sam_line(rname, pos: int, flag: int = 0, cigar=((0, 150),), name: bytes = b"r", l_seq: int = 0, tags: bytes = b"",
+             mapq: int = 60) -> bytes:
+    """One alignment line without its newline.  rname: a name or None (`*`); pos: 0-based as in BAM (POS = pos + 1, so -1 gives
+    POS 0); tags: text, TAB-separated."""
+    rn = b"*" if rname is None else (rname if isinstance(rname, bytes) else rname.encode())
+    seq = b"A" * l_seq if l_seq else b"*"
+    fields = [name, b"%d" % flag, rn, b"%d" % (pos + 1), b"%d" % mapq, sam_cigar(cigar), b"*", b"0", b"0", seq, b"*"]
+    if tags:
+        fields.append(tags)
+    return b"\t".join(fields)
+
+
+def sam_records_from(recs: Sequence[tuple], refs: Sequence[Tuple[str, int]]) -> List[bytes]:
+    """The records of bam_test_records / bam_long_read_records as SAM lines: tid -1 becomes `*`, pos -1 POS 0, an empty CIGAR
+    `*`; the binary tags become one Z tag of their size, so a record of 1 MB is a line of about 1 MB."""
+    import struct
+    out = []
+    for rec, tid, pos, flag, cigar in recs:
+        l_name, n_cig = rec[12], struct.unpack_from("<H", rec, 16)[0]
+        l_seq = struct.unpack_from("<i", rec, 20)[0]
+        name = rec[36:36 + l_name - 1]
+        n_tags = len(rec) - (36 + l_name + 4 * n_cig + (l_seq + 1) // 2 + l_seq)
+        tags = b"XX:Z:" + b"A" * (n_tags - 5) if n_tags > 5 else (b"NM:i:2" if n_tags else b"")
+        out.append(sam_line(None if tid < 0 else refs[tid][0], pos, flag, cigar, name, l_seq, tags))
+    return out
+
+
+def write_sam(path: str, header: bytes, lines: Sequence[bytes], bgzf: bool = False, layout: str = "aligned", newline: bytes = b"\n",
+              final_newline: bool = True, flush_header: bool = True, block: int = BGZF_BLOCK, eof: bool = True) -> int:
+    """Writes a SAM file, plain or BGZF-compressed (the text cut into members by bgzf_blocks: aligned = a member ends before
+    a line that would not fit, spanning = cut every `block` bytes); returns the header's size in the text."""
+    if newline != b"\n":
+        header = header.replace(b"\n", newline)
+    recs = [ln + newline for ln in lines]
+    if recs and not final_newline:
+        recs[-1] = recs[-1][:-len(newline)]
+    with open(path, "wb") as f:
+        if not bgzf:
+            f.write(header + b"".join(recs))
+        else:
+            for b in bgzf_blocks(header, recs, layout, flush_header, block):
+                f.write(bgzf_member(b))
+            if eof:
+                f.write(BGZF_EOF)
+    return len(header)
+
+
+def sam_counts_definition(recs: Sequence[tuple], ref_seq: Sequence[int]) -> Dict[str, int]:
+    """The tallies of the SAM reader on the lines of sam_records_from(recs): unmapped = flag 0x4 or, ASSUMED htslib behaviour,
+    a `*` CIGAR; no_seq = mapped, RNAME `*` or not in the index."""
+    c = {"lines": len(recs), "unmapped": 0, "no_seq": 0, "kept": 0}
+    for _, tid, pos, flag, cigar in recs:
+        if flag & 0x4 or not cigar:
+            c["unmapped"] += 1
+        elif tid < 0 or ref_seq[tid] == 0xFFFFFFFF:
+            c["no_seq"] += 1
+        elif pos >= 0 and bam_end(pos, cigar) > pos:
+            c["kept"] += 1
+    return c
+
+
+def sam_rows_definition(recs: Sequence[tuple], ref_seq: Sequence[int]) -> np.ndarray:
+    """bam_rows_definition plus the rule of the SAM parser: a record whose CIGAR is `*` (no operations) is dropped -- ASSUMED
+    htslib behaviour ("mapped query must have a CIGAR; treated as unmapped"), see device/sam_core.hpp."""
+    return bam_rows_definition([r for r in recs if r[4]], ref_seq)

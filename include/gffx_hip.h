@@ -21,6 +21,8 @@
  *     (commands/coverage.rs:92-124, :339-364)
  *   bam::Reader records -> (chr, start, end) rows        gffx_hip_bgzf_inflate, gffx_hip_bam_* (BAM sources)
  *     (commands/depth.rs:297-372, coverage.rs:125-168)
+ *   the same reader on a .sam file                       gffx_hip_sam_* (SAM sources, plain or BGZF-compressed)
+ *     (commands/depth.rs:588-591, coverage.rs:520-541)
  *
  * Semantics (bit-exact with the reference):
  *   a root interval iv of the query's seqid is a HIT iff  iv.start < q.end && iv.end > q.start
@@ -174,6 +176,7 @@ typedef struct gffx_hip_lines gffx_hip_lines;
 typedef struct gffx_hip_regions gffx_hip_regions;
 typedef struct gffx_hip_depth gffx_hip_depth;
 typedef struct gffx_hip_bam gffx_hip_bam;
+typedef struct gffx_hip_sam gffx_hip_sam;
 typedef struct gffx_hip_union gffx_hip_union;
 
 int gffx_hip_abi_version(void);
@@ -488,6 +491,42 @@ int gffx_hip_bam_counts(const gffx_hip_bam *, uint64_t *records, uint64_t *unmap
 int gffx_hip_bam_stage_ms(const gffx_hip_bam *, double *inflate_ms, double *frame_ms, double *rows_ms);
 int gffx_hip_bam_copy_rows(gffx_hip_bam *, uint32_t *rows /* 3 per row */);
 void gffx_hip_bam_destroy(gffx_hip_bam *);
+
+/* ---- SAM sources of `gffx depth` / `gffx coverage` (commands/depth.rs:588-591, commands/coverage.rs:520-541: the ----
+ * reference reads .sam through the reader it uses for .bam).  The text is cut into lines, the lines into fields, and
+ * FLAG, RNAME, POS and CIGAR are read on the device (device/sam.hip; the rules of one line, device/sam_core.hpp, are
+ * shared with the host).  The text is plain, or BGZF-compressed (bgzf != 0): then its members are inflated on the
+ * device as for BAM and the inflated bytes never leave it.
+ *
+ * _create takes the references of the header's @SQ lines in order (the order defines the tid): reference i's name is
+ * names[name_off[i], name_off[i + 1]) (no terminator), ref_seq[i] = the index's seqid number of it, or UINT32_MAX when
+ * the index has no such seqid (as for gffx_hip_bam_create); a name that occurs twice fails the call, as htslib's header
+ * parser does.  header_bytes = the offset, in the (inflated) text, of the first line that does not begin with '@'; the
+ * caller finds it and the names.  chunk_bytes bounds the fed bytes per device pass (0: 64 MiB).
+ * _feed takes the stream in file order from byte 0: text in pieces of any size, cut anywhere; BGZF in whole members.
+ * _finish reads a last line that does not end in '\n'.
+ * Rows are (seqid, start, end), 3 x u32 each, in file order.  A line needs 11 TAB-separated fields; of them FLAG (decimal,
+ * <= 65535, no leading zero, no 0x), RNAME, POS (1 to 18 decimal digits) and CIGAR (`*`, or <length><op> with op in
+ * MIDNSHP=XB and length < 2^28) are read, anything else in them fails the call with a message "line <n>: <reason>",
+ * n counted from 1 over the whole file, header lines included, and always the first such line of the file.  DEVIATION:
+ * fields 5 and 7 to 11 and the tags are not validated (htslib rejects e.g. a SEQ whose length differs from the CIGAR's).
+ * A line is kept unless flag & 0x4, CIGAR is `*`, RNAME is `*` or names no reference, ref_seq of it is UINT32_MAX, or
+ * POS is 0; start = POS - 1, end = start + the summed lengths of M/D/N/=/X (a sum of 0 counts as 1), both clamped to
+ * UINT32_MAX.  ASSUMPTION (htslib's sam.c sam_parse1 restated from memory): (1) a line without flag 0x4 whose CIGAR is
+ * `*` is treated as unmapped ("mapped query must have a CIGAR"); (2) a CIGAR length of 2^28 or more is an error; (3) an
+ * RNAME without @SQ line gets a warning and tid -1, so the line is dropped.
+ * _counts: lines read (header lines not counted), unmapped ones (flag 0x4 or `*` CIGAR), mapped ones without a seqid of
+ * the index, rows kept.  _stage_ms: device time of the inflate (plain text: the copy behind the unfinished line), the
+ * line scan and the rows kernels so far (HIP events).  After an error the object only reports it again. */
+int gffx_hip_sam_create(int device, uint32_t n_ref, const char *names /* concatenated */, const uint64_t *name_off /* n_ref + 1 */,
+                        const uint32_t *ref_seq, uint64_t header_bytes, uint64_t chunk_bytes, int bgzf, gffx_hip_sam **out);
+int gffx_hip_sam_feed(gffx_hip_sam *, const uint8_t *bytes, uint64_t n_bytes); /* bgzf: whole members; text: any split */
+int gffx_hip_sam_finish(gffx_hip_sam *);
+uint64_t gffx_hip_sam_rows(const gffx_hip_sam *);
+int gffx_hip_sam_counts(const gffx_hip_sam *, uint64_t *lines, uint64_t *unmapped, uint64_t *no_seq, uint64_t *kept);
+int gffx_hip_sam_stage_ms(const gffx_hip_sam *, double *inflate_ms, double *lines_ms, double *rows_ms);
+int gffx_hip_sam_copy_rows(gffx_hip_sam *, uint32_t *rows /* 3 per row */);
+void gffx_hip_sam_destroy(gffx_hip_sam *);
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,10 @@ pub struct gffx_hip_bam {
     _p: [u8; 0],
 }
 #[repr(C)]
+pub struct gffx_hip_sam {
+    _p: [u8; 0],
+}
+#[repr(C)]
 pub struct gffx_hip_union {
     _p: [u8; 0],
 }
@@ -137,6 +141,25 @@ extern "C" {
     pub fn gffx_hip_bam_stage_ms(h: *const gffx_hip_bam, inflate_ms: *mut f64, frame_ms: *mut f64, rows_ms: *mut f64) -> c_int;
     pub fn gffx_hip_bam_copy_rows(h: *mut gffx_hip_bam, rows: *mut u32) -> c_int;
     pub fn gffx_hip_bam_destroy(h: *mut gffx_hip_bam);
+    // SAM sources (depth.rs:588-591, coverage.rs:520-541): lines, fields, CIGARs and the RNAME lookup on the device; plain or BGZF text
+    pub fn gffx_hip_sam_create(
+        device: c_int,
+        n_ref: u32,
+        names: *const c_char,  // the @SQ names, concatenated
+        name_off: *const u64,  // n_ref + 1
+        ref_seq: *const u32,
+        header_bytes: u64,
+        chunk_bytes: u64,
+        bgzf: c_int,
+        out: *mut *mut gffx_hip_sam,
+    ) -> c_int;
+    pub fn gffx_hip_sam_feed(h: *mut gffx_hip_sam, bytes: *const u8, n_bytes: u64) -> c_int;
+    pub fn gffx_hip_sam_finish(h: *mut gffx_hip_sam) -> c_int;
+    pub fn gffx_hip_sam_rows(h: *const gffx_hip_sam) -> u64;
+    pub fn gffx_hip_sam_counts(h: *const gffx_hip_sam, lines: *mut u64, unmapped: *mut u64, no_seq: *mut u64, kept: *mut u64) -> c_int;
+    pub fn gffx_hip_sam_stage_ms(h: *const gffx_hip_sam, inflate_ms: *mut f64, lines_ms: *mut f64, rows_ms: *mut f64) -> c_int;
+    pub fn gffx_hip_sam_copy_rows(h: *mut gffx_hip_sam, rows: *mut u32) -> c_int;
+    pub fn gffx_hip_sam_destroy(h: *mut gffx_hip_sam);
     // the union of all rows of a run, built on the device (merge_intervals, coverage.rs:92-109); any grouping of the rows gives the same spans
     pub fn gffx_hip_union_create(device: c_int, n_seq: u32, out: *mut *mut gffx_hip_union) -> c_int;
     pub fn gffx_hip_union_add_host(u: *mut gffx_hip_union, rows: *const u32, n_rows: u64) -> c_int;

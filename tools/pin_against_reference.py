@@ -22,6 +22,17 @@ CLI on the same inputs and byte-diffs it against the reference directly; the wid
 widths up to 2 Mbp) sends the product down the wide form of the window kernels (round 4), which its --stats-json must confirm
 (`wide_form_passes` >= 1) -- so the day a real binary exists the kit pins the GPU paths themselves, not only the oracle.
 
+NOT pinned by this kit yet, and what a real `gffx` run (a binary linked against htslib) would have to pin by hand: the BAM and SAM
+sources of `depth` / `coverage`.  Their rules about htslib are ASSUMPTIONS restated from memory (device/bgzf_core.hpp,
+device/sam_core.hpp): run the real binary on `synth.write_bam` / `synth.write_sam` files of `synth.bam_test_records` and compare
+with the product's output to settle
+  * bam_endpos: end = pos + the M/D/N/=/X lengths, a reference length of 0 counting as 1 (BAM and SAM),
+  * SAM: a line without flag 0x4 whose CIGAR is `*` is treated as unmapped ("mapped query must have a CIGAR") and dropped --
+    while the BAM record of the same read is kept with end = pos + 1,
+  * SAM: a CIGAR operation length of 2^28 or more is a parse error,
+  * SAM: an RNAME that no @SQ line names gets a warning and tid -1 (the read is dropped, the run goes on),
+  * SAM: what else htslib rejects that the product reads (fields 5 and 7 to 11 and the tags are not validated here).
+
 Exit status: 0 = everything equal, or no toolchain (prints "no toolchain: nothing pinned"); 1 = at least one difference
 (the differing case, file and first differing byte are printed); 2 = usage / build failure.
 Nothing here is imported by the product or by the tests; it only uses oracle/ as the thing being checked.
