@@ -128,6 +128,16 @@ SIGNATURES = {
     "gffx_hip_sam_stage_ms": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gffx_hip_sam_copy_rows": (C.c_int, [vp, u32p]),
     "gffx_hip_sam_destroy": (None, [vp]),
+    "gffx_hip_ids_create": (C.c_int, [C.c_int, C.c_uint64, u8p, u64p, C.c_uint64, u32p, C.c_int, C.POINTER(vp)]),
+    "gffx_hip_ids_destroy": (None, [vp]),
+    "gffx_hip_ids_n": (C.c_uint64, [vp]),
+    "gffx_hip_ids_options": (C.c_int, [vp, C.c_char_p, C.c_size_t]),
+    "gffx_hip_ids_resolve": (C.c_int, [vp, C.c_uint64, u8p, u64p, u32p, u32p]),
+    "gffx_hip_ids_reset": (C.c_int, [vp]),
+    "gffx_hip_ids_copy_root_bitmap": (C.c_int, [vp, u64p, C.c_uint64]),
+    "gffx_hip_ids_copy_requested_bitmap": (C.c_int, [vp, u64p, C.c_uint64]),
+    "gffx_hip_ids_filter_lines": (C.c_int, [vp, u8p, C.c_uint64, C.c_uint64, u64p, u32p, C.c_int, C.c_uint32, u8p, u32p, u8p]),
+    "gffx_hip_ids_stage_ms": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
 _lib = None

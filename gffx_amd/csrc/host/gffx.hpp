@@ -11,6 +11,7 @@
 //   gffx::commands::coverage::{CoverageArgs, run}                                commands/coverage.rs (BED source)
 //   gffx::bam::read_rows                                                         depth.rs:297-372 / coverage.rs:125-168 (BAM source)
 //   gffx::sam::read_rows                                                         depth.rs:588-591 / coverage.rs:520-541 (SAM source)
+//   gffx::commands::extract::{ExtractArgs, run_extract}                          commands/extract.rs (extract.cpp)
 // Compute (Join A, Join B) goes through include/gffx_hip.h only; there is no CPU join here.
 #pragma once
 #include <algorithm>
@@ -384,6 +385,23 @@ struct CoverageArgs {  // coverage.rs:37-57
 void run(const CoverageArgs &args);  // coverage.rs:487-582
 
 }  // namespace coverage
+
+// ---- commands/extract.rs ---------------------------------------------------------------------------
+namespace extract {
+
+struct ExtractArgs {  // extract.rs:26-35
+    CommonArgs common;
+    std::optional<std::string> feature_id;    // -f/--feature-id (taken as given)
+    std::optional<std::string> feature_file;  // -F/--feature-file (one name per line)
+    int device = 0;                           // --device (addition)
+};
+
+// extract.rs:37-162: names -> fids -> roots -> blocks; whole blocks with -e (and no -T), else the lines whose ID was asked for.
+// Lookup, parent chase and the per-line ID test run on `device` (gffx_hip_ids_*).  GFFX_EXTRACT_CHUNK_BYTES sets the text bytes
+// per device pass of the line filter (default 64 MiB); results never depend on it.
+void run_extract(const ExtractArgs &args);
+
+}  // namespace extract
 }  // namespace commands
 
 // ---- BAM sources of depth / coverage (bam.cpp; commands/depth.rs:297-372, coverage.rs:125-168) ------------------------
@@ -404,7 +422,7 @@ std::vector<uint32_t> read_rows(const std::string &path, const std::unordered_ma
                                 bool verbose);
 }  // namespace sam
 
-// main.rs: `gffx <index|intersect|depth|coverage> ...`; returns the process exit code
+// main.rs: `gffx <index|intersect|extract|depth|coverage> ...`; returns the process exit code
 int cli_main(int argc, char **argv);
 
 }  // namespace gffx

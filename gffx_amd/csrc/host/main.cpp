@@ -1,5 +1,5 @@
 // main.cpp -- `gffx` command line for the intersect path: `gffx index` (prerequisite),
-// `gffx intersect` and `gffx depth` (BED source) (reference: main.rs:11-39, commands/depth.rs:34-72, commands/index.rs:11-23, commands/intersect.rs:32-70,
+// `gffx intersect`, `gffx extract` and `gffx depth` (BED source) (reference: main.rs:11-39, commands/depth.rs:34-72, commands/extract.rs:16-35, commands/index.rs:11-23, commands/intersect.rs:32-70,
 // utils/common.rs:17-52).  Flag names, short flags, defaults and groups follow the reference's
 // clap derive; usage errors exit 2 like clap, run-time errors print `Error: <msg>` and exit 1.
 #include <unistd.h>
@@ -90,6 +90,7 @@ const char *kTopUsage =
     "Usage: gffx <COMMAND>\n\nCommands:\n"
     "  index      Build index for GFF file\n"
     "  intersect  Extract models by a region or regions from a BED file (MI355X engine)\n"
+    "  extract    Extract models by feature IDs (MI355X engine)\n"
     "  depth      Compute coverage depth across genomic features from a BED, BAM or SAM file (MI355X engine)\n"
     "  coverage   Compute coverage breadth across genomic features from a BED, BAM or SAM file (MI355X engine)\n"
     "  help       Print this message\n";
@@ -111,6 +112,19 @@ const char *kIntersectUsage =
     "      --device <N>         HIP device to run on [default: 0]\n"
     "      --gpus <N>           Shard the BED regions by chromosome bucket over N devices [default: 1]\n"
     "      --stats-json <FILE>  Write the run's stage timers and counts as one JSON object\n";
+
+const char *kExtractUsage =
+    "Usage: gffx extract [OPTIONS] --input <FILE> <--feature-file <FEATURE_FILE>|--feature-id <FEATURE_ID>>\n\nOptions:\n"
+    "  -i, --input <FILE>                 Input GFF file path\n"
+    "  -o, --output <FILE>                Output file (stdout if not provided)\n"
+    "  -e, --entire_group                 Return the entire feature group for each match\n"
+    "  -T, --types <TYPES>                Comma-separated feature types to retain (e.g. exon,gene)\n"
+    "  -t, --threads <NUM>                Number of threads for parallel processing [default: 12]\n"
+    "  -v, --verbose                      Enable verbose output\n"
+    "  -f, --feature-id <FEATURE_ID>      A single feature ID\n"
+    "  -F, --feature-file <FEATURE_FILE>  File with one feature ID per line\n"
+    "      --device <N>                   HIP device to run on [default: 0]\n"
+    "      --stats-json <FILE>            Write the run's stage timers and counts as one JSON object\n";
 
 const char *kDepthUsage =
     "Usage: gffx depth [OPTIONS] --input <FILE> --source <SOURCE>\n\nOptions:\n"
@@ -184,6 +198,37 @@ int run_intersect_cli(int argc, char **argv) {
     if (o.count("gpus")) a.gpus = static_cast<int>(std::max<size_t>(1, std::min<size_t>(64, parse_size(o.at("gpus")[0], "--gpus <N>"))));
     if (o.count("stats-json")) g_run_stats.path = o.at("stats-json")[0];
     commands::intersect::run(a);
+    return 0;
+}
+
+int run_extract_cli(int argc, char **argv) {
+    static const std::vector<OptSpec> specs = {
+        {'i', "input", true},   {'o', "output", true},   {'e', "entire_group", false}, {'T', "types", true},
+        {'t', "threads", true}, {'v', "verbose", false}, {'f', "feature-id", true},    {'F', "feature-file", true},
+        {0, "device", true},    {0, "stats-json", true}, {'h', "help", false}};
+    const auto o = parse_opts(argc, argv, 2, specs);
+    if (o.count("help")) {
+        std::fputs(kExtractUsage, stdout);
+        return 0;
+    }
+    commands::extract::ExtractArgs a;
+    if (!o.count("input")) throw UsageError("the following required arguments were not provided:\n  --input <FILE>");
+    a.common.input = o.at("input")[0];
+    if (o.count("output")) a.common.output = o.at("output")[0];
+    a.common.entire_group = o.count("entire_group") > 0;
+    if (o.count("types")) a.common.types = o.at("types")[0];
+    if (o.count("threads")) a.common.threads = parse_size(o.at("threads")[0], "--threads <NUM>");
+    a.common.verbose = o.count("verbose") > 0;
+    if (o.count("feature-id")) a.feature_id = o.at("feature-id")[0];
+    if (o.count("feature-file")) a.feature_file = o.at("feature-file")[0];
+    // ArgGroup "feature": required, exactly one (extract.rs:21-25)
+    if (a.feature_id && a.feature_file)
+        throw UsageError("the argument '--feature-id <FEATURE_ID>' cannot be used with '--feature-file <FEATURE_FILE>'");
+    if (!a.feature_id && !a.feature_file)
+        throw UsageError("the following required arguments were not provided:\n  <--feature-file <FEATURE_FILE>|--feature-id <FEATURE_ID>>");
+    if (o.count("device")) a.device = static_cast<int>(parse_size(o.at("device")[0], "--device <N>"));
+    if (o.count("stats-json")) g_run_stats.path = o.at("stats-json")[0];
+    commands::extract::run_extract(a);
     return 0;
 }
 
@@ -311,6 +356,10 @@ int cli_main(int argc, char **argv) {
             usage = kIndexUsage;
             return run_index_cli(argc, argv);
         }
+        if (cmd == "extract") {
+            usage = kExtractUsage;
+            return run_extract_cli(argc, argv);
+        }
         if (cmd == "depth") {
             usage = kDepthUsage;
             return run_depth_cli(argc, argv);
@@ -319,7 +368,7 @@ int cli_main(int argc, char **argv) {
             usage = kCoverageUsage;
             return run_coverage_cli(argc, argv);
         }
-        throw UsageError("unrecognized subcommand '" + cmd + "' (this build carries the intersect, depth and coverage paths only)");
+        throw UsageError("unrecognized subcommand '" + cmd + "' (this build carries the intersect, extract, depth and coverage paths only)");
     } catch (const UsageError &e) {
         std::fprintf(stderr, "error: %s\n\n%s\nFor more information, try '--help'.\n", e.what(), usage);
         return 2;

@@ -49,22 +49,6 @@ bool split_line_for_join_b(std::string_view line, std::string_view &seq, uint32_
 
 namespace {
 
-// -T: the comma-separated type names, trimmed, empty ones dropped (intersect.rs:252-259)
-std::vector<std::string> split_types(const std::optional<std::string> &types_filter) {
-    std::vector<std::string> allow;
-    if (!types_filter) return allow;
-    size_t a = 0;
-    while (true) {
-        const size_t c = types_filter->find(',', a);
-        const std::string_view t =
-            trim_unicode_ws(std::string_view(*types_filter).substr(a, c == std::string::npos ? std::string::npos : c - a));
-        if (!t.empty()) allow.emplace_back(t);
-        if (c == std::string::npos) break;
-        a = c + 1;
-    }
-    return allow;
-}
-
 // blocks in output order (intersect.rs:335), sentinels and empty ranges dropped (:269-277)
 std::vector<std::pair<uint64_t, uint64_t>> hit_ranges(const std::vector<Block> &blocks, size_t file_len) {
     std::vector<std::pair<uint64_t, uint64_t>> ranges;

@@ -7,6 +7,7 @@
 #include <stdexcept>
 #include <string>
 #include <string_view>
+#include <vector>
 
 namespace gffx {
 
@@ -44,6 +45,22 @@ inline bool is_ascii_ws(unsigned char c) {           // u8::is_ascii_whitespace 
 }
 std::optional<uint32_t> parse_u32_rust(std::string_view s);   // str::parse::<u32>(): [+]digits
 std::optional<uint32_t> parse_u32_ascii(std::string_view s);  // intersect.rs:526-538: digits only
+
+// -T: the comma-separated type names, trimmed, empty ones dropped (intersect.rs:252-259, common.rs:306-311)
+inline std::vector<std::string> split_types(const std::optional<std::string> &types_filter) {
+    std::vector<std::string> allow;
+    if (!types_filter) return allow;
+    size_t a = 0;
+    while (true) {
+        const size_t c = types_filter->find(',', a);
+        const std::string_view t =
+            trim_unicode_ws(std::string_view(*types_filter).substr(a, c == std::string::npos ? std::string::npos : c - a));
+        if (!t.empty()) allow.emplace_back(t);
+        if (c == std::string::npos) break;
+        a = c + 1;
+    }
+    return allow;
+}
 
 inline void put_le32(std::string &out, uint32_t v) {
     char b[4] = {(char)v, (char)(v >> 8), (char)(v >> 16), (char)(v >> 24)};

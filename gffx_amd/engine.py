@@ -735,3 +735,111 @@ def sam_rows(data: bytes, names, ref_seq, header_bytes: int, chunk_bytes: int = 
         return r.rows()
     finally:
         r.close()
+
+
+# ---- `gffx extract` (include/gffx_hip.h "gffx extract"; device/ids.hip) ------------------------------------------------
+NONE = 0xFFFFFFFF  # a name that is not in the table / a fid without a valid root
+
+
+def _cat(names) -> Tuple[bytes, np.ndarray]:
+    nb = [n if isinstance(n, (bytes, bytearray)) else str(n).encode() for n in names]
+    off = np.zeros(len(nb) + 1, np.uint64)
+    if nb:
+        off[1:] = np.cumsum([len(n) for n in nb], dtype=np.uint64)
+    return b"".join(nb), off
+
+
+class FeatureIds:
+    """gffx_hip_ids_*: the feature-ID table of `.fts` with the parent pointers of `.prt` on the device (the reference's FtsMap +
+    PrtMap, index_loader/fts.rs:9-93, prt.rs:18-102).  A name's fid is the LAST line that holds it; a fid's root is where the
+    parent chase ends, NONE when a child or parent is out of range -- or, unlike the reference, which never returns then,
+    when a parent cycle has no root.  hash_bits (0..31) is a test hook: only that many low bits of the name hash are used."""
+
+    def __init__(self, handle, n_names: int, n_prt: int):
+        self._h = handle
+        self.n = n_names
+        self._words = (max(n_names, n_prt) + 63) // 64
+
+    @classmethod
+    def from_arrays(cls, names, prt, hash_bits: Optional[int] = None, device: int = 0) -> "FeatureIds":
+        blob, off = _cat(names)
+        p = _u32(prt)
+        buf, ptr = _u8(blob)
+        h = C.c_void_p()
+        check(lib().gffx_hip_ids_create(device, len(off) - 1, ptr, off.ctypes.data_as(u64p), len(p), _p(p) if len(p) else None,
+                                        -1 if hash_bits is None else int(hash_bits), C.byref(h)))
+        return cls(h, len(off) - 1, len(p))
+
+    @classmethod
+    def from_files(cls, gff: str, hash_bits: Optional[int] = None, device: int = 0) -> "FeatureIds":
+        """`<gff>.fts` (fts.rs:97-138: empty lines dropped, a trailing "\\r" stripped) and `<gff>.prt` (prt.rs:108-125)"""
+        with open(gff + ".fts", "rb") as f:
+            names = [ln[:-1] if ln.endswith(b"\r") else ln for ln in f.read().split(b"\n") if ln]
+        for n in names:
+            n.decode("utf-8")  # "FTS contains invalid UTF-8"
+        raw = open(gff + ".prt", "rb").read()
+        if len(raw) % 4:
+            raise ValueError("Corrupted PRT: not aligned to u32")
+        return cls.from_arrays(names, np.frombuffer(raw, dtype="<u4"), hash_bits, device)
+
+    def close(self) -> None:
+        if self._h:
+            lib().gffx_hip_ids_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def options(self) -> dict:
+        return _options(lib().gffx_hip_ids_options, self._h)
+
+    def resolve(self, names) -> Tuple[np.ndarray, np.ndarray]:
+        """(fids, roots) per name, NONE for a name that is not found / a fid without a valid root; the found fids and the
+        valid roots are added to the handle's bitmaps (requested_fids / unique_roots) until reset()."""
+        blob, off = _cat(names)
+        nq = len(off) - 1
+        fids, roots = np.zeros(max(nq, 1), np.uint32), np.zeros(max(nq, 1), np.uint32)
+        buf, ptr = _u8(blob)
+        check(lib().gffx_hip_ids_resolve(self._h, nq, ptr, off.ctypes.data_as(u64p), _p(fids), _p(roots)))
+        return fids[:nq], roots[:nq]
+
+    def _bits(self, fn) -> np.ndarray:
+        w = np.zeros(max(self._words, 1), np.uint64)
+        check(fn(self._h, w.ctypes.data_as(u64p), self._words))
+        return np.flatnonzero(np.unpackbits(w[:self._words].view(np.uint8), bitorder="little")).astype(np.uint32)
+
+    def unique_roots(self) -> np.ndarray:
+        return self._bits(lib().gffx_hip_ids_copy_root_bitmap)
+
+    def requested_fids(self) -> np.ndarray:
+        return self._bits(lib().gffx_hip_ids_copy_requested_bitmap)
+
+    def reset(self) -> None:
+        check(lib().gffx_hip_ids_reset(self._h))
+
+    def filter_lines(self, text: bytes, line_off, line_root, types=None) -> np.ndarray:
+        """keep[i] for line i = text[line_off[i]:line_off[i + 1]] (whole lines back to back, each with its line ending) in the
+        block of root line_root[i]: write_gff_output_filtered's test with the key "ID" (utils/common.rs:418-431).  types: None,
+        or the allowed column-3 names (-T already split at ',', trimmed, the empty ones dropped; an empty list keeps nothing)."""
+        lo = np.ascontiguousarray(line_off, dtype=np.uint64)
+        lr = _u32(line_root)
+        n = len(lr)
+        if len(lo) != n + 1:
+            raise ValueError("line_off needs one entry more than line_root")
+        keep = np.zeros(max(n, 1), np.uint8)
+        tb, toff = _cat(types or [])
+        toff32 = toff.astype(np.uint32)
+        buf, ptr = _u8(text)
+        tbuf, tptr = _u8(tb)
+        check(lib().gffx_hip_ids_filter_lines(self._h, ptr, len(text), n, lo.ctypes.data_as(u64p), _p(lr) if n else None,
+                                              int(types is not None), len(toff) - 1, tptr, _p(toff32),
+                                              keep.ctypes.data_as(_ffi.u8p)))
+        return keep[:n]
+
+    def stage_ms(self) -> Dict[str, float]:
+        v = [C.c_double() for _ in range(3)]
+        check(lib().gffx_hip_ids_stage_ms(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("build", "resolve", "filter"), (x.value for x in v)))

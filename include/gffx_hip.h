@@ -23,6 +23,9 @@
  *     (commands/depth.rs:297-372, coverage.rs:125-168)
  *   the same reader on a .sam file                       gffx_hip_sam_* (SAM sources, plain or BGZF-compressed)
  *     (commands/depth.rs:588-591, coverage.rs:520-541)
+ *   FtsMap::map_fnames_to_fids, PrtMap::map_fids_to_roots, gffx_hip_ids_* (`gffx extract`)
+ *   the ID test of write_gff_output_filtered
+ *     (index_loader/fts.rs:16-93, prt.rs:54-102, utils/common.rs:389-431)
  *
  * Semantics (bit-exact with the reference):
  *   a root interval iv of the query's seqid is a HIT iff  iv.start < q.end && iv.end > q.start
@@ -527,6 +530,45 @@ int gffx_hip_sam_counts(const gffx_hip_sam *, uint64_t *lines, uint64_t *unmappe
 int gffx_hip_sam_stage_ms(const gffx_hip_sam *, double *inflate_ms, double *lines_ms, double *rows_ms);
 int gffx_hip_sam_copy_rows(gffx_hip_sam *, uint32_t *rows /* 3 per row */);
 void gffx_hip_sam_destroy(gffx_hip_sam *);
+
+/* ---- `gffx extract`: feature-ID lookup, parent chase and the per-line ID filter (commands/extract.rs:37-162, ------------
+ * index_loader/fts.rs:16-31, index_loader/prt.rs:54-72, utils/common.rs:289-465; device/ids.hip, the rules of one name,
+ * one chase and one line in device/ids_core.hpp, shared with the host).
+ *
+ * _create builds the ID table on the device from the `.fts` strings -- name f is names[name_off[f], name_off[f + 1]) (no
+ * terminator), f = its line number = its fid -- and keeps the `.prt` words (prt[f] = the parent of f).  A name's fid is the
+ * LAST line that holds the string (fts.rs:16-22).  hash_bits < 0 or 32: the whole 32-bit hash; 0 to 31: only its low bits
+ * (a test hook: it forces the names onto few probe chains; results never depend on it); _options reports a non-default
+ * value as {"hash_bits": k}.  _n: the number of names.
+ * _resolve: per query name (bytes + offsets, as for _create) fid_out = its fid and root_out = the root the parent chase
+ * ends at (prt.rs:54-72: cur >= n_prt invalid; prt[cur] == cur the root; prt[cur] >= n_prt invalid), UINT32_MAX for a name
+ * that is not in the table / a fid without a valid root.  DEVIATION: a parent cycle that no root closes never ends in the
+ * reference; here the chase ends after n_prt steps and the fid is invalid.  Every found fid sets a bit of the requested
+ * bitmap, every valid root a bit of the root bitmap; both accumulate over calls until _reset.  _copy_*_bitmap: bit i of
+ * word i / 64, ceil(max(n_names, n_prt) / 64) words (n_words must be at least that).
+ * _filter_lines: text[0, n_bytes) holds n_lines whole lines back to back, line i = text[line_off[i], line_off[i + 1]) with its
+ * line ending (the last one may have none), line_root[i] = the root fid of the block the line lies in.  keep_out[i] = 1 iff
+ * write_gff_output_filtered keeps the line for the key "ID" (common.rs:418-431): its first byte is not '#'; with a type
+ * filter (by_type != 0; the n_types allowed strings already split at ',', trimmed and the empty ones dropped; none allowed
+ * keeps nothing) it has three TABs and column 3 is allowed; it has eight TABs, and the value after the first "ID=" behind
+ * the eighth TAB, up to the next ';' or the end of the line less a final "\n" and then "\r", is a name of the table whose
+ * fid was requested (in a _resolve since the last _reset) and whose root is line_root[i].
+ * _stage_ms: HIP-event milliseconds of the table build, the resolve and the filter kernels so far. */
+typedef struct gffx_hip_ids gffx_hip_ids;
+int gffx_hip_ids_create(int device, uint64_t n_names, const uint8_t *names /* concatenated */, const uint64_t *name_off /* n_names + 1 */,
+                        uint64_t n_prt, const uint32_t *prt, int hash_bits, gffx_hip_ids **out);
+void gffx_hip_ids_destroy(gffx_hip_ids *);
+uint64_t gffx_hip_ids_n(const gffx_hip_ids *);
+int gffx_hip_ids_options(const gffx_hip_ids *, char *buf, size_t cap);
+int gffx_hip_ids_resolve(gffx_hip_ids *, uint64_t n_queries, const uint8_t *names, const uint64_t *name_off /* n_queries + 1 */,
+                         uint32_t *fid_out, uint32_t *root_out);
+int gffx_hip_ids_reset(gffx_hip_ids *);
+int gffx_hip_ids_copy_root_bitmap(gffx_hip_ids *, uint64_t *host, uint64_t n_words);
+int gffx_hip_ids_copy_requested_bitmap(gffx_hip_ids *, uint64_t *host, uint64_t n_words);
+int gffx_hip_ids_filter_lines(gffx_hip_ids *, const uint8_t *text, uint64_t n_bytes, uint64_t n_lines, const uint64_t *line_off /* n_lines + 1 */,
+                              const uint32_t *line_root, int by_type, uint32_t n_types, const uint8_t *types /* concatenated */,
+                              const uint32_t *type_off /* n_types + 1 */, uint8_t *keep_out);
+int gffx_hip_ids_stage_ms(const gffx_hip_ids *, double *build_ms, double *resolve_ms, double *filter_ms);
 
 #ifdef __cplusplus
 }

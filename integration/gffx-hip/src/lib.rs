@@ -34,6 +34,10 @@ pub struct gffx_hip_sam {
     _p: [u8; 0],
 }
 #[repr(C)]
+pub struct gffx_hip_ids {
+    _p: [u8; 0],
+}
+#[repr(C)]
 pub struct gffx_hip_union {
     _p: [u8; 0],
 }
@@ -160,6 +164,39 @@ extern "C" {
     pub fn gffx_hip_sam_stage_ms(h: *const gffx_hip_sam, inflate_ms: *mut f64, lines_ms: *mut f64, rows_ms: *mut f64) -> c_int;
     pub fn gffx_hip_sam_copy_rows(h: *mut gffx_hip_sam, rows: *mut u32) -> c_int;
     pub fn gffx_hip_sam_destroy(h: *mut gffx_hip_sam);
+    // `gffx extract` (extract.rs:37-162): the `.fts` ID table, name -> fid -> root (fts.rs:16-93, prt.rs:54-102) and the ID test of
+    // write_gff_output_filtered (common.rs:389-431) on the device; u32::MAX = a name that is not found / a fid without a valid root
+    pub fn gffx_hip_ids_create(
+        device: c_int,
+        n_names: u64,
+        names: *const u8,     // the `.fts` strings, concatenated
+        name_off: *const u64, // n_names + 1
+        n_prt: u64,
+        prt: *const u32,
+        hash_bits: c_int,     // -1: the whole hash (0..31: a test hook)
+        out: *mut *mut gffx_hip_ids,
+    ) -> c_int;
+    pub fn gffx_hip_ids_destroy(h: *mut gffx_hip_ids);
+    pub fn gffx_hip_ids_n(h: *const gffx_hip_ids) -> u64;
+    pub fn gffx_hip_ids_options(h: *const gffx_hip_ids, buf: *mut c_char, cap: usize) -> c_int;
+    pub fn gffx_hip_ids_resolve(h: *mut gffx_hip_ids, n_queries: u64, names: *const u8, name_off: *const u64, fid_out: *mut u32, root_out: *mut u32) -> c_int;
+    pub fn gffx_hip_ids_reset(h: *mut gffx_hip_ids) -> c_int;
+    pub fn gffx_hip_ids_copy_root_bitmap(h: *mut gffx_hip_ids, host: *mut u64, n_words: u64) -> c_int;
+    pub fn gffx_hip_ids_copy_requested_bitmap(h: *mut gffx_hip_ids, host: *mut u64, n_words: u64) -> c_int;
+    pub fn gffx_hip_ids_filter_lines(
+        h: *mut gffx_hip_ids,
+        text: *const u8,
+        n_bytes: u64,
+        n_lines: u64,
+        line_off: *const u64, // n_lines + 1
+        line_root: *const u32,
+        by_type: c_int,
+        n_types: u32,
+        types: *const u8,     // the allowed column-3 strings, concatenated
+        type_off: *const u32, // n_types + 1
+        keep_out: *mut u8,
+    ) -> c_int;
+    pub fn gffx_hip_ids_stage_ms(h: *const gffx_hip_ids, build_ms: *mut f64, resolve_ms: *mut f64, filter_ms: *mut f64) -> c_int;
     // the union of all rows of a run, built on the device (merge_intervals, coverage.rs:92-109); any grouping of the rows gives the same spans
     pub fn gffx_hip_union_create(device: c_int, n_seq: u32, out: *mut *mut gffx_hip_union) -> c_int;
     pub fn gffx_hip_union_add_host(u: *mut gffx_hip_union, rows: *const u32, n_rows: u64) -> c_int;
