@@ -363,6 +363,8 @@ void write_block_table(const std::string &path, const BlockTable &t, uint64_t gf
 bool load_block_table(const std::string &path, uint64_t gff_bytes, uint64_t gof_key, BlockTable &t, std::string &why);
 BlockTable load_or_build_block_table(const std::string &gff_path, const index_loader::GofMap &gof, std::string_view gff,
                                      size_t threads, bool verbose);
+// GFFX_DEPTH_BATCH_ROWS sets the rows per device batch (default 4 Mi rows; a positive decimal number, capped at 1 << 28, anything
+// else is ignored), as GFFX_COVERAGE_BATCH_ROWS does for `coverage`: it bounds the staging buffers, and results never depend on it.
 void run(const DepthArgs &args);  // depth.rs:548-635
 
 }  // namespace depth

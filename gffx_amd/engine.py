@@ -125,6 +125,62 @@ class TreeIndexData:
         return np.ctypeslib.as_array(ptr, shape=(n,)).copy()
 
 
+class RegionStore:
+    """gffx_hip_regions_*: BED rows resident in HBM, filled chunk by chunk through two pinned staging buffers.  keep_all=False:
+    a ring of two slots of chunk_rows rows (an append from buffer k overwrites slot k); keep_all=True: every append goes
+    behind the rows before it, up to max(capacity_rows, chunk_rows) rows.  The caller's protocol is the commands': fill
+    ``staging(k)``, ``append(k, n)``, hand the rows to a batch / union / line table, and call ``wait_staging(k)`` (and
+    ``QueryBatch.sync`` for a batch that ran on slot k) before writing buffer k again."""
+
+    def __init__(self, capacity_rows: int, chunk_rows: int, keep_all: bool, device: int = 0):
+        self.chunk_rows = int(chunk_rows)
+        self.keep_all = bool(keep_all)
+        self._h = C.c_void_p()
+        check(lib().gffx_hip_regions_create(int(device), int(capacity_rows), self.chunk_rows, int(self.keep_all), C.byref(self._h)))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().gffx_hip_regions_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def staging(self, k: int) -> np.ndarray:
+        """Writable (chunk_rows, 3) u32 view of pinned staging buffer k; valid until close()."""
+        ptr = lib().gffx_hip_regions_staging(self._h, int(k))
+        if not ptr:
+            raise ValueError("staging buffer %r: k must be 0 or 1" % (k,))
+        return np.ctypeslib.as_array(C.cast(ptr, u32p), shape=(self.chunk_rows, 3))
+
+    def wait_staging(self, k: int) -> None:
+        check(lib().gffx_hip_regions_wait_staging(self._h, int(k)))
+
+    def append(self, k: int, n_rows: int) -> None:
+        """The first n_rows rows of staging buffer k go to the device (asynchronously)."""
+        check(lib().gffx_hip_regions_append(self._h, int(k), int(n_rows)))
+
+    def append_parts(self, k: int, stage_first, n_rows) -> None:
+        """One chunk gathered from pieces of staging buffer k: rows [stage_first[p], stage_first[p] + n_rows[p]) in the
+        order given, back to back on the device."""
+        f = np.ascontiguousarray(stage_first, dtype=np.uint64)
+        n = np.ascontiguousarray(n_rows, dtype=np.uint64)
+        if f.ndim != 1 or f.shape != n.shape:
+            raise ValueError("stage_first and n_rows must be 1-D and of the same length")
+        check(lib().gffx_hip_regions_append_parts(self._h, int(k), len(f), f.ctypes.data_as(u64p), n.ctypes.data_as(u64p)))
+
+    def rows(self) -> int:
+        """Rows held (keep_all stores; a ring reports 0)."""
+        return int(lib().gffx_hip_regions_rows(self._h))
+
+
 class QueryBatch:
     """Reusable query batch on one HIP stream (create once, run many)."""
 
@@ -161,6 +217,11 @@ class QueryBatch:
         """Borrow three device arrays (raw pointers, e.g. torch.Tensor.data_ptr())."""
         self._keep = keep
         check(lib().gffx_hip_batch_set_regions_device(self._h, d_chr, d_start, d_end, int(nq)))
+
+    def set_regions_store(self, store: "RegionStore", k: int, first: int, n_rows: int) -> None:
+        """Rows [first, first + n_rows) of the store's last append from staging buffer k (no copy: the batch reads the store)."""
+        self._keep = store
+        check(lib().gffx_hip_batch_set_regions_store(self._h, store.handle, int(k), int(first), int(n_rows)))
 
     def set_option(self, name: str, value: int) -> None:
         """A tuning knob of this batch's passes (include/gffx_hip.h "Tuning knobs"), e.g. ("WIN_THREADS", 512)."""
@@ -364,6 +425,12 @@ class LineTable:
                                                keep.ctypes.data_as(_ffi.u8p)))
         return keep[: self.n].astype(bool)
 
+    def test_store(self, store: "RegionStore", n_seq: int, mode: int = OverlapMode.Overlap) -> np.ndarray:
+        """The same with all rows of a keep_all ``RegionStore`` as the regions (what `gffx intersect` runs after Join A)."""
+        keep = np.zeros(max(self.n, 1), dtype=np.uint8)
+        check(lib().gffx_hip_lines_test_store(self._h, store.handle, int(n_seq), int(mode), keep.ctypes.data_as(_ffi.u8p)))
+        return keep[: self.n].astype(bool)
+
     @property
     def last_kernel_ms(self) -> float:
         """HIP-event duration of k_lines_exists in the last ``test`` call."""
@@ -475,8 +542,10 @@ class RegionUnion:
         r = _u32(rows).reshape(-1, 3)
         check(lib().gffx_hip_union_add_host(self._h, _p(r), r.shape[0]))
 
-    def add_store(self, store_handle, k: int, first: int, n_rows: int) -> None:
-        check(lib().gffx_hip_union_add_store(self._h, store_handle, k, first, n_rows))
+    def add_store(self, store, k: int, first: int, n_rows: int) -> None:
+        """Rows [first, first + n_rows) of the last append from staging buffer k of ``store`` (a RegionStore or a raw handle)."""
+        handle = store.handle if isinstance(store, RegionStore) else store
+        check(lib().gffx_hip_union_add_store(self._h, handle, int(k), int(first), int(n_rows)))
 
     def add_spans(self, u_off, us, ue) -> None:
         o = np.ascontiguousarray(u_off, dtype=np.uint64)

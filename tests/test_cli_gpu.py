@@ -143,7 +143,7 @@ def test_config1_10k_feature_gff_region_query(tmp_path):
 def test_multi_gpu_cli_is_byte_identical_and_streams_in_chunks(tmp_path):
     """`--gpus N`: every BED chunk is sharded by chromosome bucket over N devices (on this 1-GPU box the logical devices
     share the GPU); the output bytes equal the single-device run and the oracle, per-line mode and -e, and a 3 M-row BED
-    (72 MB of text: two 64 MB chunks through the pinned staging buffers)."""
+    (72 MB of text: five chunks of the default 16 MB through the pinned staging buffers)."""
     roots = synth.gencode_like_roots(4000, seed=17)
     gff = str(tmp_path / "a.gff")
     synth.write_gff3(gff, roots, seed=5, quirks=True)
