@@ -667,7 +667,7 @@ struct gffx_hip_lines {
     hipEvent_t ev_a = nullptr, ev_b = nullptr;  // bracket k_lines_exists of the last _test
     hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;  // ... and the device preparation of the region tables
     uint32_t note_seq = 0;                        // h_cnt = {degenerate regions, note_seq}, posted by the sort's histogram kernel
-    int last_sort_passes = 0;                     // radix passes of the last run's region sort (4 with the top digit, else 4 + seqid bytes)
+    int last_sort_passes = 0;                     // radix passes of the last run's region sort (4 with the top digit, else 4 + seqid bytes; 0: no regions)
     double last_kernel_ms = 0.0, last_prep_ms = 0.0;
     // region tables of the last _test (grow-only device buffers)
     uint64_t cap_q = 0, cap_seq = 0, cap_work = 0, cap_dir = 0, cap_blocks = 0;
@@ -825,6 +825,7 @@ static int lines_run(gffx_hip_lines *L, uint64_t nq, uint32_t n_seq, int mode, u
     L->d_de = nullptr;
     L->last_n_deg = 0;
     L->last_deg_known = false;
+    L->last_sort_passes = 0;  // (a run without regions sorts nothing: not the count of the run before)
     if (nq) {
         const uint32_t n_blocks = (uint32_t)((n + kScanBlock - 1) / kScanBlock);
         const size_t stride = L->cap_blocks + 1;

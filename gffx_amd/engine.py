@@ -438,7 +438,7 @@ class LineTable:
 
     @property
     def last_sort_passes(self) -> int:
-        """Radix passes of the last call's region sort (4 with the mixed-radix top digit, else 4 + seqid bytes)."""
+        """Radix passes of the last call's region sort (4 with the mixed-radix top digit, else 4 + seqid bytes; 0: no regions)."""
         return lib().gffx_hip_lines_last_sort_passes(self._h)
 
     @property

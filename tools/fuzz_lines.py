@@ -5,6 +5,7 @@ python tools/fuzz_lines.py [iterations] [seed]"""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.getcwd())
+sys.path.insert(1, os.path.join(os.getcwd(), "tests"))  # (the test modules import their shared helpers, tests/_*.py, by bare name)
 from gffx_amd import engine
 from tests.test_join_b_gpu import _oracle_keep
 from tests.test_coverage_gpu import _numpy_covered
