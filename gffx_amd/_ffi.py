@@ -138,9 +138,37 @@ SIGNATURES = {
     "gffx_hip_ids_copy_requested_bitmap": (C.c_int, [vp, u64p, C.c_uint64]),
     "gffx_hip_ids_filter_lines": (C.c_int, [vp, u8p, C.c_uint64, C.c_uint64, u64p, u32p, C.c_int, C.c_uint32, u8p, u32p, u8p]),
     "gffx_hip_ids_stage_ms": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gffx_hip_attrs_create": (C.c_int, [C.c_int, C.c_uint64, u8p, u64p, C.c_uint64, u32p, C.c_uint64, u32p, u8p, C.c_uint32, C.c_int, C.c_int,
+                                        C.POINTER(vp)]),
+    "gffx_hip_attrs_destroy": (None, [vp]),
+    "gffx_hip_attrs_n": (C.c_uint64, [vp]),
+    "gffx_hip_attrs_options": (C.c_int, [vp, C.c_char_p, C.c_size_t]),
+    "gffx_hip_attrs_match_exact": (C.c_int, [vp, C.c_uint64, u8p, u64p]),
+    "gffx_hip_attrs_match_dfa": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, u8p, C.POINTER(C.c_uint16)]),
+    "gffx_hip_attrs_dfa_kernel": (C.c_char_p, [vp]),
+    "gffx_hip_attrs_reset": (C.c_int, [vp]),
+    "gffx_hip_attrs_resolve": (C.c_int, [vp]),
+    "gffx_hip_attrs_copy_matched_bitmap": (C.c_int, [vp, u64p, C.c_uint64]),
+    "gffx_hip_attrs_copy_fid_bitmap": (C.c_int, [vp, u64p, C.c_uint64]),
+    "gffx_hip_attrs_copy_root_bitmap": (C.c_int, [vp, u64p, C.c_uint64]),
+    "gffx_hip_attrs_copy_invalid_bitmap": (C.c_int, [vp, u64p, C.c_uint64]),
+    "gffx_hip_attrs_filter_lines": (C.c_int, [vp, u8p, C.c_uint64, C.c_uint64, u64p, u32p, C.c_int, C.c_uint32, u8p, u32p, u8p]),
+    "gffx_hip_attrs_stage_ms": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+}
+
+# the regex compiler of `gffx search -r` in libgffx_host.so (include/gffx_host.h "gffx_host_regex_*"): name -> (restype, argtypes)
+HOST_LIB_PATH = os.path.join(_HERE, "lib", "libgffx_host.so")
+HOST_SIGNATURES = {
+    "gffx_host_regex_compile": (C.c_int, [C.c_uint64, u8p, u64p, C.c_uint32, C.POINTER(vp), C.c_char_p, C.c_size_t]),
+    "gffx_host_regex_groups": (C.c_uint32, [vp]),
+    "gffx_host_regex_group_info": (C.c_int, [vp, C.c_uint32, u32p, u32p, u32p, u32p, u32p]),
+    "gffx_host_regex_group_tables": (C.c_int, [vp, C.c_uint32, u8p, C.POINTER(C.c_uint16)]),
+    "gffx_host_regex_match": (C.c_int, [vp, C.c_uint64, u8p, u64p, u8p]),
+    "gffx_host_regex_destroy": (None, [vp]),
 }
 
 _lib = None
+_host = None
 
 
 class GffxHipError(RuntimeError):
@@ -169,3 +197,18 @@ def lib():
 def check(rc: int) -> None:
     if rc != 0:
         raise GffxHipError(rc, lib().gffx_hip_last_error().decode(errors="replace"))
+
+
+def host_lib():
+    """Load libgffx_host.so for the entry points of HOST_SIGNATURES (they need no device)."""
+    global _host
+    if _host is None:
+        if not os.path.exists(HOST_LIB_PATH):
+            raise ImportError("%s not found: build the host side first (make -C gffx_amd/csrc)" % HOST_LIB_PATH)
+        L = C.CDLL(HOST_LIB_PATH)
+        for name, (res, args) in HOST_SIGNATURES.items():
+            f = getattr(L, name)
+            f.restype = res
+            f.argtypes = args
+        _host = L
+    return _host

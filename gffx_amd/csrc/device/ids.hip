@@ -31,6 +31,7 @@
 #include "bgzf_device.hpp"
 #include "engine_private.hpp"
 #include "ids_core.hpp"
+#include "ids_insert_device.hpp"
 
 namespace gffx {
 
@@ -38,36 +39,13 @@ using ids::kNone;
 
 __global__ __launch_bounds__(256) void k_ids_fill(u64 *slot, uint32_t *val, uint32_t slots) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < slots) {
-        slot[i] = ids::kEmptyWord;
-        val[i] = 0;
-    }
+    if (i < slots) ids::table_clear_one(slot, val, i);
 }
 
 __global__ __launch_bounds__(256) void k_ids_insert(u64 *slot, uint32_t *val, const uint8_t *bytes, const u64 *off, uint32_t n,
                                                     uint32_t mask, uint32_t hash_mask) {
     const uint32_t f = blockIdx.x * 256u + threadIdx.x;
-    if (f >= n) return;
-    const u64 a = off[f], len = off[f + 1] - a;
-    const uint32_t h = ids::name_hash(bytes + a, len) & hash_mask;
-    const u64 mine = ((u64)h << 32) | f;
-    for (uint32_t i = h & mask, steps = 0; steps <= mask; i = (i + 1) & mask, ++steps) {  // (<= n slots are ever taken: it ends)
-        u64 w = slot[i];
-        if (w == ids::kEmptyWord) {
-            w = atomicCAS(&slot[i], ids::kEmptyWord, mine);
-            if (w == ids::kEmptyWord) {
-                atomicMax(&val[i], f);
-                return;
-            }
-        }
-        if ((uint32_t)(w >> 32) != h) continue;
-        const uint32_t rep = (uint32_t)w;
-        const u64 ra = off[rep];
-        if (off[rep + 1] - ra == len && ids::name_equal(bytes + ra, bytes + a, len)) {
-            atomicMax(&val[i], f);
-            return;
-        }
-    }
+    if (f < n) ids::table_insert_one(slot, val, bytes, off, f, mask, hash_mask);
 }
 
 __global__ __launch_bounds__(256) void k_ids_resolve(ids::Table t, const uint32_t *prt, uint32_t n_prt, const uint8_t *q, const u64 *q_off,

@@ -6,6 +6,7 @@
 
 #include "../../../include/gffx_host.h"
 #include "gffx.hpp"
+#include "regex_dfa.hpp"
 
 using namespace gffx;
 
@@ -305,3 +306,40 @@ extern "C" int gffx_host_plan_shards(const uint64_t *bucket_sizes, uint32_t n_ch
     *n_slices = flat.size() / 4;
     return 0;
 }
+
+extern "C" int gffx_host_regex_compile(uint64_t n, const uint8_t *patterns, const uint64_t *off, uint32_t max_states, void **out, char *err,
+                                       size_t errlen) {
+    if (!out) return -1;
+    *out = nullptr;
+    return guard(err, errlen, [&] {
+        if (n && (!patterns || !off)) throw Error("gffx_host_regex_compile: patterns or off is NULL");
+        std::vector<std::string> list;
+        for (uint64_t i = 0; i < n; ++i) list.emplace_back(reinterpret_cast<const char *>(patterns) + off[i], off[i + 1] - off[i]);
+        *out = new regex::Compiled(regex::compile(list, max_states));
+    });
+}
+extern "C" uint32_t gffx_host_regex_groups(const void *re) { return re ? (uint32_t) static_cast<const regex::Compiled *>(re)->groups.size() : 0; }
+extern "C" int gffx_host_regex_group_info(const void *re, uint32_t g, uint32_t *n_states, uint32_t *n_classes, uint32_t *init,
+                                          uint32_t *first_pattern, uint32_t *n_patterns) {
+    const auto *c = static_cast<const regex::Compiled *>(re);
+    if (!c || g >= c->groups.size() || !n_states || !n_classes || !init || !first_pattern || !n_patterns) return -1;
+    const regex::Dfa &d = c->groups[g];
+    *n_states = d.n_states, *n_classes = d.n_classes, *init = d.init, *first_pattern = d.first_pattern, *n_patterns = d.n_patterns;
+    return 0;
+}
+extern "C" int gffx_host_regex_group_tables(const void *re, uint32_t g, uint8_t *cls, uint16_t *trans) {
+    const auto *c = static_cast<const regex::Compiled *>(re);
+    if (!c || g >= c->groups.size() || !cls || !trans) return -1;
+    const regex::Dfa &d = c->groups[g];
+    std::memcpy(cls, d.cls, 256);
+    std::memcpy(trans, d.trans.data(), d.trans.size() * 2);
+    return 0;
+}
+extern "C" int gffx_host_regex_match(const void *re, uint64_t n, const uint8_t *values, const uint64_t *off, uint8_t *out) {
+    const auto *c = static_cast<const regex::Compiled *>(re);
+    if (!c || (n && (!values || !off || !out))) return -1;
+    for (uint64_t i = 0; i < n; ++i)
+        out[i] = regex::dfa_match(*c, std::string_view(reinterpret_cast<const char *>(values) + off[i], off[i + 1] - off[i])) ? 1 : 0;
+    return 0;
+}
+extern "C" void gffx_host_regex_destroy(void *re) { delete static_cast<regex::Compiled *>(re); }

@@ -23,6 +23,7 @@ using DepthHandle = Handle<gffx_hip_depth, gffx_hip_depth_destroy>;
 using LinesHandle = Handle<gffx_hip_lines, gffx_hip_lines_destroy>;
 using UnionHandle = Handle<gffx_hip_union, gffx_hip_union_destroy>;
 using IdsHandle = Handle<gffx_hip_ids, gffx_hip_ids_destroy>;
+using AttrsHandle = Handle<gffx_hip_attrs, gffx_hip_attrs_destroy>;
 
 // gffx_hip_x_create(..., OutPtr(h)): the `T **out` argument of a C-ABI constructor; h owns what the call stored.  Only as a
 // temporary inside the call's full expression (a hand-made std::out_ptr): h is set when the temporary dies.

@@ -12,6 +12,7 @@
 //   gffx::bam::read_rows                                                         depth.rs:297-372 / coverage.rs:125-168 (BAM source)
 //   gffx::sam::read_rows                                                         depth.rs:588-591 / coverage.rs:520-541 (SAM source)
 //   gffx::commands::extract::{ExtractArgs, run_extract}                          commands/extract.rs (extract.cpp)
+//   gffx::commands::search::{SearchArgs, run_search}                             commands/search.rs (search.cpp, regex_dfa.cpp)
 // Compute (Join A, Join B) goes through include/gffx_hip.h only; there is no CPU join here.
 #pragma once
 #include <algorithm>
@@ -404,6 +405,25 @@ struct ExtractArgs {  // extract.rs:26-35
 void run_extract(const ExtractArgs &args);
 
 }  // namespace extract
+
+// ---- commands/search.rs ----------------------------------------------------------------------------------------------
+namespace search {
+
+struct SearchArgs {  // search.rs:25-51
+    CommonArgs common;
+    std::optional<std::string> attr_list;  // -A/--attr-list (one value or pattern per line)
+    std::optional<std::string> attr;       // -a/--attr (taken as given)
+    bool regex = false;                    // -r/--regex
+    int device = 0;                        // --device (addition)
+};
+
+// search.rs:55-252: values or patterns -> aids -> fids -> roots -> blocks; whole blocks with -e (and no -T), else the lines
+// whose `<attribute name>=` value was matched under that root.  The match of every `.atn` value, the fid / root resolution
+// and the per-line value test run on `device` (gffx_hip_attrs_*); with -r the patterns are compiled to DFAs on the host
+// first (regex_dfa.hpp: a documented subset; GFFX_SEARCH_DFA_STATES caps the states of one DFA).
+void run_search(const SearchArgs &args);
+
+}  // namespace search
 }  // namespace commands
 
 // ---- BAM sources of depth / coverage (bam.cpp; commands/depth.rs:297-372, coverage.rs:125-168) ------------------------
@@ -424,7 +444,7 @@ std::vector<uint32_t> read_rows(const std::string &path, const std::unordered_ma
                                 bool verbose);
 }  // namespace sam
 
-// main.rs: `gffx <index|intersect|extract|depth|coverage> ...`; returns the process exit code
+// main.rs: `gffx <index|intersect|extract|search|depth|coverage> ...`; returns the process exit code
 int cli_main(int argc, char **argv);
 
 }  // namespace gffx

@@ -1,5 +1,5 @@
 // main.cpp -- `gffx` command line for the intersect path: `gffx index` (prerequisite),
-// `gffx intersect`, `gffx extract` and `gffx depth` (BED source) (reference: main.rs:11-39, commands/depth.rs:34-72, commands/extract.rs:16-35, commands/index.rs:11-23, commands/intersect.rs:32-70,
+// `gffx intersect`, `gffx extract`, `gffx search` and `gffx depth` (BED source) (reference: main.rs:11-39, commands/depth.rs:34-72, commands/extract.rs:16-35, commands/search.rs:18-51, commands/index.rs:11-23, commands/intersect.rs:32-70,
 // utils/common.rs:17-52).  Flag names, short flags, defaults and groups follow the reference's
 // clap derive; usage errors exit 2 like clap, run-time errors print `Error: <msg>` and exit 1.
 #include <unistd.h>
@@ -91,6 +91,7 @@ const char *kTopUsage =
     "  index      Build index for GFF file\n"
     "  intersect  Extract models by a region or regions from a BED file (MI355X engine)\n"
     "  extract    Extract models by feature IDs (MI355X engine)\n"
+    "  search     Search features by attribute values (MI355X engine)\n"
     "  depth      Compute coverage depth across genomic features from a BED, BAM or SAM file (MI355X engine)\n"
     "  coverage   Compute coverage breadth across genomic features from a BED, BAM or SAM file (MI355X engine)\n"
     "  help       Print this message\n";
@@ -125,6 +126,20 @@ const char *kExtractUsage =
     "  -F, --feature-file <FEATURE_FILE>  File with one feature ID per line\n"
     "      --device <N>                   HIP device to run on [default: 0]\n"
     "      --stats-json <FILE>            Write the run's stage timers and counts as one JSON object\n";
+
+const char *kSearchUsage =
+    "Usage: gffx search [OPTIONS] --input <FILE> <--attr-list <ATTR_LIST>|--attr <ATTR>>\n\nOptions:\n"
+    "  -i, --input <FILE>           Input GFF file path\n"
+    "  -o, --output <FILE>          Output file (stdout if not provided)\n"
+    "  -e, --entire_group           Return the entire feature group for each match\n"
+    "  -T, --types <TYPES>          Comma-separated feature types to retain (e.g. exon,gene)\n"
+    "  -t, --threads <NUM>          Number of threads for parallel processing [default: 12]\n"
+    "  -v, --verbose                Enable verbose output\n"
+    "  -A, --attr-list <ATTR_LIST>  Attribute list file (one per line)\n"
+    "  -a, --attr <ATTR>            Single attribute value to search\n"
+    "  -r, --regex                  Enable regex mode for attribute matching (a subset of the syntax: see DESIGN.md)\n"
+    "      --device <N>             HIP device to run on [default: 0]\n"
+    "      --stats-json <FILE>      Write the run's stage timers and counts as one JSON object\n";
 
 const char *kDepthUsage =
     "Usage: gffx depth [OPTIONS] --input <FILE> --source <SOURCE>\n\nOptions:\n"
@@ -229,6 +244,37 @@ int run_extract_cli(int argc, char **argv) {
     if (o.count("device")) a.device = static_cast<int>(parse_size(o.at("device")[0], "--device <N>"));
     if (o.count("stats-json")) g_run_stats.path = o.at("stats-json")[0];
     commands::extract::run_extract(a);
+    return 0;
+}
+
+int run_search_cli(int argc, char **argv) {
+    static const std::vector<OptSpec> specs = {
+        {'i', "input", true},   {'o', "output", true},   {'e', "entire_group", false}, {'T', "types", true},
+        {'t', "threads", true}, {'v', "verbose", false}, {'A', "attr-list", true},     {'a', "attr", true},
+        {'r', "regex", false},  {0, "device", true},     {0, "stats-json", true},      {'h', "help", false}};
+    const auto o = parse_opts(argc, argv, 2, specs);
+    if (o.count("help")) {
+        std::fputs(kSearchUsage, stdout);
+        return 0;
+    }
+    commands::search::SearchArgs a;
+    if (!o.count("input")) throw UsageError("the following required arguments were not provided:\n  --input <FILE>");
+    a.common.input = o.at("input")[0];
+    if (o.count("output")) a.common.output = o.at("output")[0];
+    a.common.entire_group = o.count("entire_group") > 0;
+    if (o.count("types")) a.common.types = o.at("types")[0];
+    if (o.count("threads")) a.common.threads = parse_size(o.at("threads")[0], "--threads <NUM>");
+    a.common.verbose = o.count("verbose") > 0;
+    if (o.count("attr-list")) a.attr_list = o.at("attr-list")[0];
+    if (o.count("attr")) a.attr = o.at("attr")[0];
+    a.regex = o.count("regex") > 0;
+    // ArgGroup "attr_input": required, exactly one (search.rs:19-24)
+    if (a.attr_list && a.attr) throw UsageError("the argument '--attr-list <ATTR_LIST>' cannot be used with '--attr <ATTR>'");
+    if (!a.attr_list && !a.attr)
+        throw UsageError("the following required arguments were not provided:\n  <--attr-list <ATTR_LIST>|--attr <ATTR>>");
+    if (o.count("device")) a.device = static_cast<int>(parse_size(o.at("device")[0], "--device <N>"));
+    if (o.count("stats-json")) g_run_stats.path = o.at("stats-json")[0];
+    commands::search::run_search(a);
     return 0;
 }
 
@@ -360,6 +406,10 @@ int cli_main(int argc, char **argv) {
             usage = kExtractUsage;
             return run_extract_cli(argc, argv);
         }
+        if (cmd == "search") {
+            usage = kSearchUsage;
+            return run_search_cli(argc, argv);
+        }
         if (cmd == "depth") {
             usage = kDepthUsage;
             return run_depth_cli(argc, argv);
@@ -368,7 +418,7 @@ int cli_main(int argc, char **argv) {
             usage = kCoverageUsage;
             return run_coverage_cli(argc, argv);
         }
-        throw UsageError("unrecognized subcommand '" + cmd + "' (this build carries the intersect, extract, depth and coverage paths only)");
+        throw UsageError("unrecognized subcommand '" + cmd + "' (this build carries the intersect, extract, search, depth and coverage paths only)");
     } catch (const UsageError &e) {
         std::fprintf(stderr, "error: %s\n\n%s\nFor more information, try '--help'.\n", e.what(), usage);
         return 2;

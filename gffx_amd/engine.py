@@ -912,3 +912,168 @@ class FeatureIds:
         v = [C.c_double() for _ in range(3)]
         check(lib().gffx_hip_ids_stage_ms(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("build", "resolve", "filter"), (x.value for x in v)))
+
+
+# ---- `gffx search` (include/gffx_hip.h "gffx search"; device/search.hip; the regex compiler in libgffx_host.so) -----------
+_host_lib = _ffi.host_lib  # (include/gffx_host.h: the regex compiler lives on the host and needs no device)
+
+
+class RegexError(ValueError):
+    """a pattern outside the subset of `gffx search -r`, or one that needs more DFA states than the cap"""
+
+
+class CompiledRegex:
+    """The DFAs of a pattern list (host/regex_dfa.hpp): groups[g] = dict(n_states, n_classes, init, first_pattern, n_patterns,
+    cls (256 x u8: byte -> column), trans (n_states x n_classes u16; the last column is the end of the text; state 0 accepts
+    and is absorbing)).  match(values) runs device/search_core.hpp's loop on the host."""
+
+    def __init__(self, handle):
+        self._h = handle
+        L = _host_lib()
+        self.groups: List[dict] = []
+        for g in range(L.gffx_host_regex_groups(handle)):
+            v = [C.c_uint32() for _ in range(5)]
+            if L.gffx_host_regex_group_info(handle, g, *[C.byref(x) for x in v]) != 0:
+                raise RuntimeError("gffx_host_regex_group_info failed for group %d" % g)
+            ns, nc, init, first, npat = (x.value for x in v)
+            cls = np.zeros(256, np.uint8)
+            trans = np.zeros(ns * nc, np.uint16)
+            if L.gffx_host_regex_group_tables(handle, g, cls.ctypes.data_as(_ffi.u8p), trans.ctypes.data_as(C.POINTER(C.c_uint16))) != 0:
+                raise RuntimeError("gffx_host_regex_group_tables failed for group %d" % g)
+            self.groups.append(dict(n_states=ns, n_classes=nc, init=init, first_pattern=first, n_patterns=npat, cls=cls,
+                                    trans=trans.reshape(ns, nc)))
+
+    def match(self, values) -> np.ndarray:
+        blob, off = _cat(values)
+        n = len(off) - 1
+        out = np.zeros(max(n, 1), np.uint8)
+        buf, ptr = _u8(blob)
+        if _host_lib().gffx_host_regex_match(self._h, n, ptr, off.ctypes.data_as(u64p), out.ctypes.data_as(_ffi.u8p)) != 0:
+            raise RuntimeError("gffx_host_regex_match failed (a closed CompiledRegex?)")
+        return out[:n].astype(bool)
+
+    def close(self) -> None:
+        if self._h:
+            _host_lib().gffx_host_regex_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def compile_regex(patterns, max_states: int = 0) -> CompiledRegex:
+    """The patterns (str or bytes) of one `gffx search -r` run as DFAs; RegexError for syntax outside the subset and for a
+    pattern over the state cap (max_states; 0: GFFX_SEARCH_DFA_STATES, else the 64 KiB default).  Needs no device."""
+    blob, off = _cat(patterns)
+    buf, ptr = _u8(blob)
+    h = C.c_void_p()
+    err = C.create_string_buffer(4096)
+    if _host_lib().gffx_host_regex_compile(len(off) - 1, ptr, off.ctypes.data_as(u64p), int(max_states), C.byref(h), err, len(err)) != 0:
+        raise RegexError(err.value.decode(errors="replace"))
+    return CompiledRegex(h)
+
+
+class AttrSearch:
+    """gffx_hip_attrs_*: the attribute values of `.atn` with the fid -> aid words of `.a2f` and the parent words of `.prt` on
+    the device (commands/search.rs:89-218).  match / match_regex OR into the matched-aid bitmap until reset(); resolve() turns
+    it into the fid, root and invalid-fid bitmaps and the (value class, root) pair set that filter_lines tests against.
+    hash_bits (0..31) and dfa_path ("lds" / "global") are test hooks; results never depend on them."""
+
+    def __init__(self, handle, n_values: int, n_a2f: int, n_prt: int):
+        self._h = handle
+        self.n = n_values
+        self._mwords = (n_values + 63) // 64
+        self._words = (max(n_a2f, n_prt) + 63) // 64
+
+    @classmethod
+    def from_arrays(cls, values, a2f, prt, key="gene_name", hash_bits: Optional[int] = None, dfa_path: Optional[str] = None,
+                    device: int = 0) -> "AttrSearch":
+        blob, off = _cat(values)
+        a, p = _u32(a2f), _u32(prt)
+        kb = key if isinstance(key, (bytes, bytearray)) else str(key).encode()
+        buf, ptr = _u8(blob)
+        kbuf, kptr = _u8(kb)
+        h = C.c_void_p()
+        check(lib().gffx_hip_attrs_create(device, len(off) - 1, ptr, off.ctypes.data_as(u64p), len(a), _p(a) if len(a) else None, len(p),
+                                          _p(p) if len(p) else None, kptr, len(kb), -1 if hash_bits is None else int(hash_bits),
+                                          {None: 0, "lds": 1, "global": 2}[dfa_path], C.byref(h)))
+        return cls(h, len(off) - 1, len(a), len(p))
+
+    def close(self) -> None:
+        if self._h:
+            lib().gffx_hip_attrs_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def options(self) -> dict:
+        return _options(lib().gffx_hip_attrs_options, self._h)
+
+    def match(self, wanted) -> None:
+        """exact: every aid whose value is one of the wanted strings (search.rs:105-110)"""
+        blob, off = _cat(wanted)
+        buf, ptr = _u8(blob)
+        check(lib().gffx_hip_attrs_match_exact(self._h, len(off) - 1, ptr, off.ctypes.data_as(u64p)))
+
+    def match_regex(self, compiled: CompiledRegex) -> List[str]:
+        """every aid whose value some group's DFA accepts (search.rs:99-103); returns the kernel form each group's launch took"""
+        names = []
+        for g in compiled.groups:
+            trans = np.ascontiguousarray(g["trans"], dtype=np.uint16)
+            check(lib().gffx_hip_attrs_match_dfa(self._h, g["n_states"], g["n_classes"], g["init"], g["cls"].ctypes.data_as(_ffi.u8p),
+                                                 trans.ctypes.data_as(C.POINTER(C.c_uint16))))
+            names.append(lib().gffx_hip_attrs_dfa_kernel(self._h).decode())
+        return names
+
+    def reset(self) -> None:
+        check(lib().gffx_hip_attrs_reset(self._h))
+
+    def resolve(self) -> None:
+        check(lib().gffx_hip_attrs_resolve(self._h))
+
+    def _bits(self, fn, words) -> np.ndarray:
+        w = np.zeros(max(words, 1), np.uint64)
+        check(fn(self._h, w.ctypes.data_as(u64p), words))
+        return np.flatnonzero(np.unpackbits(w[:words].view(np.uint8), bitorder="little")).astype(np.uint32)
+
+    def matched_aids(self) -> np.ndarray:
+        return self._bits(lib().gffx_hip_attrs_copy_matched_bitmap, self._mwords)
+
+    def matched_fids(self) -> np.ndarray:
+        return self._bits(lib().gffx_hip_attrs_copy_fid_bitmap, self._words)
+
+    def unique_roots(self) -> np.ndarray:
+        return self._bits(lib().gffx_hip_attrs_copy_root_bitmap, self._words)
+
+    def invalid_fids(self) -> np.ndarray:
+        return self._bits(lib().gffx_hip_attrs_copy_invalid_bitmap, self._words)
+
+    def filter_lines(self, text: bytes, line_off, line_root, types=None) -> np.ndarray:
+        """keep[i] for line i = text[line_off[i]:line_off[i + 1]] in the block of root line_root[i]: write_gff_output_filtered's
+        test with the key `<attribute name>` (utils/common.rs:418-431) against the pairs of the last resolve().  types as for
+        FeatureIds.filter_lines."""
+        lo = np.ascontiguousarray(line_off, dtype=np.uint64)
+        lr = _u32(line_root)
+        n = len(lr)
+        if len(lo) != n + 1:
+            raise ValueError("line_off needs one entry more than line_root")
+        keep = np.zeros(max(n, 1), np.uint8)
+        tb, toff = _cat(types or [])
+        toff32 = toff.astype(np.uint32)
+        buf, ptr = _u8(text)
+        tbuf, tptr = _u8(tb)
+        check(lib().gffx_hip_attrs_filter_lines(self._h, ptr, len(text), n, lo.ctypes.data_as(u64p), _p(lr) if n else None,
+                                                int(types is not None), len(toff) - 1, tptr, _p(toff32), keep.ctypes.data_as(_ffi.u8p)))
+        return keep[:n]
+
+    def stage_ms(self) -> Dict[str, float]:
+        v = [C.c_double() for _ in range(4)]
+        check(lib().gffx_hip_attrs_stage_ms(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("build", "match", "resolve", "filter"), (x.value for x in v)))

@@ -570,6 +570,56 @@ int gffx_hip_ids_filter_lines(gffx_hip_ids *, const uint8_t *text, uint64_t n_by
                               const uint32_t *type_off /* n_types + 1 */, uint8_t *keep_out);
 int gffx_hip_ids_stage_ms(const gffx_hip_ids *, double *build_ms, double *resolve_ms, double *filter_ms);
 
+/* ---- `gffx search`: attribute-value and regex lookup, fid / root resolution and the per-line value filter ---------------
+ * (commands/search.rs:55-252, index_loader/core.rs:37-89, index_loader/a2f.rs:77-113, index_loader/prt.rs:54-72,
+ * utils/common.rs:289-465; device/search.hip, the rules of one value, one chase and one line in device/search_core.hpp and
+ * device/ids_core.hpp, shared with the host).
+ *
+ * _create keeps the `.atn` values -- value a is values[value_off[a], value_off[a + 1]) (no terminator), a = its position in
+ * the loaded list = its aid --, the `.a2f` words (a2f[f] = the aid of fid f, UINT32_MAX: none), the `.prt` words and the
+ * attribute name key[0, key_len) (without '='), and builds on the device a string table over the values and the class of
+ * every aid: the largest aid with the same string.  hash_bits as for gffx_hip_ids_create (a test hook for both the value
+ * table and the table of wanted strings).  dfa_path: 0 = k_attr_match_dfa stages its tables in LDS when they fit 64 KiB
+ * and reads them from global memory otherwise; 1 = LDS (tables that do not fit fail the call); 2 = global (a test hook).
+ * _options reports non-default values as {"hash_bits": k, "dfa_path": "lds" | "global"}.  _n: the number of values.
+ * _match_exact: every aid whose value equals one of the n_wanted strings (bytes + offsets, as for _create) gets its bit in
+ * the matched bitmap (search.rs:105-110: every duplicate of a wanted string matches).
+ * _match_dfa: every aid whose value the DFA accepts gets its bit.  The DFA is host/regex_dfa.cpp's: cls[256] maps a byte to a
+ * column < n_classes - 1, the last column is the end of the text, trans[s * n_classes + c] < n_states, state 0 accepts and
+ * is absorbing, the walk starts in init; tables that break these bounds fail the call.  Values are valid UTF-8 from the
+ * loader; on other bytes the answer is unspecified, the walk is bounded all the same.  _dfa_kernel names the form the last
+ * _match_dfa took: "k_attr_match_dfa<lds>" or "k_attr_match_dfa<global>".
+ * Matches accumulate (OR) over calls until _reset, which clears all four bitmaps and the pair set.
+ * _resolve: from the matched bitmap as it stands, per fid f with a matched aid: bit f of the fid bitmap; the root of f
+ * (prt.rs:54-72; DEVIATION as for gffx_hip_ids_resolve: the chase ends after n_prt steps) sets a bit of the root bitmap, or
+ * f a bit of the invalid bitmap; (class of the aid, root) enters the pair set.  Each call starts from empty results.
+ * _copy_matched_bitmap: ceil(n_values / 64) words; the other three: ceil(max(n_a2f, n_prt) / 64) words; bit i of word i / 64.
+ * _filter_lines: as gffx_hip_ids_filter_lines, with this test of the value: the bytes after the first "<key>=" behind the
+ * eighth TAB, up to the next ';' or the end of the line, are a string of `.atn` whose class forms a pair with line_root[i]
+ * -- that is: some fid whose root is line_root[i] carries a matched value with exactly these bytes (search.rs:209-218).
+ * _stage_ms: HIP-event milliseconds of the table build, the match, the resolve and the filter kernels so far. */
+typedef struct gffx_hip_attrs gffx_hip_attrs;
+int gffx_hip_attrs_create(int device, uint64_t n_values, const uint8_t *values /* concatenated */, const uint64_t *value_off /* n_values + 1 */,
+                          uint64_t n_a2f, const uint32_t *a2f, uint64_t n_prt, const uint32_t *prt, const uint8_t *key, uint32_t key_len,
+                          int hash_bits, int dfa_path, gffx_hip_attrs **out);
+void gffx_hip_attrs_destroy(gffx_hip_attrs *);
+uint64_t gffx_hip_attrs_n(const gffx_hip_attrs *);
+int gffx_hip_attrs_options(const gffx_hip_attrs *, char *buf, size_t cap);
+int gffx_hip_attrs_match_exact(gffx_hip_attrs *, uint64_t n_wanted, const uint8_t *wanted, const uint64_t *wanted_off /* n_wanted + 1 */);
+int gffx_hip_attrs_match_dfa(gffx_hip_attrs *, uint32_t n_states, uint32_t n_classes, uint32_t init, const uint8_t *cls /* 256 */,
+                             const uint16_t *trans /* n_states x n_classes */);
+const char *gffx_hip_attrs_dfa_kernel(const gffx_hip_attrs *);
+int gffx_hip_attrs_reset(gffx_hip_attrs *);
+int gffx_hip_attrs_resolve(gffx_hip_attrs *);
+int gffx_hip_attrs_copy_matched_bitmap(gffx_hip_attrs *, uint64_t *host, uint64_t n_words);
+int gffx_hip_attrs_copy_fid_bitmap(gffx_hip_attrs *, uint64_t *host, uint64_t n_words);
+int gffx_hip_attrs_copy_root_bitmap(gffx_hip_attrs *, uint64_t *host, uint64_t n_words);
+int gffx_hip_attrs_copy_invalid_bitmap(gffx_hip_attrs *, uint64_t *host, uint64_t n_words);
+int gffx_hip_attrs_filter_lines(gffx_hip_attrs *, const uint8_t *text, uint64_t n_bytes, uint64_t n_lines, const uint64_t *line_off /* n_lines + 1 */,
+                                const uint32_t *line_root, int by_type, uint32_t n_types, const uint8_t *types /* concatenated */,
+                                const uint32_t *type_off /* n_types + 1 */, uint8_t *keep_out);
+int gffx_hip_attrs_stage_ms(const gffx_hip_attrs *, double *build_ms, double *match_ms, double *resolve_ms, double *filter_ms);
+
 #ifdef __cplusplus
 }
 #endif

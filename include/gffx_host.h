@@ -64,6 +64,20 @@ int gffx_host_all_lines_check(const char *gff, const char *types, uint32_t threa
  * chunk; the reference buckets by seqid first, commands/intersect.rs:114-120).  slices = malloc'd (rank, chr, lo, hi) u64
  * quadruples, ranks ascending, a rank's slices sorted by (chr, lo). */
 int gffx_host_plan_shards(const uint64_t *bucket_sizes, uint32_t n_chr, uint32_t n_ranks, uint64_t **slices, uint64_t *n_slices);
+/* The regex subset of `gffx search -r` (host/regex_dfa.hpp), without a device.  _compile: the n patterns (bytes + n + 1
+ * offsets) as one alternation, determinised under a cap of max_states states per DFA (0: GFFX_SEARCH_DFA_STATES, else the
+ * cap that keeps one table within 64 KiB) and split into groups in list order where the union exceeds it; -1 with the
+ * message in err for syntax outside the subset ("unsupported regex syntax at byte N of ...") and for a single pattern over
+ * the cap ("regex too large ...").  _group_info / _group_tables: group g's shape (n_classes counts the end-of-text column,
+ * the last one) and tables (cls: 256 bytes; trans: n_states x n_classes u16; state 0 accepts and is absorbing).  _match:
+ * out[i] = 1 iff some group accepts value i (device/search_core.hpp's loop on the host: what the device runs per value). */
+int gffx_host_regex_compile(uint64_t n, const uint8_t *patterns, const uint64_t *off, uint32_t max_states, void **out, char *err, size_t errlen);
+uint32_t gffx_host_regex_groups(const void *re);
+int gffx_host_regex_group_info(const void *re, uint32_t g, uint32_t *n_states, uint32_t *n_classes, uint32_t *init, uint32_t *first_pattern,
+                               uint32_t *n_patterns);
+int gffx_host_regex_group_tables(const void *re, uint32_t g, uint8_t *cls, uint16_t *trans);
+int gffx_host_regex_match(const void *re, uint64_t n, const uint8_t *values, const uint64_t *off, uint8_t *out);
+void gffx_host_regex_destroy(void *re);
 /* the `gffx` command line in-process (main.rs); returns the exit code */
 int gffx_host_cli(int argc, char **argv);
 void gffx_host_free(void *);
