@@ -17,9 +17,9 @@
 //   k_bam_rows       one wave per segment, one lane per record: validate (bgzf_core.hpp bam_record), keep or skip, and
 //                    compact the kept rows in file order (count pass, scan over the segments, write pass).
 // The unfinished record at D's end is carried into the next chunk (any size), so device memory is bounded by the chunk
-// size plus the longest record.  Staging is double-buffered: while the kernels work on one sub-batch, the host copies the
-// next one into pinned memory and its host -> device transfer runs on a second stream.  The device then idles while the
-// host takes the finished sub-batch's rows back (12 B per read) and moves its carry.
+// size plus the longest record.  Staging, the sub-batches of members, the drain's sync, rows and carry, and the sticky
+// failure are the pipeline of source_stream.hpp, shared with sam.hip; this file keeps the kernels, their enqueue, the
+// check of ChunkResult in the middle of the drain (a malformed record, named by the member it begins in) and _finish.
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -27,7 +27,7 @@
 #include <string>
 #include <vector>
 
-#include "bgzf_device.hpp"
+#include "source_stream.hpp"
 
 namespace gffx {
 
@@ -239,134 +239,51 @@ void launch_scan(hipStream_t s, const uint32_t *in, uint32_t n, u64 *out, u64 *t
 using namespace gffx;
 
 struct gffx_hip_bam {
-    int device = 0;
     uint32_t n_ref = 0;
-    uint64_t skip = 0;           // header bytes still to skip in the decompressed stream
-    uint64_t chunk_bytes = 0;    // compressed bytes per sub-batch
-    uint64_t out_cap = 0;        // decompressed bytes per sub-batch (without the carry)
-    uint64_t file_off = 0;       // compressed bytes fed so far
-    hipStream_t stream = nullptr;       // the kernels, in order
-    hipStream_t copy_stream = nullptr;  // host -> device copies of the next sub-batch, beside the kernels of this one
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t copied[2] = {nullptr, nullptr};  // in[k] / dir[k] have arrived
-    uint8_t *stage[2] = {nullptr, nullptr};  // pinned compressed bytes, double-buffered
-    uint64_t stage_cap[2] = {0, 0};
-    int cur_stage = 0;
-    BgzfDir *stage_dir[2] = {nullptr, nullptr};
-    ChunkResult *res_host = nullptr;         // pinned
-    DevArr<uint8_t> in[2], D[2];
-    DevArr<BgzfDir> dir[2];  // dst relative to the end of the carry
-    DevArr<int32_t> status;
     DevArr<ChunkResult> res;
-    DevArr<uint32_t> ref_seq, guess_n, count, kept_n, rows;
+    DevArr<uint32_t> ref_seq, guess_n, count, kept_n;
     DevArr<u64> seg, guess_end, entry, rec_base, rec_off, out_base;
-    // the sub-batch in flight (enqueued, not drained)
-    bool in_flight = false;
-    int cur = 0;           // D[cur] holds its decompressed stream
-    uint64_t carry = 0;    // bytes of the unfinished record at D[cur]'s start (before the in-flight batch: after drain)
-    uint64_t n_D = 0;      // its D length
+    // the sub-batch in flight, beside what the pipeline keeps of it
     uint32_t n_blocks = 0;
-    std::vector<BgzfDir> fl_dir;  // its members (file offsets for messages)
-    uint64_t fl_file_off = 0;
     uint64_t fl_carry = 0;        // the carry in front of its members in D
     uint64_t carry_file_off = 0;  // file offset of the member in which the carried record begins
     std::vector<u64> seg_host;    // its segment bounds (the source of an asynchronous copy: kept until the next enqueue)
-    // results
-    std::vector<uint32_t> out_rows;
-    uint64_t records = 0, unmapped = 0, no_seq = 0, kept = 0;
-    double ms[3] = {0, 0, 0};  // inflate, frame, rows
-    int error = GFFX_OK;
-    std::string error_msg;
-
-    ~gffx_hip_bam() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (copy_stream) (void)hipStreamSynchronize(copy_stream);
-        for (int k = 0; k < 2; ++k) {
-            if (copied[k]) (void)hipEventDestroy(copied[k]);
-            if (stage[k]) (void)hipHostFree(stage[k]);
-            if (stage_dir[k]) (void)hipHostFree(stage_dir[k]);
-        }
-        if (res_host) (void)hipHostFree(res_host);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-        if (copy_stream) (void)hipStreamDestroy(copy_stream);
-    }
+    uint64_t records = 0;
+    SourceStream s;  // (last, so destroyed first: its streams are idle before the arrays above are freed)
 };
 
 namespace {
-int sticky(gffx_hip_bam *h, int rc) {
-    if (rc != GFFX_OK && h->error == GFFX_OK) {
-        h->error = rc;
-        h->error_msg = g_last_error;
-    }
-    return rc;
-}
-
 // file offset of the member whose output holds byte `off` of the in-flight sub-batch's D (the carry: where its record began)
 uint64_t member_of(const gffx_hip_bam *h, uint64_t off) {
-    if (off < h->fl_carry || h->fl_dir.empty()) return h->carry_file_off;
-    uint64_t m = h->fl_dir[0].src;
-    for (const BgzfDir &d : h->fl_dir)
+    const SourceStream &S = h->s;
+    if (off < h->fl_carry || S.fl_dir.empty()) return h->carry_file_off;
+    uint64_t m = S.fl_dir[0].src;
+    for (const BgzfDir &d : S.fl_dir)
         if (h->fl_carry + d.dst <= off) m = d.src;
-    return h->fl_file_off + m;
+    return S.fl_file_off + m;
 }
 
 // waits for the sub-batch in flight, takes its rows and moves its unfinished record to the other D buffer.  (The copies of
 // the next sub-batch are already on their way: stage_upload runs before this.)
 int drain(gffx_hip_bam *h) {
-    if (!h->in_flight) return GFFX_OK;
-    h->in_flight = false;
-    GFFX_HIP_TRY(hipStreamSynchronize(h->stream));
-    const ChunkResult r = *h->res_host;
-    if (r.bad_block != 0xFFFFFFFFu) {
-        int32_t st = 0;
-        GFFX_HIP_TRY(hipMemcpy(&st, h->status.p + r.bad_block, sizeof st, hipMemcpyDeviceToHost));
-        return fail(GFFX_E_INVALID, "BGZF block at file offset %llu: %s",
-                    (unsigned long long)(h->fl_file_off + h->fl_dir[r.bad_block].src), bgzf::status_name(st));
-    }
+    SourceStream &S = h->s;
+    if (!S.in_flight) return GFFX_OK;
+    if (int rc = S.drain_front(&S.result<ChunkResult>()->bad_block)) return rc;
+    const ChunkResult r = *S.result<ChunkResult>();
     if (r.frame_status || r.rows_status)
         return fail(GFFX_E_INVALID, "malformed BAM record (block_size, read name or CIGAR out of range, or refID not in the header) "
                                     "that begins in the BGZF block at file offset %llu",
                     (unsigned long long)member_of(h, r.err_off));
-    float t = 0;
-    if (hipEventElapsedTime(&t, h->ev[0], h->ev[1]) == hipSuccess) h->ms[0] += t;
-    if (hipEventElapsedTime(&t, h->ev[1], h->ev[2]) == hipSuccess) h->ms[1] += t;
-    if (hipEventElapsedTime(&t, h->ev[2], h->ev[3]) == hipSuccess) h->ms[2] += t;
     h->records += r.records;
-    h->unmapped += r.unmapped;
-    h->no_seq += r.no_seq;
-    h->kept += r.kept;
-    if (r.kept) {
-        const size_t at = h->out_rows.size();
-        h->out_rows.resize(at + 3 * r.kept);
-        GFFX_HIP_TRY(hipMemcpy(h->out_rows.data() + at, h->rows.p, r.kept * 12, hipMemcpyDeviceToHost));
-    }
-    const uint64_t c = h->n_D - r.tail;
-    if (c) h->carry_file_off = member_of(h, r.tail);
-    const int nxt = 1 - h->cur;
-    GFFX_HIP_TRY(h->D[nxt].ensure(c + h->out_cap));
-    if (c) GFFX_HIP_TRY(hipMemcpyAsync(h->D[nxt].p, h->D[h->cur].p + r.tail, c, hipMemcpyDeviceToDevice, h->stream));
-    h->cur = nxt;
-    h->carry = c;
-    return GFFX_OK;
-}
-
-// starts the copies of stage[k] (n_src compressed bytes, nb members) to in[k] / dir[k] on the copy stream.  Their previous
-// contents belonged to the sub-batch before last, which has been drained.
-int stage_upload(gffx_hip_bam *h, int k, uint32_t nb, uint64_t n_src) {
-    GFFX_HIP_TRY(h->in[k].ensure(n_src));
-    GFFX_HIP_TRY(h->dir[k].ensure(nb));
-    GFFX_HIP_TRY(hipMemcpyAsync(h->in[k].p, h->stage[k], n_src, hipMemcpyHostToDevice, h->copy_stream));
-    GFFX_HIP_TRY(hipMemcpyAsync(h->dir[k].p, h->stage_dir[k], nb * sizeof(BgzfDir), hipMemcpyHostToDevice, h->copy_stream));
-    GFFX_HIP_TRY(hipEventRecord(h->copied[k], h->copy_stream));
-    return GFFX_OK;
+    if (S.n_D - r.tail) h->carry_file_off = member_of(h, r.tail);
+    return S.drain_back(r.tail, r.kept, r.unmapped, r.no_seq);
 }
 
 // enqueues the kernels on members dir[0, nb) of in[k] (once their copies have arrived): inflate after the carry, frame, rows
 int enqueue(gffx_hip_bam *h, int k, uint32_t nb, uint64_t file_off) {
-    const BgzfDir *dir = h->stage_dir[k];
-    const uint64_t C = h->carry;
+    SourceStream &S = h->s;
+    const BgzfDir *dir = S.stage_dir[k];
+    const uint64_t C = S.carry;
     uint64_t T = 0;
     for (uint32_t i = 0; i < nb; ++i) T += dir[i].isize;
     const uint64_t N = C + T;
@@ -375,11 +292,11 @@ int enqueue(gffx_hip_bam *h, int k, uint32_t nb, uint64_t file_off) {
     seg.assign(n_seg + 1, 0);
     for (uint32_t i = 0; i < nb; ++i) seg[i + 1] = C + dir[i].dst;
     seg[n_seg] = N;
-    const u64 start = std::min<u64>(h->skip, N);
-    h->skip -= start;
+    const u64 start = std::min<u64>(S.skip, N);
+    S.skip -= start;
     const size_t max_rec = N / 36 + 1;
-    GFFX_HIP_TRY(h->D[h->cur].ensure(N));
-    GFFX_HIP_TRY(h->status.ensure(nb));
+    GFFX_HIP_TRY(S.D[S.cur].ensure(N));
+    GFFX_HIP_TRY(S.status.ensure(nb));
     GFFX_HIP_TRY(h->seg.ensure(n_seg + 1));
     GFFX_HIP_TRY(h->guess_end.ensure(n_seg));
     GFFX_HIP_TRY(h->guess_n.ensure(n_seg));
@@ -389,21 +306,21 @@ int enqueue(gffx_hip_bam *h, int k, uint32_t nb, uint64_t file_off) {
     GFFX_HIP_TRY(h->rec_base.ensure(n_seg + 1));
     GFFX_HIP_TRY(h->out_base.ensure(n_seg + 1));
     GFFX_HIP_TRY(h->rec_off.ensure(max_rec));
-    GFFX_HIP_TRY(h->rows.ensure(3 * max_rec));
-    hipStream_t s = h->stream;
-    uint8_t *D = h->D[h->cur].p;
-    ChunkResult *res = h->res.p;
+    GFFX_HIP_TRY(S.rows.ensure(3 * max_rec));
+    hipStream_t s = S.stream;
+    uint8_t *D = S.D[S.cur].p;
+    ChunkResult *res = h->res.p, *res_host = S.result<ChunkResult>();
     ChunkResult init{};
     init.tail = N;
     init.bad_block = 0xFFFFFFFFu;
-    *h->res_host = init;
-    GFFX_HIP_TRY(hipMemcpyAsync(res, h->res_host, sizeof init, hipMemcpyHostToDevice, s));
+    *res_host = init;
+    GFFX_HIP_TRY(hipMemcpyAsync(res, res_host, sizeof init, hipMemcpyHostToDevice, s));
     GFFX_HIP_TRY(hipMemcpyAsync(h->seg.p, seg.data(), (n_seg + 1) * sizeof(u64), hipMemcpyHostToDevice, s));
-    GFFX_HIP_TRY(hipStreamWaitEvent(s, h->copied[k], 0));
-    GFFX_HIP_TRY(hipEventRecord(h->ev[0], s));
-    if (nb) hipLaunchKernelGGL(k_bgzf_inflate, dim3(nb), dim3(64), 0, s, h->in[k].p, h->dir[k].p, nb, D + C, h->status.p, &res->bad_block);
+    GFFX_HIP_TRY(hipStreamWaitEvent(s, S.copied[k], 0));
+    GFFX_HIP_TRY(hipEventRecord(S.ev[0], s));
+    if (nb) hipLaunchKernelGGL(k_bgzf_inflate, dim3(nb), dim3(64), 0, s, S.in[k].p, S.dir[k].p, nb, D + C, S.status.p, &res->bad_block);
     GFFX_HIP_TRY(hipGetLastError());
-    GFFX_HIP_TRY(hipEventRecord(h->ev[1], s));
+    GFFX_HIP_TRY(hipEventRecord(S.ev[1], s));
     hipLaunchKernelGGL(k_frame_guess, dim3((n_seg + 255) / 256), dim3(256), 0, s, D, N, h->seg.p, n_seg, h->guess_end.p, h->guess_n.p, res);
     hipLaunchKernelGGL(k_frame_fix, dim3(1), dim3(64), 0, s, D, N, h->seg.p, n_seg, start, h->guess_end.p, h->guess_n.p, h->entry.p,
                        h->count.p, res);
@@ -411,20 +328,17 @@ int enqueue(gffx_hip_bam *h, int k, uint32_t nb, uint64_t file_off) {
     hipLaunchKernelGGL(k_frame_list, dim3((n_seg + 255) / 256), dim3(256), 0, s, D, n_seg, h->entry.p, h->count.p, h->rec_base.p,
                        h->rec_off.p, res);
     GFFX_HIP_TRY(hipGetLastError());
-    GFFX_HIP_TRY(hipEventRecord(h->ev[2], s));
+    GFFX_HIP_TRY(hipEventRecord(S.ev[2], s));
     hipLaunchKernelGGL(k_bam_rows<0>, dim3(n_seg), dim3(64), 0, s, D, h->rec_base.p, h->rec_off.p, h->n_ref, h->ref_seq.p, h->kept_n.p,
-                       h->out_base.p, h->rows.p, res);
+                       h->out_base.p, S.rows.p, res);
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, h->kept_n.p, n_seg, h->out_base.p, &res->kept);
     hipLaunchKernelGGL(k_bam_rows<1>, dim3(n_seg), dim3(64), 0, s, D, h->rec_base.p, h->rec_off.p, h->n_ref, h->ref_seq.p, h->kept_n.p,
-                       h->out_base.p, h->rows.p, res);
+                       h->out_base.p, S.rows.p, res);
     GFFX_HIP_TRY(hipGetLastError());
-    GFFX_HIP_TRY(hipEventRecord(h->ev[3], s));
-    GFFX_HIP_TRY(hipMemcpyAsync(h->res_host, res, sizeof(ChunkResult), hipMemcpyDeviceToHost, s));
-    h->in_flight = true;
-    h->n_D = N;
+    GFFX_HIP_TRY(hipEventRecord(S.ev[3], s));
+    GFFX_HIP_TRY(hipMemcpyAsync(res_host, res, sizeof(ChunkResult), hipMemcpyDeviceToHost, s));
+    S.set_in_flight(N, k, nb, file_off);
     h->n_blocks = nb;
-    h->fl_dir.assign(dir, dir + nb);
-    h->fl_file_off = file_off;
     h->fl_carry = C;
     return GFFX_OK;
 }
@@ -439,16 +353,11 @@ extern "C" int gffx_hip_bam_create(int device, uint32_t n_ref, const uint32_t *r
     GFFX_HIP_TRY(hipSetDevice(device));
     std::unique_ptr<gffx_hip_bam> h(new (std::nothrow) gffx_hip_bam);
     if (!h) return fail(GFFX_E_OOM, "gffx_hip_bam_create: out of host memory");
-    h->device = device;
     h->n_ref = n_ref;
-    h->skip = header_bytes;
-    h->chunk_bytes = std::max<uint64_t>(chunk_bytes ? chunk_bytes : (256ull << 20), 1);
-    h->out_cap = std::min<uint64_t>(std::max<uint64_t>(4 * h->chunk_bytes, 1ull << 20), 1ull << 30);
-    GFFX_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    GFFX_HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    for (hipEvent_t &e : h->ev) GFFX_HIP_TRY(hipEventCreate(&e));
-    for (hipEvent_t &e : h->copied) GFFX_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    GFFX_HIP_TRY(hipHostMalloc((void **)&h->res_host, sizeof(ChunkResult)));
+    h->s.skip = header_bytes;
+    h->s.chunk_bytes = std::max<uint64_t>(chunk_bytes ? chunk_bytes : (256ull << 20), 1);
+    h->s.out_cap = SourceStream::bgzf_out_cap(h->s.chunk_bytes);
+    if (int rc = h->s.init(device, "gffx_hip_bam_feed", sizeof(ChunkResult))) return rc;
     GFFX_HIP_TRY(h->res.ensure(1));
     GFFX_HIP_TRY(h->ref_seq.ensure(std::max<uint32_t>(n_ref, 1)));
     if (n_ref) GFFX_HIP_TRY(hipMemcpy(h->ref_seq.p, ref_seq, n_ref * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -458,86 +367,53 @@ extern "C" int gffx_hip_bam_create(int device, uint32_t n_ref, const uint32_t *r
 
 extern "C" int gffx_hip_bam_feed(gffx_hip_bam *h, const uint8_t *bgzf, uint64_t n_bytes) {
     if (!h) return fail(GFFX_E_INVALID, "gffx_hip_bam_feed: NULL handle");
-    if (h->error) return fail(h->error, "%s", h->error_msg.c_str());
+    SourceStream &S = h->s;
+    if (S.error) return fail(S.error, "%s", S.error_msg.c_str());
     if (n_bytes && !bgzf) return fail(GFFX_E_INVALID, "gffx_hip_bam_feed: NULL input");
-    GFFX_HIP_TRY(hipSetDevice(h->device));
-    std::vector<BgzfDir> all;
-    if (int rc = walk_members(bgzf, n_bytes, h->file_off, &all)) return sticky(h, rc);
-    // sub-batches: at most chunk_bytes compressed, out_cap decompressed, kMaxBlocksPerBatch members (at least one member)
-    size_t i = 0;
-    while (i < all.size()) {
-        size_t j = i;
-        uint64_t src = 0, dst = 0;
-        while (j < all.size() && (j == i || (src + all[j].len <= h->chunk_bytes && dst + all[j].isize <= h->out_cap &&
-                                             j - i < kMaxBlocksPerBatch))) {
-            src += all[j].len;
-            dst += all[j].isize;
-            ++j;
-        }
-        const int k = h->cur_stage;
-        h->cur_stage ^= 1;
-        if (src > h->stage_cap[k]) {
-            if (h->stage[k]) (void)hipHostFree(h->stage[k]);
-            h->stage[k] = nullptr;
-            h->stage_cap[k] = 0;
-            if (hipHostMalloc((void **)&h->stage[k], src) != hipSuccess)
-                return sticky(h, fail(GFFX_E_OOM, "gffx_hip_bam_feed: pinned staging of %llu bytes", (unsigned long long)src));
-            h->stage_cap[k] = src;
-        }
-        if (!h->stage_dir[k] && hipHostMalloc((void **)&h->stage_dir[k], kMaxBlocksPerBatch * sizeof(BgzfDir)) != hipSuccess)
-            return sticky(h, fail(GFFX_E_OOM, "gffx_hip_bam_feed: pinned directory"));
-        // while the previous sub-batch runs: its successor's bytes into the other staging buffer and on to the device
-        std::memcpy(h->stage[k], bgzf + all[i].src, src);
-        for (size_t x = i; x < j; ++x) {
-            BgzfDir d = all[x];
-            d.src -= all[i].src;
-            d.dst -= all[i].dst;
-            h->stage_dir[k][x - i] = d;
-        }
-        if (int rc = stage_upload(h, k, (uint32_t)(j - i), src)) return sticky(h, rc);
-        if (int rc = drain(h)) return sticky(h, rc);
-        if (int rc = enqueue(h, k, (uint32_t)(j - i), h->file_off + all[i].src)) return sticky(h, rc);
-        i = j;
-    }
-    h->file_off += n_bytes;
+    GFFX_HIP_TRY(hipSetDevice(S.device));
+    const int rc = S.feed_members(bgzf, n_bytes, [h](int k, uint32_t nb, uint64_t, uint64_t file_off) {
+        if (int e = drain(h)) return e;
+        return enqueue(h, k, nb, file_off);
+    });
+    if (rc) return S.sticky(rc);
+    S.file_off += n_bytes;
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_bam_finish(gffx_hip_bam *h) {
     if (!h) return fail(GFFX_E_INVALID, "gffx_hip_bam_finish: NULL handle");
-    if (h->error) return fail(h->error, "%s", h->error_msg.c_str());
-    GFFX_HIP_TRY(hipSetDevice(h->device));
-    if (int rc = drain(h)) return sticky(h, rc);
-    if (h->skip) return sticky(h, fail(GFFX_E_INVALID, "BAM file ends inside its header (%llu bytes missing)", (unsigned long long)h->skip));
-    if (h->carry)
-        return sticky(h, fail(GFFX_E_INVALID, "BAM file ends inside a record (%llu bytes of an unfinished record)", (unsigned long long)h->carry));
+    SourceStream &S = h->s;
+    if (S.error) return fail(S.error, "%s", S.error_msg.c_str());
+    GFFX_HIP_TRY(hipSetDevice(S.device));
+    if (int rc = drain(h)) return S.sticky(rc);
+    if (S.skip) return S.sticky(fail(GFFX_E_INVALID, "BAM file ends inside its header (%llu bytes missing)", (unsigned long long)S.skip));
+    if (S.carry)
+        return S.sticky(fail(GFFX_E_INVALID, "BAM file ends inside a record (%llu bytes of an unfinished record)", (unsigned long long)S.carry));
     return GFFX_OK;
 }
 
-extern "C" uint64_t gffx_hip_bam_rows(const gffx_hip_bam *h) { return h ? h->out_rows.size() / 3 : 0; }
+extern "C" uint64_t gffx_hip_bam_rows(const gffx_hip_bam *h) { return h ? h->s.n_rows() : 0; }
 
 extern "C" int gffx_hip_bam_counts(const gffx_hip_bam *h, uint64_t *records, uint64_t *unmapped, uint64_t *no_seq, uint64_t *kept) {
     if (!h) return fail(GFFX_E_INVALID, "gffx_hip_bam_counts: NULL handle");
     if (records) *records = h->records;
-    if (unmapped) *unmapped = h->unmapped;
-    if (no_seq) *no_seq = h->no_seq;
-    if (kept) *kept = h->kept;
+    if (unmapped) *unmapped = h->s.unmapped;
+    if (no_seq) *no_seq = h->s.no_seq;
+    if (kept) *kept = h->s.kept;
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_bam_stage_ms(const gffx_hip_bam *h, double *inflate, double *frame, double *rows) {
     if (!h) return fail(GFFX_E_INVALID, "gffx_hip_bam_stage_ms: NULL handle");
-    if (inflate) *inflate = h->ms[0];
-    if (frame) *frame = h->ms[1];
-    if (rows) *rows = h->ms[2];
+    h->s.stage_ms(inflate, frame, rows);
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_bam_copy_rows(gffx_hip_bam *h, uint32_t *rows) {
     if (!h) return fail(GFFX_E_INVALID, "gffx_hip_bam_copy_rows: NULL handle");
-    if (h->in_flight) return fail(GFFX_E_STATE, "gffx_hip_bam_copy_rows: call gffx_hip_bam_finish first");
-    if (!h->out_rows.empty() && !rows) return fail(GFFX_E_INVALID, "gffx_hip_bam_copy_rows: rows is NULL");
-    if (!h->out_rows.empty()) std::memcpy(rows, h->out_rows.data(), h->out_rows.size() * sizeof(uint32_t));
+    if (h->s.in_flight) return fail(GFFX_E_STATE, "gffx_hip_bam_copy_rows: call gffx_hip_bam_finish first");
+    if (h->s.n_rows() && !rows) return fail(GFFX_E_INVALID, "gffx_hip_bam_copy_rows: rows is NULL");
+    h->s.copy_rows(rows);
     return GFFX_OK;
 }
 

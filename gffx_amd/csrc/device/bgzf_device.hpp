@@ -1,5 +1,6 @@
-// bgzf_device.hpp -- what the source readers of the engine share (bgzf.hip: BAM, sam.hip: SAM): the member directory of a
-// BGZF chunk, a growable device array, and launchers of the two kernels both use (defined in bgzf.hip).
+// bgzf_device.hpp -- the pieces the source readers of the engine share (bgzf.hip: BAM, sam.hip: SAM): the member directory
+// of a BGZF chunk, a growable device array, and launchers of the two kernels both use (defined in bgzf.hip).  The streaming
+// pipeline built from them is source_stream.hpp.
 #pragma once
 #include <algorithm>
 #include <vector>

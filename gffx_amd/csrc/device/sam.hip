@@ -14,6 +14,10 @@
 //                    line (a final line need not end in '\n'): the last tile then lists one more line end, at N.
 //   k_sam_rows       one wave per tile, over the lines that end in the tile: validate (sam_record), keep or skip, and compact
 //                    the kept rows in file order (count pass, scan over the tiles, write pass) -- the shape of k_bam_rows.
+// Staging, the sub-batches (BGZF members as in bgzf.hip, or plain text in pieces of chunk_bytes), the drain's sync, rows
+// and carry, and the sticky failure are the pipeline of source_stream.hpp, shared with bgzf.hip; this file keeps the
+// kernels, their enqueue, the pending text, the check of SamResult in the middle of the drain (the first malformed line)
+// and _finish (a last line without '\n').
 //
 // LANE SHARING in k_sam_rows: one lane per line, and the lane runs sam_record() as the host does.  Reason: there is one code
 // path for a 60-byte line, a 1 MB line and a CIGAR of 70,000 operations -- the one tools/sam_check.cpp runs under the
@@ -31,7 +35,7 @@
 #include <string>
 #include <vector>
 
-#include "bgzf_device.hpp"
+#include "source_stream.hpp"
 #include "sam_core.hpp"
 
 namespace gffx {
@@ -186,204 +190,100 @@ __global__ __launch_bounds__(64) void k_sam_rows(const uint8_t *D, u64 start, co
 using namespace gffx;
 
 struct gffx_hip_sam {
-    int device = 0;
     bool bgzf = false;
-    uint64_t skip = 0;         // header bytes still to skip in the text
-    uint64_t chunk_bytes = 0;  // fed bytes per sub-batch (text: exactly, but for the last; BGZF: compressed, at most)
-    uint64_t out_cap = 0;      // text bytes per sub-batch (without the carry)
-    uint64_t file_off = 0;     // bytes fed so far
-    hipStream_t stream = nullptr;       // the kernels, in order
-    hipStream_t copy_stream = nullptr;  // host -> device copies of the next sub-batch, beside the kernels of this one
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t copied[2] = {nullptr, nullptr};  // in[k] / dir[k] have arrived
-    uint8_t *stage[2] = {nullptr, nullptr};     // pinned fed bytes, double-buffered
-    uint64_t stage_cap[2] = {0, 0};
-    int cur_stage = 0;
-    BgzfDir *stage_dir[2] = {nullptr, nullptr};
-    SamResult *res_host = nullptr;  // pinned
-    std::vector<uint8_t> pend;      // text fed in pieces smaller than a sub-batch
-    DevArr<uint8_t> in[2], D[2], name_bytes;
-    DevArr<BgzfDir> dir[2];  // dst relative to the end of the carry
-    DevArr<int32_t> status;
+    std::vector<uint8_t> pend;  // text fed in pieces smaller than a sub-batch
+    DevArr<uint8_t> name_bytes;
     DevArr<SamResult> res;
     DevArr<sam::NameEntry> table;
     uint32_t table_mask = 0;
-    DevArr<uint32_t> count, kept_n, nl, rows;
+    DevArr<uint32_t> count, kept_n, nl;
     DevArr<u64> line_base, out_base;
-    // the sub-batch in flight (enqueued, not drained)
-    bool in_flight = false;
-    int cur = 0;         // D[cur] holds its text
-    uint64_t carry = 0;  // bytes of the unfinished line at D[cur]'s start (before the in-flight batch: after drain)
-    uint64_t n_D = 0;    // its text length
-    std::vector<BgzfDir> fl_dir;  // its members (file offsets for messages)
-    uint64_t fl_file_off = 0;
-    // results
-    std::vector<uint32_t> out_rows;
-    uint64_t lines = 0, header_lines = 0, unmapped = 0, no_seq = 0, kept = 0;
-    double ms[3] = {0, 0, 0};  // inflate (text: the copy behind the carry), lines, rows
-    int error = GFFX_OK;
-    std::string error_msg;
-
-    ~gffx_hip_sam() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (copy_stream) (void)hipStreamSynchronize(copy_stream);
-        for (int k = 0; k < 2; ++k) {
-            if (copied[k]) (void)hipEventDestroy(copied[k]);
-            if (stage[k]) (void)hipHostFree(stage[k]);
-            if (stage_dir[k]) (void)hipHostFree(stage_dir[k]);
-        }
-        if (res_host) (void)hipHostFree(res_host);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-        if (copy_stream) (void)hipStreamDestroy(copy_stream);
-    }
+    uint64_t lines = 0, header_lines = 0;
+    SourceStream s;  // (last, so destroyed first: its streams are idle before the arrays above are freed)
 };
 
 namespace {
-int sticky(gffx_hip_sam *h, int rc) {
-    if (rc != GFFX_OK && h->error == GFFX_OK) {
-        h->error = rc;
-        h->error_msg = g_last_error;
-    }
-    return rc;
-}
-
 // waits for the sub-batch in flight, takes its rows and moves its unfinished line to the other D buffer
 int drain(gffx_hip_sam *h) {
-    if (!h->in_flight) return GFFX_OK;
-    h->in_flight = false;
-    GFFX_HIP_TRY(hipStreamSynchronize(h->stream));
-    const SamResult r = *h->res_host;
-    if (r.bad_block != 0xFFFFFFFFu) {
-        int32_t st = 0;
-        GFFX_HIP_TRY(hipMemcpy(&st, h->status.p + r.bad_block, sizeof st, hipMemcpyDeviceToHost));
-        return fail(GFFX_E_INVALID, "BGZF block at file offset %llu: %s",
-                    (unsigned long long)(h->fl_file_off + h->fl_dir[r.bad_block].src), bgzf::status_name(st));
-    }
+    SourceStream &S = h->s;
+    if (!S.in_flight) return GFFX_OK;
+    if (int rc = S.drain_front(&S.result<SamResult>()->bad_block)) return rc;
+    const SamResult r = *S.result<SamResult>();
     h->header_lines += r.header_lines;
     if (r.bad != kNoBad)
         return fail(GFFX_E_INVALID, "line %llu: %s", (unsigned long long)(h->header_lines + h->lines + (r.bad >> 8) + 1),
                     sam::status_name((int)(r.bad & 0xFF)));
-    float t = 0;
-    for (int k = 0; k < 3; ++k)
-        if (hipEventElapsedTime(&t, h->ev[k], h->ev[k + 1]) == hipSuccess) h->ms[k] += t;
     h->lines += r.lines;
-    h->unmapped += r.unmapped;
-    h->no_seq += r.no_seq;
-    h->kept += r.kept;
-    if (r.kept) {
-        const size_t at = h->out_rows.size();
-        h->out_rows.resize(at + 3 * r.kept);
-        GFFX_HIP_TRY(hipMemcpy(h->out_rows.data() + at, h->rows.p, r.kept * 12, hipMemcpyDeviceToHost));
-    }
-    const uint64_t c = h->n_D - r.tail;
-    const int nxt = 1 - h->cur;
-    GFFX_HIP_TRY(h->D[nxt].ensure(c + h->out_cap));
-    if (c) GFFX_HIP_TRY(hipMemcpyAsync(h->D[nxt].p, h->D[h->cur].p + r.tail, c, hipMemcpyDeviceToDevice, h->stream));
-    h->cur = nxt;
-    h->carry = c;
-    return GFFX_OK;
-}
-
-// starts the copies of stage[k] (n_src bytes, nb members) to in[k] / dir[k] on the copy stream.  Their previous contents
-// belonged to the sub-batch before last, which has been drained.
-int stage_upload(gffx_hip_sam *h, int k, uint32_t nb, uint64_t n_src) {
-    GFFX_HIP_TRY(h->in[k].ensure(std::max<uint64_t>(n_src, 1)));
-    GFFX_HIP_TRY(hipMemcpyAsync(h->in[k].p, h->stage[k], n_src, hipMemcpyHostToDevice, h->copy_stream));
-    if (nb) {
-        GFFX_HIP_TRY(h->dir[k].ensure(nb));
-        GFFX_HIP_TRY(hipMemcpyAsync(h->dir[k].p, h->stage_dir[k], nb * sizeof(BgzfDir), hipMemcpyHostToDevice, h->copy_stream));
-    }
-    GFFX_HIP_TRY(hipEventRecord(h->copied[k], h->copy_stream));
-    return GFFX_OK;
+    return S.drain_back(r.tail, r.kept, r.unmapped, r.no_seq);
 }
 
 // enqueues the kernels on the carry followed by T new text bytes: in[k]'s n_src bytes themselves (nb == 0), or the output of
 // its nb members.  k < 0: the carry alone, as the file's last line (final_line).
 int enqueue(gffx_hip_sam *h, int k, uint32_t nb, uint64_t T, uint64_t file_off, int final_line) {
-    const uint64_t C = h->carry, N = C + T;
+    SourceStream &S = h->s;
+    const uint64_t C = S.carry, N = C + T;
     if (N > kMaxText) return fail(GFFX_E_INVALID, "line %llu: longer than 4 GiB", (unsigned long long)(h->header_lines + h->lines + 1));
     const uint32_t n_tiles = (uint32_t)std::max<uint64_t>((N + kTile - 1) / kTile, 1);
-    const u64 start = std::min<u64>(h->skip, N);
-    h->skip -= start;
-    GFFX_HIP_TRY(h->D[h->cur].ensure(std::max<uint64_t>(N, 1)));  // (no reallocation over a carry: drain sized it)
-    GFFX_HIP_TRY(h->status.ensure(std::max<uint32_t>(nb, 1)));
+    const u64 start = std::min<u64>(S.skip, N);
+    S.skip -= start;
+    GFFX_HIP_TRY(S.D[S.cur].ensure(std::max<uint64_t>(N, 1)));  // (no reallocation over a carry: drain sized it)
+    GFFX_HIP_TRY(S.status.ensure(std::max<uint32_t>(nb, 1)));
     GFFX_HIP_TRY(h->count.ensure(n_tiles));
     GFFX_HIP_TRY(h->kept_n.ensure(n_tiles));
     GFFX_HIP_TRY(h->line_base.ensure(n_tiles + 1));
     GFFX_HIP_TRY(h->out_base.ensure(n_tiles + 1));
     GFFX_HIP_TRY(h->nl.ensure(N + 1));             // every byte a '\n', and the line end at N
     const uint64_t rows_cap = std::max<uint64_t>(sam::max_kept_lines(N), 1);  // whatever the text: the shortest kept line
-    GFFX_HIP_TRY(h->rows.ensure(3 * rows_cap));
-    hipStream_t s = h->stream;
-    uint8_t *D = h->D[h->cur].p;
-    SamResult *res = h->res.p;
+    GFFX_HIP_TRY(S.rows.ensure(3 * rows_cap));
+    hipStream_t s = S.stream;
+    uint8_t *D = S.D[S.cur].p;
+    SamResult *res = h->res.p, *res_host = S.result<SamResult>();
     SamResult init{};
     init.bad = kNoBad;
     init.tail = start;
     init.bad_block = 0xFFFFFFFFu;
-    *h->res_host = init;
-    GFFX_HIP_TRY(hipMemcpyAsync(res, h->res_host, sizeof init, hipMemcpyHostToDevice, s));
-    if (k >= 0) GFFX_HIP_TRY(hipStreamWaitEvent(s, h->copied[k], 0));
-    GFFX_HIP_TRY(hipEventRecord(h->ev[0], s));
+    *res_host = init;
+    GFFX_HIP_TRY(hipMemcpyAsync(res, res_host, sizeof init, hipMemcpyHostToDevice, s));
+    if (k >= 0) GFFX_HIP_TRY(hipStreamWaitEvent(s, S.copied[k], 0));
+    GFFX_HIP_TRY(hipEventRecord(S.ev[0], s));
     if (k >= 0 && nb) {
-        launch_bgzf_inflate(s, h->in[k].p, h->dir[k].p, nb, D + C, h->status.p, &res->bad_block);
+        launch_bgzf_inflate(s, S.in[k].p, S.dir[k].p, nb, D + C, S.status.p, &res->bad_block);
         GFFX_HIP_TRY(hipGetLastError());
     } else if (k >= 0 && T) {
-        GFFX_HIP_TRY(hipMemcpyAsync(D + C, h->in[k].p, T, hipMemcpyDeviceToDevice, s));
+        GFFX_HIP_TRY(hipMemcpyAsync(D + C, S.in[k].p, T, hipMemcpyDeviceToDevice, s));
     }
-    GFFX_HIP_TRY(hipEventRecord(h->ev[1], s));
+    GFFX_HIP_TRY(hipEventRecord(S.ev[1], s));
     hipLaunchKernelGGL(k_sam_line_count, dim3(n_tiles), dim3(64), 0, s, D, N, start, n_tiles, final_line, h->count.p, res);
     launch_scan(s, h->count.p, n_tiles, h->line_base.p, &res->lines);
     hipLaunchKernelGGL(k_sam_line_list, dim3(n_tiles), dim3(64), 0, s, D, N, start, n_tiles, final_line, h->line_base.p, h->nl.p, res);
     GFFX_HIP_TRY(hipGetLastError());
-    GFFX_HIP_TRY(hipEventRecord(h->ev[2], s));
+    GFFX_HIP_TRY(hipEventRecord(S.ev[2], s));
     const sam::Names names{h->table.p, h->name_bytes.p, h->table_mask};
     hipLaunchKernelGGL(k_sam_rows<0>, dim3(n_tiles), dim3(64), 0, s, D, start, h->line_base.p, h->nl.p, names, h->kept_n.p, h->out_base.p,
-                       h->rows.p, rows_cap, res);
+                       S.rows.p, rows_cap, res);
     launch_scan(s, h->kept_n.p, n_tiles, h->out_base.p, &res->kept);
     hipLaunchKernelGGL(k_sam_rows<1>, dim3(n_tiles), dim3(64), 0, s, D, start, h->line_base.p, h->nl.p, names, h->kept_n.p, h->out_base.p,
-                       h->rows.p, rows_cap, res);
+                       S.rows.p, rows_cap, res);
     GFFX_HIP_TRY(hipGetLastError());
-    GFFX_HIP_TRY(hipEventRecord(h->ev[3], s));
-    GFFX_HIP_TRY(hipMemcpyAsync(h->res_host, res, sizeof(SamResult), hipMemcpyDeviceToHost, s));
-    h->in_flight = true;
-    h->n_D = N;
-    if (k >= 0 && nb) h->fl_dir.assign(h->stage_dir[k], h->stage_dir[k] + nb);
-    else h->fl_dir.clear();
-    h->fl_file_off = file_off;
-    return GFFX_OK;
-}
-
-// the next staging buffer, at least n bytes
-int next_stage(gffx_hip_sam *h, uint64_t n, int *k_out) {
-    const int k = h->cur_stage;
-    h->cur_stage ^= 1;
-    if (n > h->stage_cap[k]) {
-        if (h->stage[k]) (void)hipHostFree(h->stage[k]);
-        h->stage[k] = nullptr;
-        h->stage_cap[k] = 0;
-        if (hipHostMalloc((void **)&h->stage[k], n) != hipSuccess)
-            return fail(GFFX_E_OOM, "gffx_hip_sam_feed: pinned staging of %llu bytes", (unsigned long long)n);
-        h->stage_cap[k] = n;
-    }
-    *k_out = k;
+    GFFX_HIP_TRY(hipEventRecord(S.ev[3], s));
+    GFFX_HIP_TRY(hipMemcpyAsync(res_host, res, sizeof(SamResult), hipMemcpyDeviceToHost, s));
+    S.set_in_flight(N, k, nb, file_off);
     return GFFX_OK;
 }
 
 // one sub-batch of plain text (n <= chunk_bytes)
 int submit_text(gffx_hip_sam *h, const uint8_t *p, uint64_t n) {
+    SourceStream &S = h->s;
     int k = 0;
-    if (int rc = next_stage(h, n, &k)) return rc;
-    std::memcpy(h->stage[k], p, n);  // while the previous sub-batch runs
-    if (int rc = stage_upload(h, k, 0, n)) return rc;
+    if (int rc = S.next_stage(n, &k)) return rc;
+    std::memcpy(S.stage[k], p, n);  // while the previous sub-batch runs
+    if (int rc = S.stage_upload(k, 0, n)) return rc;
     if (int rc = drain(h)) return rc;
     return enqueue(h, k, 0, n, 0, 0);
 }
 
 int feed_text(gffx_hip_sam *h, const uint8_t *p, uint64_t n) {
-    const uint64_t chunk = h->chunk_bytes;
+    const uint64_t chunk = h->s.chunk_bytes;
     while (n) {
         if (h->pend.empty() && n >= chunk) {
             if (int rc = submit_text(h, p, chunk)) return rc;
@@ -404,36 +304,10 @@ int feed_text(gffx_hip_sam *h, const uint8_t *p, uint64_t n) {
 }
 
 int feed_bgzf(gffx_hip_sam *h, const uint8_t *bgzf, uint64_t n_bytes) {
-    std::vector<BgzfDir> all;
-    if (int rc = walk_members(bgzf, n_bytes, h->file_off, &all)) return rc;
-    // sub-batches: at most chunk_bytes compressed, out_cap decompressed, kMaxBlocksPerBatch members (at least one member)
-    size_t i = 0;
-    while (i < all.size()) {
-        size_t j = i;
-        uint64_t src = 0, dst = 0;
-        while (j < all.size() && (j == i || (src + all[j].len <= h->chunk_bytes && dst + all[j].isize <= h->out_cap &&
-                                             j - i < kMaxBlocksPerBatch))) {
-            src += all[j].len;
-            dst += all[j].isize;
-            ++j;
-        }
-        int k = 0;
-        if (int rc = next_stage(h, src, &k)) return rc;
-        if (!h->stage_dir[k] && hipHostMalloc((void **)&h->stage_dir[k], kMaxBlocksPerBatch * sizeof(BgzfDir)) != hipSuccess)
-            return fail(GFFX_E_OOM, "gffx_hip_sam_feed: pinned directory");
-        std::memcpy(h->stage[k], bgzf + all[i].src, src);
-        for (size_t x = i; x < j; ++x) {
-            BgzfDir d = all[x];
-            d.src -= all[i].src;
-            d.dst -= all[i].dst;
-            h->stage_dir[k][x - i] = d;
-        }
-        if (int rc = stage_upload(h, k, (uint32_t)(j - i), src)) return rc;
+    return h->s.feed_members(bgzf, n_bytes, [h](int k, uint32_t nb, uint64_t T, uint64_t file_off) {
         if (int rc = drain(h)) return rc;
-        if (int rc = enqueue(h, k, (uint32_t)(j - i), dst, h->file_off + all[i].src, 0)) return rc;
-        i = j;
-    }
-    return GFFX_OK;
+        return enqueue(h, k, nb, T, file_off, 0);
+    });
 }
 }  // namespace
 
@@ -456,17 +330,12 @@ extern "C" int gffx_hip_sam_create(int device, uint32_t n_ref, const char *names
     GFFX_HIP_TRY(hipSetDevice(device));
     std::unique_ptr<gffx_hip_sam> h(new (std::nothrow) gffx_hip_sam);
     if (!h) return fail(GFFX_E_OOM, "gffx_hip_sam_create: out of host memory");
-    h->device = device;
     h->bgzf = bgzf != 0;
-    h->skip = header_bytes;
-    h->chunk_bytes = std::max<uint64_t>(chunk_bytes ? chunk_bytes : (64ull << 20), 1);
-    h->chunk_bytes = std::min<uint64_t>(h->chunk_bytes, 1ull << 30);
-    h->out_cap = h->bgzf ? std::min<uint64_t>(std::max<uint64_t>(4 * h->chunk_bytes, 1ull << 20), 1ull << 30) : h->chunk_bytes;
-    GFFX_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    GFFX_HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    for (hipEvent_t &e : h->ev) GFFX_HIP_TRY(hipEventCreate(&e));
-    for (hipEvent_t &e : h->copied) GFFX_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    GFFX_HIP_TRY(hipHostMalloc((void **)&h->res_host, sizeof(SamResult)));
+    h->s.skip = header_bytes;
+    h->s.chunk_bytes = std::max<uint64_t>(chunk_bytes ? chunk_bytes : (64ull << 20), 1);
+    h->s.chunk_bytes = std::min<uint64_t>(h->s.chunk_bytes, 1ull << 30);
+    h->s.out_cap = h->bgzf ? SourceStream::bgzf_out_cap(h->s.chunk_bytes) : h->s.chunk_bytes;
+    if (int rc = h->s.init(device, "gffx_hip_sam_feed", sizeof(SamResult))) return rc;
     GFFX_HIP_TRY(h->res.ensure(1));
     GFFX_HIP_TRY(h->table.ensure(table.size()));
     GFFX_HIP_TRY(hipMemcpy(h->table.p, table.data(), table.size() * sizeof(sam::NameEntry), hipMemcpyHostToDevice));
@@ -479,57 +348,57 @@ extern "C" int gffx_hip_sam_create(int device, uint32_t n_ref, const char *names
 
 extern "C" int gffx_hip_sam_feed(gffx_hip_sam *h, const uint8_t *bytes, uint64_t n_bytes) {
     if (!h) return fail(GFFX_E_INVALID, "gffx_hip_sam_feed: NULL handle");
-    if (h->error) return fail(h->error, "%s", h->error_msg.c_str());
+    SourceStream &S = h->s;
+    if (S.error) return fail(S.error, "%s", S.error_msg.c_str());
     if (n_bytes && !bytes) return fail(GFFX_E_INVALID, "gffx_hip_sam_feed: NULL input");
-    GFFX_HIP_TRY(hipSetDevice(h->device));
-    if (int rc = h->bgzf ? feed_bgzf(h, bytes, n_bytes) : feed_text(h, bytes, n_bytes)) return sticky(h, rc);
-    h->file_off += n_bytes;
+    GFFX_HIP_TRY(hipSetDevice(S.device));
+    if (int rc = h->bgzf ? feed_bgzf(h, bytes, n_bytes) : feed_text(h, bytes, n_bytes)) return S.sticky(rc);
+    S.file_off += n_bytes;
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_sam_finish(gffx_hip_sam *h) {
     if (!h) return fail(GFFX_E_INVALID, "gffx_hip_sam_finish: NULL handle");
-    if (h->error) return fail(h->error, "%s", h->error_msg.c_str());
-    GFFX_HIP_TRY(hipSetDevice(h->device));
+    SourceStream &S = h->s;
+    if (S.error) return fail(S.error, "%s", S.error_msg.c_str());
+    GFFX_HIP_TRY(hipSetDevice(S.device));
     if (!h->pend.empty()) {
-        if (int rc = submit_text(h, h->pend.data(), h->pend.size())) return sticky(h, rc);
+        if (int rc = submit_text(h, h->pend.data(), h->pend.size())) return S.sticky(rc);
         h->pend.clear();
     }
-    if (int rc = drain(h)) return sticky(h, rc);
-    if (h->skip)
-        return sticky(h, fail(GFFX_E_INVALID, "the stream ends %llu bytes before the end of its header", (unsigned long long)h->skip));
-    if (h->carry) {  // a last line without '\n'
-        if (int rc = enqueue(h, -1, 0, 0, h->file_off, 1)) return sticky(h, rc);
-        if (int rc = drain(h)) return sticky(h, rc);
-        h->carry = 0;
+    if (int rc = drain(h)) return S.sticky(rc);
+    if (S.skip)
+        return S.sticky(fail(GFFX_E_INVALID, "the stream ends %llu bytes before the end of its header", (unsigned long long)S.skip));
+    if (S.carry) {  // a last line without '\n'
+        if (int rc = enqueue(h, -1, 0, 0, S.file_off, 1)) return S.sticky(rc);
+        if (int rc = drain(h)) return S.sticky(rc);
+        S.carry = 0;
     }
     return GFFX_OK;
 }
 
-extern "C" uint64_t gffx_hip_sam_rows(const gffx_hip_sam *h) { return h ? h->out_rows.size() / 3 : 0; }
+extern "C" uint64_t gffx_hip_sam_rows(const gffx_hip_sam *h) { return h ? h->s.n_rows() : 0; }
 
 extern "C" int gffx_hip_sam_counts(const gffx_hip_sam *h, uint64_t *lines, uint64_t *unmapped, uint64_t *no_seq, uint64_t *kept) {
     if (!h) return fail(GFFX_E_INVALID, "gffx_hip_sam_counts: NULL handle");
     if (lines) *lines = h->lines;
-    if (unmapped) *unmapped = h->unmapped;
-    if (no_seq) *no_seq = h->no_seq;
-    if (kept) *kept = h->kept;
+    if (unmapped) *unmapped = h->s.unmapped;
+    if (no_seq) *no_seq = h->s.no_seq;
+    if (kept) *kept = h->s.kept;
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_sam_stage_ms(const gffx_hip_sam *h, double *inflate, double *lines, double *rows) {
     if (!h) return fail(GFFX_E_INVALID, "gffx_hip_sam_stage_ms: NULL handle");
-    if (inflate) *inflate = h->ms[0];
-    if (lines) *lines = h->ms[1];
-    if (rows) *rows = h->ms[2];
+    h->s.stage_ms(inflate, lines, rows);
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_sam_copy_rows(gffx_hip_sam *h, uint32_t *rows) {
     if (!h) return fail(GFFX_E_INVALID, "gffx_hip_sam_copy_rows: NULL handle");
-    if (h->in_flight || !h->pend.empty()) return fail(GFFX_E_STATE, "gffx_hip_sam_copy_rows: call gffx_hip_sam_finish first");
-    if (!h->out_rows.empty() && !rows) return fail(GFFX_E_INVALID, "gffx_hip_sam_copy_rows: rows is NULL");
-    if (!h->out_rows.empty()) std::memcpy(rows, h->out_rows.data(), h->out_rows.size() * sizeof(uint32_t));
+    if (h->s.in_flight || !h->pend.empty()) return fail(GFFX_E_STATE, "gffx_hip_sam_copy_rows: call gffx_hip_sam_finish first");
+    if (h->s.n_rows() && !rows) return fail(GFFX_E_INVALID, "gffx_hip_sam_copy_rows: rows is NULL");
+    h->s.copy_rows(rows);
     return GFFX_OK;
 }
 

@@ -77,12 +77,8 @@ void run(const CoverageArgs &args) {
     TreeIndexData index_data = TreeIndexData::load_tree_index(args.input);  // :511
     const depth::SourceKind kind = depth::source_kind(args.source);  // coverage.rs:520-541
     const size_t threads = capped_threads(args.threads);
-    // the kept rows as flat (seqid number, start, end) words, one vector per parsed piece (file order); part_row[p] = rows before piece p
-    const std::vector<std::vector<uint32_t>> part =
-        depth::read_source_rows(kind, args.source, index_data.seqid_to_num, threads, args.device, verbose, warm);
-    std::vector<size_t> part_row(part.size() + 1, 0);
-    for (size_t p = 0; p < part.size(); ++p) part_row[p + 1] = part_row[p] + part[p].size() / 3;
-    const size_t n_regions = part_row.back();
+    const depth::SourceRows src = depth::read_source_rows(kind, args.source, index_data.seqid_to_num, threads, args.device, verbose, warm);
+    const size_t n_regions = src.n_rows;
     if (verbose) std::fprintf(stderr, "[INFO] %zu %s rows kept\n", n_regions, depth::source_label(kind));
     timer.lap(depth::source_lap(kind, true));
 
@@ -170,8 +166,24 @@ void run(const CoverageArgs &args) {
             size_t rows_in[2] = {0, 0};
             std::vector<uint32_t> counts, fids;
             std::vector<uint64_t> offsets;
-            // Batch i goes through staging buffer / batches i & 1 (depth.cpp).  finish(k): the passes over slot k are through; the
-            // rows paired with a root of the side index are gathered from staging buffer k, which still holds the batch.
+            // submit(k, n): the passes over the n rows resident in slot k
+            auto submit = [&](int k, size_t n) {
+                if (gffx_hip_batch_set_regions_store(P.b[k].get(), P.store.get(), k, 0, n) != GFFX_OK) hip_fail("set_regions_store");
+                const uint32_t flags = static_cast<uint32_t>(GFFX_OUT_ROOT_BITMAP) | static_cast<uint32_t>(GFFX_OUT_NO_COUNTS) |
+                                       (used[k] ? static_cast<uint32_t>(GFFX_OUT_BITMAP_KEEP) : 0u);  // (the bitmap accumulates across batches)
+                if (gffx_hip_batch_run(P.b[k].get(), GFFX_MODE_OVERLAP, 0, flags, GFFX_STRATEGY_AUTO) != GFFX_OK) hip_fail("gffx_hip_batch_run");
+                if (have_side) {
+                    if (gffx_hip_batch_set_regions_store(P.c[k].get(), P.store.get(), k, 0, n) != GFFX_OK) hip_fail("set_regions_store");
+                    if (gffx_hip_batch_run(P.c[k].get(), GFFX_MODE_OVERLAP, 0, GFFX_OUT_FIDS | GFFX_OUT_OFFSETS, GFFX_STRATEGY_AUTO) != GFFX_OK)
+                        hip_fail("gffx_hip_batch_run");
+                }
+                used[k] = true;
+                rows_in[k] = n;
+                // the same resident rows into the union (on the union's own stream, beside Join A; returns when they are read)
+                if (gffx_hip_union_add_store(P.u.get(), P.store.get(), k, 0, n) != GFFX_OK) hip_fail("gffx_hip_union_add_store");
+            };
+            // finish(k): the passes over slot k are through; the rows paired with a root of the side index are gathered from
+            // staging buffer k, which still holds the batch.
             auto finish = [&](int k) {
                 if (gffx_hip_batch_wait(P.b[k].get()) != GFFX_OK) hip_fail("query_features");
                 if (!have_side) return;
@@ -194,45 +206,7 @@ void run(const CoverageArgs &args) {
                 P.side_pairs += total;
             };
             const size_t fill_threads = std::max<size_t>(1, std::min<size_t>(threads / D, 8));
-            size_t i = 0;
-            for (size_t a = d * kBatch; a < n_regions; a += D * kBatch, ++i) {
-                const int k = static_cast<int>(i & 1);
-                const size_t n = std::min(kBatch, n_regions - a);
-                if (gffx_hip_regions_wait_staging(P.store.get(), k) != GFFX_OK) hip_fail("wait_staging");
-                uint32_t *stage = gffx_hip_regions_staging(P.store.get(), k);
-                // rows [a, a + n) of the file: the tails / heads of the pieces they lie in, copied by a few threads
-                struct Move {
-                    const uint32_t *src;
-                    size_t at, rows;
-                };
-                std::vector<Move> moves;
-                size_t p = static_cast<size_t>(std::upper_bound(part_row.begin(), part_row.end(), a) - part_row.begin()) - 1;
-                for (size_t done = 0; done < n; ++p) {
-                    const size_t from = a + done - part_row[p], take = std::min(n - done, part_row[p + 1] - (a + done));
-                    for (size_t x = 0; x < take; x += 1u << 18)
-                        moves.push_back({part[p].data() + 3 * (from + x), done + x, std::min<size_t>(take - x, 1u << 18)});
-                    done += take;
-                }
-                parallel_for(moves.size(), fill_threads,
-                             [&](size_t m) { std::memcpy(stage + 3 * moves[m].at, moves[m].src, moves[m].rows * 12); });
-                if (gffx_hip_regions_append(P.store.get(), k, n) != GFFX_OK) hip_fail("regions_append");  // the batch's ONE upload
-                if (gffx_hip_batch_set_regions_store(P.b[k].get(), P.store.get(), k, 0, n) != GFFX_OK) hip_fail("set_regions_store");
-                const uint32_t flags = static_cast<uint32_t>(GFFX_OUT_ROOT_BITMAP) | static_cast<uint32_t>(GFFX_OUT_NO_COUNTS) |
-                                       (used[k] ? static_cast<uint32_t>(GFFX_OUT_BITMAP_KEEP) : 0u);  // (the bitmap accumulates across batches)
-                if (gffx_hip_batch_run(P.b[k].get(), GFFX_MODE_OVERLAP, 0, flags, GFFX_STRATEGY_AUTO) != GFFX_OK) hip_fail("gffx_hip_batch_run");
-                if (have_side) {
-                    if (gffx_hip_batch_set_regions_store(P.c[k].get(), P.store.get(), k, 0, n) != GFFX_OK) hip_fail("set_regions_store");
-                    if (gffx_hip_batch_run(P.c[k].get(), GFFX_MODE_OVERLAP, 0, GFFX_OUT_FIDS | GFFX_OUT_OFFSETS, GFFX_STRATEGY_AUTO) != GFFX_OK)
-                        hip_fail("gffx_hip_batch_run");
-                }
-                used[k] = true;
-                rows_in[k] = n;
-                // the same resident rows into the union (on the union's own stream, beside Join A; returns when they are read)
-                if (gffx_hip_union_add_store(P.u.get(), P.store.get(), k, 0, n) != GFFX_OK) hip_fail("gffx_hip_union_add_store");
-                if (i > 0) finish(1 - k);
-                P.rows += n;
-            }
-            if (i > 0) finish(static_cast<int>((i - 1) & 1));
+            P.rows = depth::run_row_batches(src, P.store.get(), d, D, kBatch, fill_threads, submit, finish);
             std::vector<uint64_t> tmp(n_words, 0);
             for (int k = 0; k < 2; ++k) {
                 if (!used[k]) continue;

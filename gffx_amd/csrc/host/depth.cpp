@@ -182,14 +182,35 @@ SourceKind source_kind(const std::string &path) {
     return ext == "bam" ? SourceKind::Bam : ext == "sam" ? SourceKind::Sam : SourceKind::Bed;
 }
 
-std::vector<std::vector<uint32_t>> read_source_rows(SourceKind kind, const std::string &path,
-                                                    const std::unordered_map<std::string, uint32_t> &seqid_to_num, size_t threads,
-                                                    int device, bool verbose, DeviceWarmup &warm) {
-    if (kind == SourceKind::Bed) return parse_bed_rows_flat(path, seqid_to_num, threads);  // depth.rs:450-495, coverage.rs:230-256
-    warm.wait();  // depth.rs:297-372, coverage.rs:125-168: the same (chr, start, end) rows, from BAM records or SAM lines
-    std::vector<std::vector<uint32_t>> part;
-    part.push_back(kind == SourceKind::Sam ? sam::read_rows(path, seqid_to_num, device, verbose) : bam::read_rows(path, seqid_to_num, device, verbose));
-    return part;
+SourceRows read_source_rows(SourceKind kind, const std::string &path, const std::unordered_map<std::string, uint32_t> &seqid_to_num,
+                            size_t threads, int device, bool verbose, DeviceWarmup &warm) {
+    SourceRows r;
+    if (kind == SourceKind::Bed) {
+        r.part = parse_bed_rows_flat(path, seqid_to_num, threads);  // depth.rs:450-495, coverage.rs:230-256
+    } else {
+        warm.wait();  // depth.rs:297-372, coverage.rs:125-168: the same (chr, start, end) rows, from BAM records or SAM lines
+        r.part.push_back(kind == SourceKind::Sam ? sam::read_rows(path, seqid_to_num, device, verbose) : bam::read_rows(path, seqid_to_num, device, verbose));
+    }
+    r.part_row.assign(r.part.size() + 1, 0);
+    for (size_t p = 0; p < r.part.size(); ++p) r.part_row[p + 1] = r.part_row[p] + r.part[p].size() / 3;
+    r.n_rows = r.part_row.back();
+    return r;
+}
+
+void SourceRows::fill(uint32_t *stage, size_t a, size_t n, size_t threads) const {
+    struct Move {
+        const uint32_t *src;
+        size_t at, rows;
+    };
+    std::vector<Move> moves;
+    size_t p = static_cast<size_t>(std::upper_bound(part_row.begin(), part_row.end(), a) - part_row.begin()) - 1;
+    for (size_t done = 0; done < n; ++p) {
+        const size_t from = a + done - part_row[p], take = std::min(n - done, part_row[p + 1] - (a + done));
+        for (size_t x = 0; x < take; x += 1u << 18)  // (256 K-row slices: pieces are much larger than a fair share)
+            moves.push_back({part[p].data() + 3 * (from + x), done + x, std::min<size_t>(take - x, 1u << 18)});
+        done += take;
+    }
+    parallel_for(moves.size(), threads, [&](size_t m) { std::memcpy(stage + 3 * moves[m].at, moves[m].src, moves[m].rows * 12); });
 }
 
 void run(const DepthArgs &args) {
@@ -202,12 +223,8 @@ void run(const DepthArgs &args) {
     const SourceKind kind = source_kind(args.source);  // depth.rs:590-601
     timer.lap("Loading index");
     const size_t threads = capped_threads(args.threads);
-    // the kept rows as flat triples, one vector per parsed piece (file order); part_row[p] = rows before piece p
-    const std::vector<std::vector<uint32_t>> part =
-        read_source_rows(kind, args.source, index_data.seqid_to_num, threads, args.device, verbose, warm);
-    std::vector<size_t> part_row(part.size() + 1, 0);
-    for (size_t p = 0; p < part.size(); ++p) part_row[p + 1] = part_row[p] + part[p].size() / 3;
-    const size_t n_rows = part_row.back();
+    const SourceRows src = read_source_rows(kind, args.source, index_data.seqid_to_num, threads, args.device, verbose, warm);
+    const size_t n_rows = src.n_rows;
     if (verbose) std::fprintf(stderr, "[INFO] %zu %s rows kept\n", n_rows, source_label(kind));
     timer.lap(source_lap(kind, false));
 
@@ -248,43 +265,17 @@ void run(const DepthArgs &args) {
             if (gffx_hip_regions_create(devs[d], 0, cap, 0, OutPtr(P.store)) != GFFX_OK) hip_fail("gffx_hip_regions_create");
             for (int k = 0; k < 2; ++k)
                 if (gffx_hip_batch_create(ix, cap, OutPtr(P.b[k])) != GFFX_OK) hip_fail("gffx_hip_batch_create");
-            // Batch i goes through staging buffer / batch i & 1: while its rows cross PCIe and Join A runs on them, the host
-            // waits for batch i - 1 and adds its depth, then fills the other staging buffer.  (One batch at a time was 19 ms per
-            // 4 M rows, nearly all of it the flat copy and the pageable upload.)
-            auto finish = [&](int k) {
+            auto submit = [&](int k, size_t n) {
+                if (gffx_hip_batch_set_regions_store(P.b[k].get(), P.store.get(), k, 0, n) != GFFX_OK) hip_fail("set_regions_store");
+                if (gffx_hip_batch_run(P.b[k].get(), GFFX_MODE_OVERLAP, 0, GFFX_OUT_FIDS | GFFX_OUT_OFFSETS, GFFX_STRATEGY_AUTO) != GFFX_OK)
+                    hip_fail("gffx_hip_batch_run");
+            };
+            auto finish = [&](int k) {  // the host waits for the batch in slot k and adds its depth
                 if (gffx_hip_batch_wait(P.b[k].get()) != GFFX_OK) hip_fail("query_features");
                 if (gffx_hip_depth_accumulate(P.dt.get(), P.b[k].get()) != GFFX_OK) hip_fail("gffx_hip_depth_accumulate");
             };
             const size_t fill_threads = std::max<size_t>(1, std::min<size_t>(threads / D, 8));
-            size_t i = 0;
-            for (size_t a = d * kBatch; a < n_rows; a += D * kBatch, ++i) {
-                const int k = static_cast<int>(i & 1);
-                const size_t n = std::min(kBatch, n_rows - a);
-                if (gffx_hip_regions_wait_staging(P.store.get(), k) != GFFX_OK) hip_fail("wait_staging");
-                uint32_t *stage = gffx_hip_regions_staging(P.store.get(), k);
-                // rows [a, a + n) of the file: the tails / heads of the pieces they lie in, copied by a few threads
-                struct Move {
-                    const uint32_t *src;
-                    size_t at, rows;
-                };
-                std::vector<Move> moves;
-                size_t p = static_cast<size_t>(std::upper_bound(part_row.begin(), part_row.end(), a) - part_row.begin()) - 1;
-                for (size_t done = 0; done < n; ++p) {
-                    const size_t from = a + done - part_row[p], take = std::min(n - done, part_row[p + 1] - (a + done));
-                    for (size_t x = 0; x < take; x += 1u << 18)  // (256 K-row slices: pieces are much larger than a fair share)
-                        moves.push_back({part[p].data() + 3 * (from + x), done + x, std::min<size_t>(take - x, 1u << 18)});
-                    done += take;
-                }
-                parallel_for(moves.size(), fill_threads,
-                             [&](size_t m) { std::memcpy(stage + 3 * moves[m].at, moves[m].src, moves[m].rows * 12); });
-                if (gffx_hip_regions_append(P.store.get(), k, n) != GFFX_OK) hip_fail("regions_append");
-                if (gffx_hip_batch_set_regions_store(P.b[k].get(), P.store.get(), k, 0, n) != GFFX_OK) hip_fail("set_regions_store");
-                if (gffx_hip_batch_run(P.b[k].get(), GFFX_MODE_OVERLAP, 0, GFFX_OUT_FIDS | GFFX_OUT_OFFSETS, GFFX_STRATEGY_AUTO) != GFFX_OK)
-                    hip_fail("gffx_hip_batch_run");
-                if (i > 0) finish(1 - k);
-                P.rows += n;
-            }
-            if (i > 0) finish(static_cast<int>((i - 1) & 1));
+            P.rows = run_row_batches(src, P.store.get(), d, D, kBatch, fill_threads, submit, finish);
             P.depth.assign(std::max<size_t>(n_groups, 1), 0);
             P.mn.assign(std::max<size_t>(n_groups, 1), 0xFFFFFFFFu);
             P.mx.assign(std::max<size_t>(n_groups, 1), 0);

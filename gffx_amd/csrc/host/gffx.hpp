@@ -341,10 +341,39 @@ inline const char *source_lap(SourceKind k, bool with_index) {
     }
 }
 SourceKind source_kind(const std::string &path);  // depth.rs:590-601 / coverage.rs:520-541: by the extension, any letter case; others: Error
-// the kept rows of a .bed (on `threads` host threads), a .bam or a .sam (read on `device` once `warm` is through), flat, in pieces, in file order
-std::vector<std::vector<uint32_t>> read_source_rows(SourceKind kind, const std::string &path,
-                                                    const std::unordered_map<std::string, uint32_t> &seqid_to_num, size_t threads,
-                                                    int device, bool verbose, DeviceWarmup &warm);
+// the kept rows of a source as flat (seqid number, start, end) words, one vector per parsed piece, in file order
+struct SourceRows {
+    std::vector<std::vector<uint32_t>> part;
+    std::vector<size_t> part_row;  // part_row[p] = rows before piece p
+    size_t n_rows = 0;
+    // rows [a, a + n) of the file into stage: the tails / heads of the pieces they lie in, copied by up to `threads` threads
+    void fill(uint32_t *stage, size_t a, size_t n, size_t threads) const;
+};
+// ... of a .bed (on `threads` host threads), a .bam or a .sam (read on `device` once `warm` is through)
+SourceRows read_source_rows(SourceKind kind, const std::string &path, const std::unordered_map<std::string, uint32_t> &seqid_to_num,
+                            size_t threads, int device, bool verbose, DeviceWarmup &warm);
+// Device d's share of the rows (of D devices, round robin in batches of kBatch) through its region store.  Batch i goes
+// through staging buffer / slot k = i & 1: filled and uploaded, then submit(k, n) starts the passes over its n rows; while
+// they run, finish(1 - k) takes the results of batch i - 1, and the host goes on to fill the other staging buffer.  (One batch
+// at a time was 19 ms per 4 M rows, nearly all of it the flat copy and the pageable upload.)  Returns the rows that went through.
+template <class Submit, class Finish>
+uint64_t run_row_batches(const SourceRows &rows, gffx_hip_regions *store, size_t d, size_t D, size_t kBatch, size_t fill_threads,
+                         Submit &&submit, Finish &&finish) {
+    uint64_t through = 0;
+    size_t i = 0;
+    for (size_t a = d * kBatch; a < rows.n_rows; a += D * kBatch, ++i) {
+        const int k = static_cast<int>(i & 1);
+        const size_t n = std::min(kBatch, rows.n_rows - a);
+        if (gffx_hip_regions_wait_staging(store, k) != GFFX_OK) hip_fail("wait_staging");
+        rows.fill(gffx_hip_regions_staging(store, k), a, n, fill_threads);
+        if (gffx_hip_regions_append(store, k, n) != GFFX_OK) hip_fail("regions_append");  // the batch's ONE upload
+        submit(k, n);
+        if (i > 0) finish(1 - k);
+        through += n;
+    }
+    if (i > 0) finish(static_cast<int>((i - 1) & 1));
+    return through;
+}
 struct BlockTable {  // the device line table (include/gffx_hip.h "gffx depth") + what names the groups
     std::vector<uint64_t> block_line_off{0};
     std::vector<uint32_t> line_start, line_end, line_group, block_of_fid;

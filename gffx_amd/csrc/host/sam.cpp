@@ -5,40 +5,29 @@
 // and the text -- or the BGZF members, whose inflated bytes never leave the device -- goes to the engine in chunks
 // (gffx_hip_sam_*, device/sam.hip), which finds the lines, reads FLAG, RNAME, POS and CIGAR and hands back the kept
 // (seqid number, start, end) rows in file order: what the BED path of both commands takes, unchanged.
+// The BGZF front end (directory, EOF marker, header inflate, chunked feed) is bgzf_file.hpp's and the read-back of times, rows
+// and tallies source_read.hpp's, both shared with bam.cpp; the sniffing, the header's names and the messages are this file's.
 // Every failure message ends in "(read without htslib)".
-#include <cstdlib>
 #include <cstring>
-#include <memory>
 
 #include "../device/sam_core.hpp"
-#include "gffx.hpp"
+#include "source_read.hpp"
 
 namespace gffx::sam {
 
 namespace {
 const char *const kNoHtslib = " (read without htslib)";
-// the 28-byte empty member that ends a BGZF file (SAM spec §4.1.2)
-const uint8_t kEof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
-uint64_t chunk_bytes_from_env() {
-    const char *e = std::getenv("GFFX_SAM_CHUNK_BYTES");
-    if (e && *e) {
-        char *end = nullptr;
-        const unsigned long long v = std::strtoull(e, &end, 10);
-        if (end && !*end && v > 0) return v;
-    }
-    return 0;  // the engine's default
-}
+const source::Reader<gffx_hip_sam> kReader = {gffx_hip_sam_stage_ms, gffx_hip_sam_rows, gffx_hip_sam_copy_rows, gffx_hip_sam_counts,
+                                              {"SAM inflate (device)", "SAM line scan (device)", "SAM rows (device)",
+                                               "SAM chunks in all (staging, device, rows back)", "SAM rows copy"}};
 }  // namespace
 
 std::vector<uint32_t> read_rows(const std::string &path, const std::unordered_map<std::string, uint32_t> &seqid_to_num, int device,
                                 bool verbose) {
-    using clock = std::chrono::steady_clock;
-    auto ms_since = [](clock::time_point t) { return std::chrono::duration<double, std::milli>(clock::now() - t).count(); };
-    auto timer = [&](const char *what, double ms) {
-        if (verbose) std::fprintf(stderr, "[TIMER] [run] %s took %.3f ms\n", what, ms);
-        g_run_stats.stage(what, ms);
-    };
+    using source::clock;
+    using source::ms_since;
+    const source::Timer timer{verbose};
     const std::string who = "SAM file \"" + path + "\"";
     std::vector<uint64_t> member_off;  // BGZF: member i = [member_off[i], member_off[i + 1])
     std::vector<uint8_t> head;         // BGZF: the inflated text up to the header's end
@@ -53,41 +42,32 @@ std::vector<uint32_t> read_rows(const std::string &path, const std::unordered_ma
         auto t = clock::now();
         if (n >= 2 && p[0] == 0x1f && p[1] == 0x8b) {
             // gzip: BGZF members (the BC extra field) or refused
-            for (uint64_t at = 0; at < n;) {
-                uint32_t total = 0, hdr = 0;
-                const int st = bgzf::member_header(p + at, n - at, &total, &hdr);
-                if (st == bgzf::kHeader && at == 0)
+            auto offset_error = [&](uint64_t off, int st) {
+                return Error(who + ": BGZF block at file offset " + std::to_string(off) + ": " + bgzf::status_name(st) + kNoHtslib);
+            };
+            uint64_t bad_off = 0;
+            if (const int st = bgzf_file::member_directory(p, n, &member_off, &bad_off)) {
+                if (st == bgzf::kHeader && bad_off == 0)
                     throw Error(who + " is gzip-compressed but not BGZF (no BC extra field): recompress it with bgzip, or decompress it" + kNoHtslib);
-                if (st != bgzf::kOk)
-                    throw Error(who + ": BGZF block at file offset " + std::to_string(at) + ": " + bgzf::status_name(st) + kNoHtslib);
-                member_off.push_back(at);
-                at += total;
+                throw offset_error(bad_off, st);
             }
-            member_off.push_back(n);
             bgzf_text = true;
             // the header, inflated on the host (it may span several members; lines may begin in its last one)
-            std::unique_ptr<bgzf::Scratch> scratch(new bgzf::Scratch);
-            uint32_t crc_table[256];
-            for (uint32_t i = 0; i < 256; ++i) crc_table[i] = bgzf::crc_table_entry(i);
+            bool first = true, holds_bam = false;
+            auto complete = [&](const std::vector<uint8_t> &h) {
+                if (first && h.size() >= 4 && std::memcmp(h.data(), "BAM\1", 4) == 0) holds_bam = true;
+                first = false;
+                return holds_bam ? (int)bgzf::kOk : sam_header_scan(h.data(), h.size(), &header_bytes);
+            };
             int hst = bgzf::kTruncated;
-            for (size_t m = 0; m + 1 < member_off.size() && hst == bgzf::kTruncated; ++m) {
-                const size_t at = head.size();
-                head.resize(at + bgzf::kMaxIsize);
-                uint32_t total = 0, isize = 0;
-                const int st = bgzf::member_inflate(p + member_off[m], member_off[m + 1] - member_off[m], head.data() + at, bgzf::kMaxIsize,
-                                                    &total, &isize, scratch.get(), crc_table);
-                if (st != bgzf::kOk)
-                    throw Error(who + ": BGZF block at file offset " + std::to_string(member_off[m]) + ": " + bgzf::status_name(st) + kNoHtslib);
-                head.resize(at + isize);
-                if (m == 0 && head.size() >= 4 && std::memcmp(head.data(), "BAM\1", 4) == 0) {
-                    if (verbose) std::fprintf(stderr, "[INFO] \"%s\" holds BAM: read as BAM\n", path.c_str());
-                    return bam::read_rows(path, seqid_to_num, device, verbose);
-                }
-                hst = sam_header_scan(head.data(), head.size(), &header_bytes);
+            if (const int st = bgzf_file::inflate_header(p, member_off, &head, complete, &hst, &bad_off)) throw offset_error(bad_off, st);
+            if (holds_bam) {
+                if (verbose) std::fprintf(stderr, "[INFO] \"%s\" holds BAM: read as BAM\n", path.c_str());
+                return bam::read_rows(path, seqid_to_num, device, verbose);
             }
             if (hst == bgzf::kTruncated) header_bytes = head.size();  // all header
             head.resize(header_bytes);
-            if (n < 28 || std::memcmp(p + n - 28, kEof, 28) != 0)
+            if (!bgzf_file::has_eof_marker(p, n))
                 std::fprintf(stderr, "[WARN] SAM file \"%s\" has no BGZF EOF marker: it may be truncated\n", path.c_str());
         } else {
             if (sam_header_scan(p, n, &header_bytes) == bgzf::kTruncated) header_bytes = n;  // all header
@@ -109,7 +89,7 @@ std::vector<uint32_t> read_rows(const std::string &path, const std::unordered_ma
         timer("SAM header", ms_since(t));
 
         t = clock::now();
-        const uint64_t chunk = chunk_bytes_from_env();
+        const uint64_t chunk = source::chunk_bytes_from_env("GFFX_SAM_CHUNK_BYTES", 0);  // (0: the engine's default)
         Handle<gffx_hip_sam, gffx_hip_sam_destroy> owner;
         auto engine_error = [&]() { return Error(who + ": " + gffx_hip_last_error() + kNoHtslib); };
         const int rc = gffx_hip_sam_create(device, (uint32_t)sq.size(), names.data(), name_off.data(), ref_seq.data(), header_bytes, chunk,
@@ -117,38 +97,17 @@ std::vector<uint32_t> read_rows(const std::string &path, const std::unordered_ma
         if (rc == GFFX_E_INVALID) throw engine_error();  // the header's names: a duplicate @SQ SN, checked before any device call
         if (rc != GFFX_OK) hip_fail("gffx_hip_sam_create");
         gffx_hip_sam *h = owner.get();
-        if (bgzf_text) {
-            const uint64_t per = chunk ? chunk : (64ull << 20);
-            const size_t n_members = member_off.size() - 1;
-            for (size_t m = 0; m < n_members;) {
-                size_t e = m + 1;
-                while (e < n_members && member_off[e + 1] - member_off[m] <= per) ++e;
-                if (gffx_hip_sam_feed(h, p + member_off[m], member_off[e] - member_off[m]) != GFFX_OK) throw engine_error();
-                m = e;
-            }
-        } else if (gffx_hip_sam_feed(h, p, n) != GFFX_OK) {
-            throw engine_error();
-        }
+        auto feed = [&](const uint8_t *q, uint64_t nb) { return gffx_hip_sam_feed(h, q, nb) == GFFX_OK; };
+        if (!(bgzf_text ? bgzf_file::feed_chunks(p, member_off, chunk ? chunk : (64ull << 20), feed) : feed(p, n))) throw engine_error();
         if (gffx_hip_sam_finish(h) != GFFX_OK) throw engine_error();
-        const double feed_ms = ms_since(t);
-        double ms_inflate = 0, ms_lines = 0, ms_rows = 0;
-        gffx_hip_sam_stage_ms(h, &ms_inflate, &ms_lines, &ms_rows);
-        timer("SAM inflate (device)", ms_inflate);
-        timer("SAM line scan (device)", ms_lines);
-        timer("SAM rows (device)", ms_rows);
-        timer("SAM chunks in all (staging, device, rows back)", feed_ms);
-        t = clock::now();
-        std::vector<uint32_t> rows(3 * gffx_hip_sam_rows(h));
-        if (gffx_hip_sam_copy_rows(h, rows.data()) != GFFX_OK) throw engine_error();
-        timer("SAM rows copy", ms_since(t));
-        uint64_t lines = 0, unmapped = 0, no_seq = 0, kept = 0;
-        gffx_hip_sam_counts(h, &lines, &unmapped, &no_seq, &kept);
+        uint64_t c[4] = {0, 0, 0, 0};  // lines, unmapped, no_seq, kept
+        std::vector<uint32_t> rows = source::take_rows(h, kReader, timer, ms_since(t), c, engine_error);
         if (verbose)
             std::fprintf(stderr, "[INFO] SAM: %s, %llu lines, %llu unmapped, %llu without a seqid of the index, %llu rows kept\n",
-                         bgzf_text ? "BGZF text" : "plain text", (unsigned long long)lines, (unsigned long long)unmapped,
-                         (unsigned long long)no_seq, (unsigned long long)kept);
-        g_run_stats.count("sam_lines", (double)lines);
-        g_run_stats.count("sam_rows_kept", (double)kept);
+                         bgzf_text ? "BGZF text" : "plain text", (unsigned long long)c[0], (unsigned long long)c[1],
+                         (unsigned long long)c[2], (unsigned long long)c[3]);
+        g_run_stats.count("sam_lines", (double)c[0]);
+        g_run_stats.count("sam_rows_kept", (double)c[3]);
         return rows;
     }
 }

@@ -671,41 +671,42 @@ def bgzf_members(data: bytes) -> List[int]:
     return off
 
 
-class BamReader:
-    """gffx_hip_bam_*: the kept (seqid, start, end) rows of a BAM stream.  ref_seq[tid] = seqid number or 0xFFFFFFFF;
-    header_bytes = the BAM header's size in the decompressed stream."""
+class _SourceReader:
+    """What BamReader and SamReader share: the gffx_hip_<stem>_* calls on one handle (device/source_stream.hpp is the
+    pipeline behind both).  A subclass creates self._h and names the four tallies and the three stages of its format."""
+    _stem = ""
+    _count_keys: Tuple[str, ...] = ()
+    _stage_keys: Tuple[str, ...] = ()
 
-    def __init__(self, ref_seq, header_bytes: int, chunk_bytes: int = 0, device: int = 0):
-        rs = _u32(ref_seq)
-        self._h = C.c_void_p()
-        check(lib().gffx_hip_bam_create(device, len(rs), _p(rs) if len(rs) else None, header_bytes, chunk_bytes, C.byref(self._h)))
+    def _fn(self, name: str):
+        return getattr(lib(), "gffx_hip_%s_%s" % (self._stem, name))
 
     def feed(self, data: bytes) -> None:
         buf, ptr = _u8(data)
-        check(lib().gffx_hip_bam_feed(self._h, ptr, len(data)))
+        check(self._fn("feed")(self._h, ptr, len(data)))
 
     def finish(self) -> None:
-        check(lib().gffx_hip_bam_finish(self._h))
+        check(self._fn("finish")(self._h))
 
     def rows(self) -> np.ndarray:
-        n = lib().gffx_hip_bam_rows(self._h)
+        n = self._fn("rows")(self._h)
         out = np.zeros((max(n, 1), 3), np.uint32)
-        check(lib().gffx_hip_bam_copy_rows(self._h, _p(out)))
+        check(self._fn("copy_rows")(self._h, _p(out)))
         return out[:n]
 
     def counts(self) -> Dict[str, int]:
         v = [C.c_uint64() for _ in range(4)]
-        check(lib().gffx_hip_bam_counts(self._h, *[C.byref(x) for x in v]))
-        return dict(zip(("records", "unmapped", "no_seq", "kept"), (x.value for x in v)))
+        check(self._fn("counts")(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(self._count_keys, (x.value for x in v)))
 
     def stage_ms(self) -> Dict[str, float]:
         v = [C.c_double() for _ in range(3)]
-        check(lib().gffx_hip_bam_stage_ms(self._h, *[C.byref(x) for x in v]))
-        return dict(zip(("inflate", "frame", "rows"), (x.value for x in v)))
+        check(self._fn("stage_ms")(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(self._stage_keys, (x.value for x in v)))
 
     def close(self) -> None:
         if self._h:
-            lib().gffx_hip_bam_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -713,6 +714,17 @@ class BamReader:
             self.close()
         except Exception:
             pass
+
+
+class BamReader(_SourceReader):
+    """gffx_hip_bam_*: the kept (seqid, start, end) rows of a BAM stream.  ref_seq[tid] = seqid number or 0xFFFFFFFF;
+    header_bytes = the BAM header's size in the decompressed stream."""
+    _stem, _count_keys, _stage_keys = "bam", ("records", "unmapped", "no_seq", "kept"), ("inflate", "frame", "rows")
+
+    def __init__(self, ref_seq, header_bytes: int, chunk_bytes: int = 0, device: int = 0):
+        rs = _u32(ref_seq)
+        self._h = C.c_void_p()
+        check(lib().gffx_hip_bam_create(device, len(rs), _p(rs) if len(rs) else None, header_bytes, chunk_bytes, C.byref(self._h)))
 
 
 def bam_rows(data: bytes, ref_seq, header_bytes: int, chunk_bytes: int = 0, feed_members: int = 0, device: int = 0) -> np.ndarray:
@@ -732,10 +744,11 @@ def bam_rows(data: bytes, ref_seq, header_bytes: int, chunk_bytes: int = 0, feed
 
 
 # ---- SAM sources (include/gffx_hip.h "SAM sources"; device/sam.hip) ----------------------------------------------------
-class SamReader:
+class SamReader(_SourceReader):
     """gffx_hip_sam_*: the kept (seqid, start, end) rows of a SAM stream, plain text or BGZF-compressed (bgzf=True).
     names = the SN values of the header's @SQ lines in order, ref_seq[tid] = seqid number or 0xFFFFFFFF;
     header_bytes = the offset of the first line that does not begin with '@' in the (inflated) text."""
+    _stem, _count_keys, _stage_keys = "sam", ("lines", "unmapped", "no_seq", "kept"), ("inflate", "lines", "rows")
 
     def __init__(self, names, ref_seq, header_bytes: int, chunk_bytes: int = 0, bgzf: bool = False, device: int = 0):
         nb = [n if isinstance(n, bytes) else str(n).encode() for n in names]
@@ -747,40 +760,6 @@ class SamReader:
         self._h = C.c_void_p()
         check(lib().gffx_hip_sam_create(device, len(nb), b"".join(nb), off.ctypes.data_as(_ffi.u64p), _p(rs) if len(rs) else None,
                                         header_bytes, chunk_bytes, int(bool(bgzf)), C.byref(self._h)))
-
-    def feed(self, data: bytes) -> None:
-        buf, ptr = _u8(data)
-        check(lib().gffx_hip_sam_feed(self._h, ptr, len(data)))
-
-    def finish(self) -> None:
-        check(lib().gffx_hip_sam_finish(self._h))
-
-    def rows(self) -> np.ndarray:
-        n = lib().gffx_hip_sam_rows(self._h)
-        out = np.zeros((max(n, 1), 3), np.uint32)
-        check(lib().gffx_hip_sam_copy_rows(self._h, _p(out)))
-        return out[:n]
-
-    def counts(self) -> Dict[str, int]:
-        v = [C.c_uint64() for _ in range(4)]
-        check(lib().gffx_hip_sam_counts(self._h, *[C.byref(x) for x in v]))
-        return dict(zip(("lines", "unmapped", "no_seq", "kept"), (x.value for x in v)))
-
-    def stage_ms(self) -> Dict[str, float]:
-        v = [C.c_double() for _ in range(3)]
-        check(lib().gffx_hip_sam_stage_ms(self._h, *[C.byref(x) for x in v]))
-        return dict(zip(("inflate", "lines", "rows"), (x.value for x in v)))
-
-    def close(self) -> None:
-        if self._h:
-            lib().gffx_hip_sam_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def sam_rows(data: bytes, names, ref_seq, header_bytes: int, chunk_bytes: int = 0, bgzf: bool = False, feed_bytes: int = 0,

@@ -189,3 +189,44 @@ def test_a_file_ending_inside_a_record_is_rejected(tool, tmp_path):
     for per in (None, 1, 2):
         r = _run(tool, "bam", path, *([per] if per else []))
         assert r.returncode == 3 and "unfinished record" in r.stdout, (per, r.stdout[-300:])
+
+
+def test_file_front_end_on_whole_cut_and_unmarked_streams(tool, tmp_path):
+    """host/bgzf_file.hpp, what bam.cpp and sam.cpp open a BGZF file with: the member directory, the EOF-marker test, the
+    header inflated member by member until it is complete, and the runs of members fed per call -- on a stream whose header
+    spans three members, cut at every member boundary, cut inside a member, and without the EOF member."""
+    recs = synth.bam_test_records(300, seed=3, refs=REFS, big=False)
+    path = tmp_path / "x.bam"
+    hb = synth.write_bam(str(path), synth.bam_header(REFS, b"@CO\t" + b"x" * 150000), [r[0] for r in recs], flush_header=False)
+    data = path.read_bytes()
+    off, at = [], 0
+    while at < len(data):
+        off.append(at)
+        at += struct.unpack_from("<H", data, at + 16)[0] + 1
+    off.append(len(data))
+    n = len(off) - 1
+    isize = [struct.unpack_from("<I", data, off[i + 1] - 4)[0] for i in range(n)]
+    in_header = next(k for k in range(1, n + 1) if sum(isize[:k]) >= hb)  # members the header needs
+    assert in_header == 3 and n >= 4
+
+    def front(*args):
+        r = _run(tool, "front", path, *args)
+        return r.returncode, r.stdout.splitlines()
+
+    rc, out = front()
+    assert rc == 0 and out == ["members %d eof 1" % n, "header ok %d %d inflated %d" % (hb, len(REFS), sum(isize[:3])),
+                               "chunks %d bytes %d" % (n, len(data))], out
+    rc, out = front(len(data), len(data))  # one run takes all members
+    assert rc == 0 and out[2] == "chunks 1 bytes %d" % len(data), out
+    rc, out = front(len(data), off[2])  # the largest run that fits starts at member 0; every run is whole members
+    assert rc == 0 and int(out[2].split()[1]) < n, out
+    for k in range(n + 1):  # cut at every member boundary: sound members, a header that is complete or not
+        rc, out = front(off[k])
+        want = "header ok %d %d inflated %d" % (hb, len(REFS), sum(isize[:3])) if k >= 3 else "header truncated 0 0 inflated %d" % sum(isize[:k])
+        assert rc == 0 and out == ["members %d eof %d" % (k, k == n), want, "chunks %d bytes %d" % (k, off[k])], (k, out)
+    for k in range(n):  # cut inside a member: refused with the member's offset, read inside the bytes that are there
+        for cut in {off[k] + 1, off[k] + 17, (off[k] + off[k + 1]) // 2, off[k + 1] - 1}:
+            rc, out = front(cut)
+            assert rc == 3 and out[0].startswith("status ") and out[0].endswith("offset %d" % off[k]), (k, cut, out)
+    rc, out = front(off[n - 1])  # without the EOF member: the same members but the last, no marker
+    assert rc == 0 and out[0] == "members %d eof 0" % (n - 1) and out[1].startswith("header ok"), out

@@ -8,6 +8,10 @@
 //                                  on a malformed or unfinished record
 //   bgzf_check truncate IN         IN's first member cut at every length 0 .. len-1: each must fail with a status
 //   bgzf_check fuzz IN N SEED      N random corruptions of IN (byte flips, truncations, spliced bytes), each inflated
+//   bgzf_check front IN [LEN [PER]] the file front end of the BAM and SAM sources (host/bgzf_file.hpp) on the first LEN bytes of IN
+//                                  (default all): "members <n> eof <0|1>", "header <ok|truncated|bad> <bytes> <n_ref> inflated
+//                                  <bytes>" (the BAM header rule), "chunks <calls> bytes <fed>" for runs of PER bytes (default
+//                                  1); exit 3 + "status <n> <name> offset <file offset>" on a bad member
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -18,6 +22,7 @@
 #include <vector>
 
 #include "../gffx_amd/csrc/device/bgzf_core.hpp"
+#include "../gffx_amd/csrc/host/bgzf_file.hpp"
 
 using namespace gffx::bgzf;
 
@@ -223,6 +228,49 @@ int main(int argc, char **argv) {
         std::printf("\n");
         return 0;
     }
-    std::fprintf(stderr, "usage: bgzf_check inflate IN OUT | bam IN [K] | truncate IN | fuzz IN N SEED\n");
+    if (mode == "front" && argc >= 3 && argc <= 5) {
+        namespace bf = gffx::bgzf_file;
+        const std::vector<uint8_t> in = read_file(argv[2]);
+        const size_t len = argc > 3 ? std::min<size_t>(in.size(), std::strtoull(argv[3], nullptr, 10)) : in.size();
+        const uint64_t per = argc > 4 ? std::strtoull(argv[4], nullptr, 10) : 1;
+        std::unique_ptr<uint8_t[]> copy(new uint8_t[len ? len : 1]);  // exactly the bytes: a read past them is reported
+        if (len) std::memcpy(copy.get(), in.data(), len);
+        const uint8_t *p = copy.get();
+        std::vector<uint64_t> off;
+        uint64_t bad = 0;
+        int st = bf::member_directory(p, len, &off, &bad);
+        if (st != kOk) {
+            std::printf("status %d %s offset %llu\n", st, status_name(st), (unsigned long long)bad);
+            return 3;
+        }
+        std::printf("members %zu eof %d\n", off.size() - 1, bf::has_eof_marker(p, len) ? 1 : 0);
+        std::vector<uint8_t> head;
+        uint64_t hb = 0;
+        uint32_t n_ref = 0;
+        int hst = kTruncated;
+        st = bf::inflate_header(p, off, &head, [&](const std::vector<uint8_t> &h) { return bam_header_size(h.data(), h.size(), &hb, &n_ref); },
+                                &hst, &bad);
+        if (st != kOk) {
+            std::printf("status %d %s offset %llu\n", st, status_name(st), (unsigned long long)bad);
+            return 3;
+        }
+        std::printf("header %s %llu %u inflated %zu\n", hst == kOk ? "ok" : hst == kTruncated ? "truncated" : "bad",
+                    (unsigned long long)(hst == kOk ? hb : 0), hst == kOk ? n_ref : 0, head.size());
+        uint64_t calls = 0, fed = 0, next = 0;
+        const bool all = bf::feed_chunks(p, off, per, [&](const uint8_t *q, uint64_t nb) {
+            if (q != p + next || nb == 0) return false;  // runs are adjacent, in order, never empty
+            next += nb;
+            ++calls;
+            fed += nb;
+            return true;
+        });
+        if (!all || fed != len) {
+            std::printf("chunks do not tile the file (%llu of %zu bytes)\n", (unsigned long long)fed, len);
+            return 4;
+        }
+        std::printf("chunks %llu bytes %llu\n", (unsigned long long)calls, (unsigned long long)fed);
+        return 0;
+    }
+    std::fprintf(stderr, "usage: bgzf_check inflate IN OUT | bam IN [K] | truncate IN | fuzz IN N SEED | front IN [LEN [PER]]\n");
     return 2;
 }
