@@ -68,6 +68,8 @@ class TreeIndexData:
 
     def __init__(self, handle, num_to_seqid: Sequence[str]):
         self._h = handle
+        self._batches = 0      # open QueryBatches: each holds the native index (its device, its count of busy batches)
+        self._closing = False  # close() was asked for while batches were open: the last of them destroys the index
         self.num_to_seqid: List[str] = list(num_to_seqid)
         # FxHashMap built by collect(): a later duplicate name wins (index_loader/core.rs:28-32)
         self.seqid_to_num: Dict[str, int] = {n: i for i, n in enumerate(self.num_to_seqid)}
@@ -91,9 +93,19 @@ class TreeIndexData:
         return TreeIndexData(h, self.num_to_seqid)
 
     def close(self) -> None:
+        """Destroys the native index -- once no QueryBatch of it is open any more: gffx_hip_batch_destroy reads the index, and
+        the collector finalises an index and its batches in no particular order when they die together in a reference cycle."""
         if getattr(self, "_h", None):
+            if getattr(self, "_batches", 0) > 0:
+                self._closing = True
+                return
             lib().gffx_hip_index_destroy(self._h)
             self._h = None
+
+    def _batch_closed(self) -> None:
+        self._batches -= 1
+        if self._closing and self._batches == 0:
+            self.close()
 
     def __del__(self):
         try:
@@ -188,12 +200,14 @@ class QueryBatch:
         self.index = index
         self._h = C.c_void_p()
         check(lib().gffx_hip_batch_create(index._h, int(max_queries), C.byref(self._h)))
+        index._batches += 1
         self._keep = None  # keeps host/device inputs alive until wait()
 
     def close(self) -> None:
         if getattr(self, "_h", None):
             lib().gffx_hip_batch_destroy(self._h)
             self._h = None
+            self.index._batch_closed()
 
     def __del__(self):
         try:

@@ -11,33 +11,12 @@ from gffx_amd import engine, synth
 from gffx_amd.engine import OverlapMode
 from oracle import binding as ob
 
+from _depth_definition import _numpy_depth
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GFFX = os.path.join(ROOT, "gffx_amd", "bin", "gffx")
-
-
-def _numpy_depth(roots, block_of_fid, block_off, ls, le, lg, n_groups, regions):
-    depth = np.zeros(n_groups, np.uint64)
-    mn = np.full(n_groups, 0xFFFFFFFF, np.uint32)
-    mx = np.zeros(n_groups, np.uint32)
-    co, S, E, F = roots["chr_offsets"], roots["start"].astype(np.int64), roots["end"].astype(np.int64), roots["fid"]
-    for c, qs, qe in regions.astype(np.int64).tolist():
-        lo, hi = int(co[c]), int(co[c + 1])
-        hit = np.nonzero((S[lo:hi] < qe) & (E[lo:hi] > qs))[0] + lo
-        for fid in np.unique(F[hit]).tolist():  # a region counts a root once (depth.rs:241)
-            b = int(block_of_fid[fid])
-            if b == 0xFFFFFFFF:
-                continue
-            a, z = int(block_off[b]), int(block_off[b + 1])
-            ov = np.maximum(ls[a:z].astype(np.int64), qs) < np.minimum(le[a:z].astype(np.int64), qe)
-            if not ov.any():
-                continue
-            g = lg[a:z][ov]
-            depth[np.unique(g)] += 1
-            np.minimum.at(mn, g, ls[a:z][ov])
-            np.maximum.at(mx, g, le[a:z][ov])
-    return depth, mn, mx
 
 
 @pytest.mark.parametrize("seed", range(4))
