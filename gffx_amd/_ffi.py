@@ -154,6 +154,30 @@ SIGNATURES = {
     "gffx_hip_attrs_copy_invalid_bitmap": (C.c_int, [vp, u64p, C.c_uint64]),
     "gffx_hip_attrs_filter_lines": (C.c_int, [vp, u8p, C.c_uint64, C.c_uint64, u64p, u32p, C.c_int, C.c_uint32, u8p, u32p, u8p]),
     "gffx_hip_attrs_stage_ms": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gffx_hip_gff_create": (C.c_int, [C.c_int, C.c_char_p, C.c_uint32, C.c_char_p, u32p, C.c_uint64, C.c_int, C.POINTER(vp)]),
+    "gffx_hip_gff_feed": (C.c_int, [vp, u8p, C.c_uint64]),
+    "gffx_hip_gff_finish": (C.c_int, [vp]),
+    "gffx_hip_gff_error": (C.c_int, [vp, u64p, C.POINTER(C.c_int)]),
+    "gffx_hip_gff_counts": (C.c_int, [vp] + [u64p] * 8),
+    "gffx_hip_gff_stage_ms": (C.c_int, [vp] + [C.POINTER(C.c_double)] * 5),
+    "gffx_hip_gff_n_rows": (C.c_uint64, [vp]),
+    "gffx_hip_gff_n_roots": (C.c_uint64, [vp]),
+    "gffx_hip_gff_fts_bytes": (C.c_uint64, [vp]),
+    "gffx_hip_gff_atn_bytes": (C.c_uint64, [vp]),
+    "gffx_hip_gff_seqids_bytes": (C.c_uint64, [vp]),
+    "gffx_hip_gff_n_skipped_lines": (C.c_uint64, [vp]),
+    "gffx_hip_gff_n_warn_rows": (C.c_uint64, [vp]),
+    "gffx_hip_gff_copy_fts": (C.c_int, [vp, u8p]),
+    "gffx_hip_gff_copy_fid": (C.c_int, [vp, u32p]),
+    "gffx_hip_gff_copy_prt": (C.c_int, [vp, u32p]),
+    "gffx_hip_gff_copy_a2f": (C.c_int, [vp, u32p]),
+    "gffx_hip_gff_copy_atn": (C.c_int, [vp, u8p]),
+    "gffx_hip_gff_copy_seqids": (C.c_int, [vp, u8p]),
+    "gffx_hip_gff_copy_gof": (C.c_int, [vp, u8p]),
+    "gffx_hip_gff_copy_roots": (C.c_int, [vp, u32p]),
+    "gffx_hip_gff_copy_skipped_lines": (C.c_int, [vp, u64p]),
+    "gffx_hip_gff_copy_warn_rows": (C.c_int, [vp, u32p]),
+    "gffx_hip_gff_destroy": (None, [vp]),
 }
 
 # the regex compiler of `gffx search -r` in libgffx_host.so (include/gffx_host.h "gffx_host_regex_*"): name -> (restype, argtypes)

@@ -142,6 +142,9 @@ void write_gff_output(const std::string &gff_path, const std::vector<Block> &blo
 // core.rs:41-242: one pass over the GFF -> <gff>.{fts,prt,a2f,atn,sqs,gof,rit,rix}
 void build_index(const std::string &gff, const std::string &attr_key, const std::string &skip_types,
                  bool verbose);
+// the same files, the arrays behind them built on HIP device `device` (gffx_hip_gff_*: device/gff.hip); no fallback
+void build_index_device(const std::string &gff, const std::string &attr_key, const std::string &skip_types,
+                        int device, bool verbose);
 
 // ---- index_loader ------------------------------------------------------------------------------
 namespace index_loader {

@@ -8,11 +8,18 @@
 //     alone enter the interval index, as 0-based half-open [start-1, end) with start/end swapped
 //     when reversed (:107-109), and open a byte block that ends at the next root's line (:182-185);
 //   * seqid numbers are handed out in order of first appearance as a ROOT's seqid (:171-175).
+//
+// Two producers of the arrays, one writer: build_index walks the text on the host; build_index_device (`gffx index --gpu`)
+// feeds it to the engine (gffx_hip_gff_*, device/gff.hip) and takes the arrays back.  write_index builds the trees,
+// serialises them and writes the eight files for both.
 #include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 #include <unordered_map>
 #include <unordered_set>
 
+#include "../../../include/gffx_hip.h"
+#include "../device/gff_core.hpp"
 #include "gffx.hpp"
 
 namespace gffx {
@@ -95,6 +102,39 @@ void serialize_tree(const std::vector<TreeNode> &arena, int node, std::string &o
     serialize_tree(arena, n.right, out);
 }
 
+// what both producers hand to the writer
+struct IndexArrays {
+    std::string fts, gof, prt, a2f;  // the files' bytes
+    std::string sqs, atn;            // the names in number order, a '\n' after each (.atn without its "#attribute=" line)
+    std::vector<std::vector<std::tuple<uint32_t, uint32_t, uint32_t>>> trees_input;  // per seqid, in file order
+};
+
+// .rit / .rix (core.rs:206-224, utils/tree_io.rs:37-63) and the eight files
+void write_index(const std::string &gff, const std::string &attr_key, const IndexArrays &ia) {
+    std::string rit, rix = "[";
+    for (size_t c = 0; c < ia.trees_input.size(); ++c) {
+        if (c) rix.push_back(',');
+        rix += std::to_string(rit.size());
+        std::vector<TreeNode> arena;
+        const int root = build_tree(ia.trees_input[c], arena);
+        serialize_tree(arena, root, rit);
+    }
+    rix.push_back(']');
+
+    const std::string atn_text = "#attribute=" + attr_key + "\n" + ia.atn;
+
+    write_whole_file(append_suffix(gff, ".fts"), ia.fts);
+    write_whole_file(append_suffix(gff, ".gof"), ia.gof);
+    write_whole_file(append_suffix(gff, ".rit"), rit);
+    write_whole_file(append_suffix(gff, ".rix"), rix);
+    write_whole_file(append_suffix(gff, ".sqs"), ia.sqs);
+    write_whole_file(append_suffix(gff, ".atn"), atn_text);
+    write_whole_file(append_suffix(gff, ".a2f"), ia.a2f);
+    write_whole_file(append_suffix(gff, ".prt"), ia.prt);
+}
+
+const char *kWarnFormat = "[WARN] Attribute value contains invalid chars (.,;) (should be URL-encoded): in '%s'\n";
+
 }  // namespace
 
 void build_index(const std::string &gff, const std::string &attr_key, const std::string &skip_types,
@@ -157,9 +197,7 @@ void build_index(const std::string &gff, const std::string &attr_key, const std:
         if (const auto v = capture_after_key(line, attr_key, false)) {
             rf.attr = std::string(*v);
             if (rf.attr->find_first_of(" ;,") != std::string::npos)
-                std::fprintf(stderr,
-                             "[WARN] Attribute value contains invalid chars (.,;) (should be URL-encoded): in '%s'\n",
-                             rf.attr->c_str());
+                std::fprintf(stderr, kWarnFormat, rf.attr->c_str());
         }
         raw.push_back(std::move(rf));
     }
@@ -168,10 +206,11 @@ void build_index(const std::string &gff, const std::string &attr_key, const std:
     feature_map.reserve(raw.size() * 2);
     for (size_t i = 0; i < raw.size(); ++i) feature_map[raw[i].id] = static_cast<uint32_t>(i);
 
-    std::string fts, gof, prt, a2f;
+    IndexArrays ia;
+    std::string &fts = ia.fts, &gof = ia.gof, &prt = ia.prt, &a2f = ia.a2f;
     std::vector<std::string> atn, seqids;
     std::unordered_map<std::string, uint32_t> attr_ids, seq_ids;
-    std::vector<std::vector<std::tuple<uint32_t, uint32_t, uint32_t>>> trees_input;
+    auto &trees_input = ia.trees_input;
     bool have_root = false;
     uint32_t cur_fid = 0, cur_seq = 0;
     uint64_t cur_off = 0;
@@ -215,29 +254,128 @@ void build_index(const std::string &gff, const std::string &attr_key, const std:
     }
     if (have_root) emit_gof(data.size());  // core.rs:201-203
 
-    // .rit / .rix (core.rs:206-224, utils/tree_io.rs:37-63)
-    std::string rit, rix = "[";
-    for (size_t c = 0; c < trees_input.size(); ++c) {
-        if (c) rix.push_back(',');
-        rix += std::to_string(rit.size());
-        std::vector<TreeNode> arena;
-        const int root = build_tree(trees_input[c], arena);
-        serialize_tree(arena, root, rit);
+    for (const auto &s : seqids) ia.sqs += s + "\n";
+    for (const auto &v : atn) ia.atn += v + "\n";
+    write_index(gff, attr_key, ia);
+    if (verbose) std::fprintf(stderr, "Index built successfully for %s\n", gff.c_str());
+}
+
+void build_index_device(const std::string &gff, const std::string &attr_key, const std::string &skip_types, int device,
+                        bool verbose) {
+    std::string skip_bytes;  // core.rs:47 split(',') (no trimming)
+    std::vector<uint32_t> skip_off{0};
+    {
+        size_t a = 0;
+        while (true) {
+            const size_t c = skip_types.find(',', a);
+            skip_bytes += skip_types.substr(a, c == std::string::npos ? std::string::npos : c - a);
+            skip_off.push_back(static_cast<uint32_t>(skip_bytes.size()));
+            if (c == std::string::npos) break;
+            a = c + 1;
+        }
     }
-    rix.push_back(']');
+    if (attr_key.find('\0') != std::string::npos) throw Error("the attribute key holds a NUL byte");
+    if (verbose) std::fprintf(stderr, "Building index for %s ...\n", gff.c_str());
+    MappedFile file(gff);
+    const std::string_view data = file.view();
 
-    std::string sqs, atn_text = "#attribute=" + attr_key + "\n";
-    for (const auto &s : seqids) sqs += s + "\n";
-    for (const auto &v : atn) atn_text += v + "\n";
+    uint64_t chunk = 0;  // GFFX_INDEX_CHUNK_BYTES: the text bytes per device pass (0 / unset: the engine's 64 MiB)
+    if (const char *e = std::getenv("GFFX_INDEX_CHUNK_BYTES")) chunk = std::strtoull(e, nullptr, 10);
+    gffx_hip_gff *h = nullptr;
+    auto engine_error = [&]() { return Error(std::string("gffx index --gpu: ") + gffx_hip_last_error()); };
+    if (gffx_hip_gff_create(device, attr_key.c_str(), static_cast<uint32_t>(skip_off.size() - 1), skip_bytes.data(), skip_off.data(), chunk, -1, &h) !=
+        GFFX_OK)
+        throw engine_error();
+    struct Closer {
+        gffx_hip_gff *h;
+        ~Closer() { gffx_hip_gff_destroy(h); }
+    } closer{h};
 
-    write_whole_file(append_suffix(gff, ".fts"), fts);
-    write_whole_file(append_suffix(gff, ".gof"), gof);
-    write_whole_file(append_suffix(gff, ".rit"), rit);
-    write_whole_file(append_suffix(gff, ".rix"), rix);
-    write_whole_file(append_suffix(gff, ".sqs"), sqs);
-    write_whole_file(append_suffix(gff, ".atn"), atn_text);
-    write_whole_file(append_suffix(gff, ".a2f"), a2f);
-    write_whole_file(append_suffix(gff, ".prt"), prt);
+    const uint8_t *text = reinterpret_cast<const uint8_t *>(data.data());
+    int rc = gffx_hip_gff_feed(h, text, data.size());
+    if (rc == GFFX_OK) rc = gffx_hip_gff_finish(h);
+    if (rc != GFFX_OK) {
+        uint64_t off = 0;
+        int kind = 0;
+        gffx_hip_gff_error(h, &off, &kind);
+        if (kind == 0 || off > data.size()) throw engine_error();
+        // the host path's message for the line the device names
+        size_t nl = data.find('\n', off);
+        if (nl == std::string_view::npos) nl = data.size();
+        const std::string line(trim_unicode_ws(data.substr(off, nl - off)));
+        switch (kind) {
+            case gff::kBadUtf8: throw Error("invalid utf-8 sequence in GFF line at byte " + std::to_string(off));
+            case gff::kColumns: throw Error("Invalid GFF line (expected 9 columns): " + line);
+            case gff::kDigits: throw Error("invalid digit found in string");
+            default: throw Error("Missing ID in feature: " + line);
+        }
+    }
+
+    IndexArrays ia;
+    auto take = [&](int r) {
+        if (r != GFFX_OK) throw engine_error();
+    };
+    const uint64_t n_rows = gffx_hip_gff_n_rows(h), n_roots = gffx_hip_gff_n_roots(h);
+    ia.fts.resize(gffx_hip_gff_fts_bytes(h));
+    ia.prt.resize(4 * n_rows);
+    ia.a2f.resize(4 * n_rows);
+    ia.gof.resize(24 * n_roots);
+    ia.sqs.resize(gffx_hip_gff_seqids_bytes(h));
+    ia.atn.resize(gffx_hip_gff_atn_bytes(h));
+    auto u8 = [](std::string &s) { return reinterpret_cast<uint8_t *>(s.data()); };
+    auto u32 = [](std::string &s) { return reinterpret_cast<uint32_t *>(s.data()); };  // (the files are little-endian, as the host is)
+    take(gffx_hip_gff_copy_fts(h, u8(ia.fts)));
+    take(gffx_hip_gff_copy_prt(h, u32(ia.prt)));
+    take(gffx_hip_gff_copy_a2f(h, u32(ia.a2f)));
+    take(gffx_hip_gff_copy_gof(h, u8(ia.gof)));
+    take(gffx_hip_gff_copy_seqids(h, u8(ia.sqs)));
+    take(gffx_hip_gff_copy_atn(h, u8(ia.atn)));
+    std::vector<uint32_t> roots(4 * n_roots);
+    take(gffx_hip_gff_copy_roots(h, roots.data()));
+    uint64_t n_seq = 0;
+    take(gffx_hip_gff_counts(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &n_seq, nullptr));
+    ia.trees_input.resize(n_seq);  // the roots per seqid, in file order: what the stable sort of build_tree sees today
+    for (uint64_t k = 0; k < n_roots; ++k) {
+        const uint32_t seq = roots[4 * k + 3];
+        if (seq >= n_seq) throw Error("gffx index --gpu: a root with seqid number " + std::to_string(seq) + " of " + std::to_string(n_seq));
+        ia.trees_input[seq].emplace_back(roots[4 * k], roots[4 * k + 1], roots[4 * k + 2]);
+    }
+
+    if (verbose) {  // the `skip comment feature` lines, in file order
+        std::vector<uint64_t> skipped(gffx_hip_gff_n_skipped_lines(h));
+        take(gffx_hip_gff_copy_skipped_lines(h, skipped.data()));
+        for (const uint64_t off : skipped) {
+            if (off > data.size()) continue;
+            size_t nl = data.find('\n', off);
+            if (nl == std::string_view::npos) nl = data.size();
+            const std::string_view line = trim_unicode_ws(data.substr(off, nl - off));
+            size_t a = 0;
+            for (int k = 0; k < 2 && a != std::string_view::npos; ++k) {
+                a = line.find('\t', a);
+                if (a != std::string_view::npos) ++a;
+            }
+            if (a == std::string_view::npos) continue;
+            const size_t z = line.find('\t', a);
+            const std::string_view ty = line.substr(a, z == std::string_view::npos ? std::string_view::npos : z - a);
+            std::printf("skip comment feature: %.*s\n", (int)ty.size(), ty.data());
+        }
+    }
+    {  // the [WARN] lines, one per flagged row in file order: the row's value is name a2f[row] of .atn
+        std::vector<uint32_t> warn(gffx_hip_gff_n_warn_rows(h));
+        take(gffx_hip_gff_copy_warn_rows(h, warn.data()));
+        if (!warn.empty()) {
+            std::vector<size_t> name_at{0};
+            for (size_t i = 0; i < ia.atn.size(); ++i)
+                if (ia.atn[i] == '\n') name_at.push_back(i + 1);
+            const uint32_t *a2f = u32(ia.a2f);
+            for (const uint32_t row : warn) {
+                if (row >= n_rows || a2f[row] + 1 >= name_at.size()) continue;
+                const std::string v = ia.atn.substr(name_at[a2f[row]], name_at[a2f[row] + 1] - 1 - name_at[a2f[row]]);
+                std::fprintf(stderr, kWarnFormat, v.c_str());
+            }
+        }
+    }
+    write_index(gff, attr_key, ia);
     if (verbose) std::fprintf(stderr, "Index built successfully for %s\n", gff.c_str());
 }
 

@@ -168,7 +168,9 @@ const char *kIndexUsage =
     "  -i, --input <INPUT>\n"
     "  -a, --attribute <ATTRIBUTE>    [default: gene_name]\n"
     "  -s, --skip-types <SKIP_TYPES>  [default: remark,note,comment,region,gap,assembly_gap,contig,scaffold,source]\n"
-    "  -v, --verbose\n";
+    "  -v, --verbose\n"
+    "  -g, --gpu                      Build the side-cars on the HIP device (same bytes; no CPU fallback)\n"
+    "      --device <N>               HIP device of --gpu [default: 0]\n";
 
 size_t parse_size(const std::string &v, const char *flag) {
     const auto x = parse_u32_rust(v);
@@ -334,6 +336,8 @@ int run_index_cli(int argc, char **argv) {
                                                {'a', "attribute", true},
                                                {'s', "skip-types", true},
                                                {'v', "verbose", false},
+                                               {'g', "gpu", false},
+                                               {0, "device", true},
                                                {'h', "help", false}};
     const auto o = parse_opts(argc, argv, 2, specs);
     if (o.count("help")) {
@@ -348,7 +352,11 @@ int run_index_cli(int argc, char **argv) {
                                  : "remark,note,comment,region,gap,assembly_gap,contig,scaffold,source";  // :18
     const bool verbose = o.count("verbose") > 0;
     if (verbose) std::printf("Indexing: %s\n", input.c_str());  // commands/index.rs:26-28
-    build_index(input, attr, skip, verbose);
+    // addition: --gpu builds the same eight files from arrays made on the device (GFFX_INDEX_CHUNK_BYTES: the text per pass)
+    if (o.count("gpu"))
+        build_index_device(input, attr, skip, o.count("device") ? static_cast<int>(parse_size(o.at("device")[0], "--device <N>")) : 0, verbose);
+    else
+        build_index(input, attr, skip, verbose);
     // addition: the all-line SoA image `<gff>.lsoa` for depth / coverage (block_table.cpp); GFFX_LINE_TABLE=off skips it
     const char *lt = std::getenv("GFFX_LINE_TABLE");
     if (!(lt && std::string(lt) == "off")) {

@@ -1070,3 +1070,145 @@ class AttrSearch:
         v = [C.c_double() for _ in range(4)]
         check(lib().gffx_hip_attrs_stage_ms(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("build", "match", "resolve", "filter"), (x.value for x in v)))
+
+
+# ---- `gffx index --gpu` (include/gffx_hip.h "gffx index --gpu"; device/gff.hip) -----------------------------------------
+DEFAULT_SKIP_TYPES = "remark,note,comment,region,gap,assembly_gap,contig,scaffold,source"
+
+
+class GffBuilt:
+    """The arrays of an index, with the fields of oracle.gffx_oracle_py.Built: ids (the `.fts` lines), fid, prt, a2f, atn,
+    seqids, gof [(fid, seq, start offset, end offset)], trees_input [per seqid: (start, end, fid) in file order]."""
+    FIELDS = ("ids", "fid", "prt", "a2f", "atn", "seqids", "gof", "trees_input")
+
+    def __init__(self, **kw):
+        for f in self.FIELDS:
+            setattr(self, f, kw[f])
+
+    def astuple(self):
+        return tuple(getattr(self, f) for f in self.FIELDS)
+
+
+class GffIndexer:
+    """gffx_hip_gff_*: GFF3 text in (file order, cut anywhere), the arrays of the side-cars out.  skip_types is the raw
+    --skip-types string (split at ',', not trimmed).  chunk_bytes bounds a device pass (0: 64 MiB); hash_bits (0..31) is
+    the test hook of FeatureIds.  A malformed line fails feed() / finish(); error() then names it."""
+    ERROR_KINDS = {4: "BAD_UTF8", 5: "COLUMNS", 6: "DIGITS", 7: "NO_ID"}
+    _count_keys = ("lines", "blank", "skipped_type", "zero_end", "rows", "roots", "seqids", "attr_values")
+    _stage_keys = ("scan", "rows", "table", "resolve", "number")
+
+    def __init__(self, attr_key: str = "gene_name", skip_types: str = DEFAULT_SKIP_TYPES, device: int = 0, chunk_bytes: int = 0,
+                 hash_bits: int = -1):
+        key = attr_key if isinstance(attr_key, bytes) else attr_key.encode()
+        raw = skip_types if isinstance(skip_types, bytes) else skip_types.encode()
+        parts = raw.split(b",")
+        off = np.zeros(len(parts) + 1, np.uint32)
+        off[1:] = np.cumsum([len(p) for p in parts], dtype=np.uint32)
+        self._h = C.c_void_p()
+        check(lib().gffx_hip_gff_create(device, key, len(parts), b"".join(parts), _p(off), chunk_bytes, hash_bits, C.byref(self._h)))
+
+    def feed(self, data: bytes) -> None:
+        buf, ptr = _u8(data)
+        check(lib().gffx_hip_gff_feed(self._h, ptr, len(data)))
+
+    def finish(self) -> None:
+        check(lib().gffx_hip_gff_finish(self._h))
+
+    def error(self) -> Optional[Tuple[int, str]]:
+        """(file offset of the first bad line, its kind), or None"""
+        off, kind = C.c_uint64(), C.c_int()
+        check(lib().gffx_hip_gff_error(self._h, C.byref(off), C.byref(kind)))
+        return (off.value, self.ERROR_KINDS.get(kind.value, str(kind.value))) if kind.value else None
+
+    @property
+    def counts(self) -> Dict[str, int]:
+        v = [C.c_uint64() for _ in range(8)]
+        check(lib().gffx_hip_gff_counts(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(self._count_keys, (x.value for x in v)))
+
+    @property
+    def stage_ms(self) -> Dict[str, float]:
+        v = [C.c_double() for _ in range(5)]
+        check(lib().gffx_hip_gff_stage_ms(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(self._stage_keys, (x.value for x in v)))
+
+    def _bytes(self, size_fn, copy_fn) -> bytes:
+        out = np.zeros(max(size_fn(self._h), 1), np.uint8)
+        check(copy_fn(self._h, out.ctypes.data_as(_ffi.u8p)))
+        return out[:size_fn(self._h)].tobytes()
+
+    def _words(self, n: int, copy_fn, dtype=np.uint32) -> np.ndarray:
+        out = np.zeros(max(n, 1), dtype)
+        check(copy_fn(self._h, out.ctypes.data_as(u64p if dtype == np.uint64 else u32p)))
+        return out[:n]
+
+    def fts(self) -> bytes:
+        return self._bytes(lib().gffx_hip_gff_fts_bytes, lib().gffx_hip_gff_copy_fts)
+
+    def atn(self) -> bytes:
+        return self._bytes(lib().gffx_hip_gff_atn_bytes, lib().gffx_hip_gff_copy_atn)
+
+    def sqs(self) -> bytes:
+        return self._bytes(lib().gffx_hip_gff_seqids_bytes, lib().gffx_hip_gff_copy_seqids)
+
+    def gof(self) -> bytes:
+        L = lib()
+        return self._bytes(lambda h: 24 * L.gffx_hip_gff_n_roots(h), L.gffx_hip_gff_copy_gof)
+
+    def fid(self) -> np.ndarray:
+        return self._words(lib().gffx_hip_gff_n_rows(self._h), lib().gffx_hip_gff_copy_fid)
+
+    def prt(self) -> np.ndarray:
+        return self._words(lib().gffx_hip_gff_n_rows(self._h), lib().gffx_hip_gff_copy_prt)
+
+    def a2f(self) -> np.ndarray:
+        return self._words(lib().gffx_hip_gff_n_rows(self._h), lib().gffx_hip_gff_copy_a2f)
+
+    def roots(self) -> np.ndarray:
+        """(start, end, fid, seqid) per root, in file order"""
+        n = lib().gffx_hip_gff_n_roots(self._h)
+        return self._words(4 * n, lib().gffx_hip_gff_copy_roots).reshape(-1, 4)
+
+    def skipped_lines(self) -> np.ndarray:
+        return self._words(lib().gffx_hip_gff_n_skipped_lines(self._h), lib().gffx_hip_gff_copy_skipped_lines, np.uint64)
+
+    def warn_rows(self) -> np.ndarray:
+        return self._words(lib().gffx_hip_gff_n_warn_rows(self._h), lib().gffx_hip_gff_copy_warn_rows)
+
+    def built(self) -> GffBuilt:
+        names = lambda b: [x.decode("utf-8") for x in b.split(b"\n")[:-1]]  # noqa: E731
+        seqids = names(self.sqs())
+        gof = np.frombuffer(self.gof(), dtype=np.dtype([("fid", "<u4"), ("seq", "<u4"), ("a", "<u8"), ("z", "<u8")]))
+        trees: List[List[Tuple[int, int, int]]] = [[] for _ in seqids]
+        for s, e, f, q in self.roots().tolist():
+            trees[q].append((s, e, f))
+        return GffBuilt(ids=names(self.fts()), fid=self.fid().tolist(), prt=self.prt().tolist(), a2f=self.a2f().tolist(),
+                        atn=names(self.atn()), seqids=seqids, gof=[tuple(int(x) for x in g) for g in gof.tolist()], trees_input=trees)
+
+    def close(self) -> None:
+        if self._h:
+            lib().gffx_hip_gff_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def gff_index(data: bytes, attr_key: str = "gene_name", skip_types: str = DEFAULT_SKIP_TYPES, chunk_bytes: int = 0, feed_bytes: int = 0,
+              hash_bits: int = -1, device: int = 0) -> GffIndexer:
+    """A finished GffIndexer over the whole text (feed_bytes > 0: fed in pieces of that many bytes).  The caller closes it."""
+    g = GffIndexer(attr_key, skip_types, device, chunk_bytes, hash_bits)
+    try:
+        if feed_bytes > 0:
+            for i in range(0, len(data), feed_bytes):
+                g.feed(data[i:i + feed_bytes])
+        else:
+            g.feed(data)
+        g.finish()
+    except Exception:
+        g.close()
+        raise
+    return g

@@ -26,6 +26,8 @@
  *   FtsMap::map_fnames_to_fids, PrtMap::map_fids_to_roots, gffx_hip_ids_* (`gffx extract`)
  *   the ID test of write_gff_output_filtered
  *     (index_loader/fts.rs:16-93, prt.rs:54-102, utils/common.rs:389-431)
+ *   the line loop, feature_map and the numbering loop of   gffx_hip_gff_* (`gffx index --gpu`)
+ *     build_index (index_builder/core.rs:71-203)
  *
  * Semantics (bit-exact with the reference):
  *   a root interval iv of the query's seqid is a HIT iff  iv.start < q.end && iv.end > q.start
@@ -619,6 +621,71 @@ int gffx_hip_attrs_filter_lines(gffx_hip_attrs *, const uint8_t *text, uint64_t 
                                 const uint32_t *line_root, int by_type, uint32_t n_types, const uint8_t *types /* concatenated */,
                                 const uint32_t *type_off /* n_types + 1 */, uint8_t *keep_out);
 int gffx_hip_attrs_stage_ms(const gffx_hip_attrs *, double *build_ms, double *match_ms, double *resolve_ms, double *filter_ms);
+
+/* ---- `gffx index --gpu`: the GFF3 text to the arrays of the side-cars .fts .prt .a2f .atn .sqs .gof and the root list of ----
+ * .rit / .rix (index_builder/core.rs:41-242; device/gff.hip, the rules of one line in device/gff_core.hpp, shared with
+ * the host).  The bytes are what host/index_builder.cpp writes for the same text.
+ *
+ * _create takes the attribute key (a C string, without '=') and the skip strings of --skip-types already split at ','
+ * (string k = skip[skip_off[k], skip_off[k + 1]), not trimmed, an empty one a member like any other).  chunk_bytes bounds the
+ * fed bytes per device pass (0: 64 MiB; at most 1 GiB).  hash_bits as for gffx_hip_ids_create (a test hook).
+ * _feed takes the text in file order from byte 0, in pieces of any size, cut anywhere; the unfinished line is carried into
+ * the next pass.  _finish reads a last line that does not end in '\n' and runs the steps that need the whole file.
+ * One line, without its '\n', in this order: empty or first byte '#' (before any trimming): skipped.  Not valid UTF-8: error
+ * 4 BAD_UTF8.  Unicode White_Space (U+0009-000D, 0020, 0085, 00A0, 1680, 2000-200A, 2028, 2029, 202F, 205F, 3000) trimmed at
+ * both ends; empty then: skipped.  Not exactly 9 TAB-separated fields: error 5 COLUMNS.  Column 3 equal to a skip string:
+ * skipped by type.  Columns 4 / 5 not an optional '+' and decimal digits <= 2^32 - 1: error 6 DIGITS.  end == 0: skipped;
+ * start > end swapped; the row is [start ? start - 1 : 0, end).  ID = the leftmost match of ID=([^;\s]+) over the whole
+ * trimmed line (\s: the White_Space set; an empty value makes the search go on: `ID=;ID=z` yields z, `geneID=x;ID=y`
+ * yields x); none: error 7 NO_ID.  Parent: the same with `Parent`, optional.  The attribute value: the leftmost match of
+ * <key>=([^;]+); a value that holds ' ' or ',' flags the row (the [WARN] line of the command).
+ * The first bad line of the file and the first failing check on it fail the call (whatever the chunking); _error reports
+ * its file offset and kind (0: none).  After an error the object only reports it again and copies nothing out.
+ * Over the whole file: a row's number is its `.fts` line; fid[row] = the LAST row with the row's ID (an earlier duplicate's
+ * fid is not its own row); prt[row] = the fid of its Parent where it has one and that string is some row's ID (a comma
+ * list names none), else fid[row]; a row is a root iff prt == fid.  Seqids are numbered by their first appearance as column
+ * 1 of a ROOT row, attribute values by their first appearance on any row; a2f[row] = the value's number, UINT32_MAX: none.
+ * _counts: lines read; empty, comment and white-space-only lines; lines skipped by type; lines with end == 0; rows; roots;
+ * distinct seqids; distinct attribute values (the last three after _finish).
+ * After _finish, each with its size query: _copy_fts (the IDs, a '\n' after each: the `.fts` file; _fts_bytes), _copy_fid /
+ * _copy_prt / _copy_a2f (a word per row; _n_rows), _copy_atn / _copy_seqids (the names in number order, a '\n' after each;
+ * _atn_bytes / _seqids_bytes), _copy_gof (24 bytes per root in file order: fid u32, seqid u32, the root's line offset u64,
+ * the next root's -- the fed byte count for the last -- u64, little-endian: the `.gof` file; _n_roots), _copy_roots
+ * (start, end, fid, seqid per root, in file order; _n_roots), _copy_skipped_lines (file offsets of the lines skipped by type;
+ * _n_skipped_lines), _copy_warn_rows (the flagged rows; _n_warn_rows).
+ * _stage_ms: HIP-event milliseconds of the line scan, the rows kernels, the ID table's build, the resolve and the numbering
+ * (with the root list) so far.
+ * LIMITS: more than 2^30 rows fail the call; a pass with its carry has no 4 GiB bound (line ends are 64-bit, the text
+ * buffer grows with a line longer than a pass), but the strings of one kind of the lines that END within one 4 KiB tile of
+ * a pass must total less than 4 GiB.  DEVIATION: none in what is computed; the passes run one after the other (no
+ * double-buffered staging as in the BAM / SAM readers). */
+typedef struct gffx_hip_gff gffx_hip_gff;
+int gffx_hip_gff_create(int device, const char *attr_key, uint32_t n_skip, const char *skip /* concatenated */,
+                        const uint32_t *skip_off /* n_skip + 1 */, uint64_t chunk_bytes, int hash_bits, gffx_hip_gff **out);
+int gffx_hip_gff_feed(gffx_hip_gff *, const uint8_t *bytes, uint64_t n_bytes);
+int gffx_hip_gff_finish(gffx_hip_gff *);
+int gffx_hip_gff_error(const gffx_hip_gff *, uint64_t *line_offset, int *kind);
+int gffx_hip_gff_counts(const gffx_hip_gff *, uint64_t *lines, uint64_t *blank, uint64_t *skipped_type, uint64_t *zero_end, uint64_t *rows,
+                        uint64_t *roots, uint64_t *seqids, uint64_t *attr_values);
+int gffx_hip_gff_stage_ms(const gffx_hip_gff *, double *scan_ms, double *rows_ms, double *table_ms, double *resolve_ms, double *number_ms);
+uint64_t gffx_hip_gff_n_rows(const gffx_hip_gff *);
+uint64_t gffx_hip_gff_n_roots(const gffx_hip_gff *);
+uint64_t gffx_hip_gff_fts_bytes(const gffx_hip_gff *);
+uint64_t gffx_hip_gff_atn_bytes(const gffx_hip_gff *);
+uint64_t gffx_hip_gff_seqids_bytes(const gffx_hip_gff *);
+uint64_t gffx_hip_gff_n_skipped_lines(const gffx_hip_gff *);
+uint64_t gffx_hip_gff_n_warn_rows(const gffx_hip_gff *);
+int gffx_hip_gff_copy_fts(const gffx_hip_gff *, uint8_t *out);
+int gffx_hip_gff_copy_fid(const gffx_hip_gff *, uint32_t *out);
+int gffx_hip_gff_copy_prt(const gffx_hip_gff *, uint32_t *out);
+int gffx_hip_gff_copy_a2f(const gffx_hip_gff *, uint32_t *out);
+int gffx_hip_gff_copy_atn(const gffx_hip_gff *, uint8_t *out);
+int gffx_hip_gff_copy_seqids(const gffx_hip_gff *, uint8_t *out);
+int gffx_hip_gff_copy_gof(const gffx_hip_gff *, uint8_t *out);
+int gffx_hip_gff_copy_roots(const gffx_hip_gff *, uint32_t *out /* 4 per root */);
+int gffx_hip_gff_copy_skipped_lines(const gffx_hip_gff *, uint64_t *out);
+int gffx_hip_gff_copy_warn_rows(const gffx_hip_gff *, uint32_t *out);
+void gffx_hip_gff_destroy(gffx_hip_gff *);
 
 #ifdef __cplusplus
 }
