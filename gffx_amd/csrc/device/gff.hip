@@ -19,7 +19,7 @@
 // These line kernels restate sam.hip's with 64-bit line ends and without a header; the BAM/SAM readers are untouched.
 //
 // _finish, over the whole file (a Parent= may name a later line):
-//   k_gff_insert       all IDs into the ID table (ids::table_insert_one: one compare-and-swap, atomicMax: the last row wins)
+//   k_table_insert     all IDs into the ID table (string_table.hpp: one compare-and-swap, atomicMax: the last row wins)
 //   k_gff_resolve      (a launch of its own, after all inserts) fid = the table's value of the row's own ID; prt = the
 //                      value of its Parent where it has one that is found, else fid; root = (prt == fid)
 //   numbering by first appearance, once for column 1 over the root rows and once for the attribute value over the rows
@@ -41,9 +41,9 @@
 #include <string>
 #include <vector>
 
-#include "bgzf_device.hpp"
 #include "gff_core.hpp"
-#include "ids_insert_device.hpp"
+#include "string_table.hpp"
+#include "table_handle.hpp"
 
 namespace gffx {
 
@@ -248,50 +248,16 @@ __global__ __launch_bounds__(64) void k_gff_rows(const uint8_t *D, u64 d_file_of
 }
 
 // ---- the finish steps: one thread per slot or per row --------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_gff_fill(u64 *slot, uint32_t *val, uint32_t slots, uint32_t v) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < slots) {
-        slot[i] = ids::kEmptyWord;
-        val[i] = v;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_gff_insert(u64 *slot, uint32_t *val, const uint8_t *bytes, const u64 *off, uint32_t n, uint32_t mask,
-                                                    uint32_t hash_mask) {
-    const uint32_t f = blockIdx.x * 256u + threadIdx.x;
-    if (f < n) ids::table_insert_one(slot, val, bytes, off, f, mask, hash_mask);
-}
-
 // what decides whether row f takes part in a numbering: its root flag (column 1), or that it has a value (attribute)
 __device__ __forceinline__ bool gff_eligible(const uint32_t *root, const u64 *off, uint32_t f) {
     return root ? root[f] != 0 : off[f + 1] > off[f];
 }
 
-// ids::table_insert_one with the LOWEST row per string: val starts at kNone, atomicMin
+// the rows that take part enter the table with the LOWEST row per string (the values filled for Keep::kSmallest)
 __global__ __launch_bounds__(256) void k_gff_insert_min(u64 *slot, uint32_t *val, const uint8_t *bytes, const u64 *off, const uint32_t *root,
                                                         uint32_t n, uint32_t mask, uint32_t hash_mask) {
     const uint32_t f = blockIdx.x * 256u + threadIdx.x;
-    if (f >= n || !gff_eligible(root, off, f)) return;
-    const u64 a = off[f], len = off[f + 1] - a;
-    const uint32_t h = ids::name_hash(bytes + a, len) & hash_mask;
-    const u64 mine = ((u64)h << 32) | f;
-    for (uint32_t i = h & mask, steps = 0; steps <= mask; i = (i + 1) & mask, ++steps) {  // (<= n slots are ever taken: it ends)
-        u64 w = slot[i];
-        if (w == ids::kEmptyWord) {
-            w = atomicCAS(&slot[i], ids::kEmptyWord, mine);
-            if (w == ids::kEmptyWord) {
-                atomicMin(&val[i], f);
-                return;
-            }
-        }
-        if ((uint32_t)(w >> 32) != h) continue;
-        const uint32_t rep = (uint32_t)w;
-        const u64 ra = off[rep];
-        if (off[rep + 1] - ra == len && ids::name_equal(bytes + ra, bytes + a, len)) {
-            atomicMin(&val[i], f);
-            return;
-        }
-    }
+    if (f < n && gff_eligible(root, off, f)) ids::table_insert_one<ids::Keep::kSmallest>(slot, val, bytes, off, f, mask, hash_mask);
 }
 
 __global__ __launch_bounds__(256) void k_gff_resolve(ids::Table t, const uint8_t *par_bytes, const u64 *par_off, uint32_t n, uint32_t *fid,
@@ -381,39 +347,16 @@ __global__ __launch_bounds__(256) void k_gff_gof(const uint32_t *root_rows, uint
     roots[4 * (u64)k + 3] = seq[r];
 }
 
-// a device array that keeps its first `used` elements when it grows
-template <class T>
-hipError_t grow_keep(DevArr<T> &a, size_t used, size_t need) {
-    if (need <= a.cap) return hipSuccess;
-    const size_t c = std::max(need, a.cap + a.cap / 2);
-    T *p = nullptr;
-    hipError_t e = hipMalloc(&p, c * sizeof(T));
-    if (e != hipSuccess) return e;
-    if (used && a.p) {
-        e = hipMemcpy(p, a.p, used * sizeof(T), hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(p);
-            return e;
-        }
-    }
-    if (a.p) (void)hipFree(a.p);
-    a.p = p;
-    a.cap = c;
-    return hipSuccess;
-}
-
 inline dim3 grid256(u64 n) { return dim3((uint32_t)std::max<u64>((n + 255) / 256, 1)); }
 
 }  // namespace gffx
 
 using namespace gffx;
 
-struct gffx_hip_gff {
+struct gffx_hip_gff : StreamEvents<3> {
     int device = 0;
     uint64_t chunk_bytes = 0;
     int hash_bits = -1;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     GffResult *res_host = nullptr;  // pinned
     DevArr<GffResult> res;
     DevArr<uint8_t> key, skip_bytes;
@@ -448,10 +391,7 @@ struct gffx_hip_gff {
 
     ~gffx_hip_gff() {
         if (stream) (void)hipStreamSynchronize(stream);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
         if (res_host) (void)hipHostFree(res_host);
-        if (stream) (void)hipStreamDestroy(stream);
     }
     int sticky(int rc) {
         if (rc != GFFX_OK && error == GFFX_OK) {
@@ -463,13 +403,6 @@ struct gffx_hip_gff {
 };
 
 namespace {
-
-int add_ms(gffx_hip_gff *h, int k, hipEvent_t a, hipEvent_t b) {
-    float t = 0;
-    GFFX_HIP_TRY(hipEventElapsedTime(&t, a, b));
-    h->ms[k] += t;
-    return GFFX_OK;
-}
 
 // one pass over the carry followed by the T bytes at p; final_line: the carry alone, as the file's last line
 int run_pass(gffx_hip_gff *h, const uint8_t *p, uint64_t T, int final_line) {
@@ -550,8 +483,8 @@ int run_pass(gffx_hip_gff *h, const uint8_t *p, uint64_t T, int final_line) {
         GFFX_HIP_TRY(hipGetLastError());
         GFFX_HIP_TRY(hipEventRecord(h->ev[2], s));
         GFFX_HIP_TRY(hipStreamSynchronize(s));
-        if (int rc = add_ms(h, 0, h->ev[0], h->ev[1])) return rc;
-        if (int rc = add_ms(h, 1, h->ev[1], h->ev[2])) return rc;
+        GFFX_HIP_TRY(h->add_ms(&h->ms[0], 0, 1));
+        GFFX_HIP_TRY(h->add_ms(&h->ms[1], 1, 2));
         h->n_rows += rows;
         h->n_skipped += skips;
         for (int k = 0; k < 4; ++k) h->n_bytes[k] += r.total[k + 1];
@@ -600,7 +533,7 @@ int number_strings(gffx_hip_gff *h, int k, const uint32_t *root, uint32_t slots,
     hipStream_t s = h->stream;
     const uint32_t n = (uint32_t)h->n_rows, hm = ids::hash_mask_of(h->hash_bits);
     GFFX_HIP_TRY(number.ensure(std::max<uint32_t>(n, 1)));
-    hipLaunchKernelGGL(k_gff_fill, grid256(slots), dim3(256), 0, s, h->slot.p, h->val.p, slots, ids::kNone);
+    ids::launch_table_fill(s, h->slot.p, h->val.p, slots, ids::Keep::kSmallest);
     hipLaunchKernelGGL(k_gff_insert_min, grid256(n), dim3(256), 0, s, h->slot.p, h->val.p, h->bytes[k].p, h->off[k].p, root, n, slots - 1, hm);
     const ids::Table t{h->slot.p, h->val.p, h->bytes[k].p, h->off[k].p, slots - 1, hm};
     hipLaunchKernelGGL(k_gff_first, grid256(n), dim3(256), 0, s, t, root, n, h->first_row.p, h->is_first.p);
@@ -632,8 +565,7 @@ int finish_steps(gffx_hip_gff *h) {
     GFFX_HIP_TRY(h->fts.ensure(h->n_bytes[1] + n));
     // 1. the ID table, 2. the parents
     GFFX_HIP_TRY(hipEventRecord(h->ev[0], s));
-    hipLaunchKernelGGL(k_gff_fill, grid256(slots), dim3(256), 0, s, h->slot.p, h->val.p, slots, 0u);
-    hipLaunchKernelGGL(k_gff_insert, grid256(n), dim3(256), 0, s, h->slot.p, h->val.p, h->bytes[1].p, h->off[1].p, n, slots - 1, hm);
+    ids::launch_table_build(s, h->slot.p, h->val.p, slots, h->bytes[1].p, h->off[1].p, n, hm);
     GFFX_HIP_TRY(hipGetLastError());
     GFFX_HIP_TRY(hipEventRecord(h->ev[1], s));
     const ids::Table t{h->slot.p, h->val.p, h->bytes[1].p, h->off[1].p, slots - 1, hm};
@@ -642,8 +574,8 @@ int finish_steps(gffx_hip_gff *h) {
     GFFX_HIP_TRY(hipGetLastError());
     GFFX_HIP_TRY(hipEventRecord(h->ev[2], s));
     GFFX_HIP_TRY(hipStreamSynchronize(s));
-    if (int rc = add_ms(h, 2, h->ev[0], h->ev[1])) return rc;
-    if (int rc = add_ms(h, 3, h->ev[1], h->ev[2])) return rc;
+    GFFX_HIP_TRY(h->add_ms(&h->ms[2], 0, 1));
+    GFFX_HIP_TRY(h->add_ms(&h->ms[3], 1, 2));
     // 3. the numbering of the seqids (root rows) and of the attribute values, 4. the root list
     GFFX_HIP_TRY(hipEventRecord(h->ev[0], s));
     if (int rc = number_strings(h, 0, h->root.p, slots, h->seq, h->sqs, &h->n_seqids, &h->sqs_bytes)) return rc;
@@ -663,7 +595,8 @@ int finish_steps(gffx_hip_gff *h) {
     }
     GFFX_HIP_TRY(hipEventRecord(h->ev[1], s));
     GFFX_HIP_TRY(hipStreamSynchronize(s));
-    return add_ms(h, 4, h->ev[0], h->ev[1]);
+    GFFX_HIP_TRY(h->add_ms(&h->ms[4], 0, 1));
+    return GFFX_OK;
 }
 
 int ready(const gffx_hip_gff *h, const char *who) {
@@ -703,8 +636,7 @@ extern "C" int gffx_hip_gff_create(int device, const char *attr_key, uint32_t n_
     h->device = device;
     h->hash_bits = hash_bits;
     h->chunk_bytes = std::min<uint64_t>(std::max<uint64_t>(chunk_bytes ? chunk_bytes : (64ull << 20), 1), 1ull << 30);
-    GFFX_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    for (hipEvent_t &e : h->ev) GFFX_HIP_TRY(hipEventCreate(&e));
+    GFFX_HIP_TRY(h->create_stream());
     GFFX_HIP_TRY(hipHostMalloc((void **)&h->res_host, sizeof(GffResult)));
     GFFX_HIP_TRY(h->res.ensure(1));
     h->key_len = (uint32_t)key_len;

@@ -1,7 +1,8 @@
-// gffx_device.hpp -- shared declarations of the gfx950 engine (device views, error plumbing).
+// gffx_device.hpp -- shared declarations of the gfx950 engine (device views, error plumbing, device arrays).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -31,6 +32,56 @@ int fail(int code, const char *fmt, ...);
                                 "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e),        \
                                 __FILE__, __LINE__);                                          \
     } while (0)
+
+// ---- device arrays -------------------------------------------------------------------------------
+using u64 = unsigned long long;
+
+// a growable device array (its content is lost when it grows)
+template <class T>
+struct DevArr {
+    T *p = nullptr;
+    size_t cap = 0;
+    ~DevArr() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t ensure(size_t n) {
+        if (n <= cap) return hipSuccess;
+        const size_t c = std::max(n, cap + cap / 2);  // (grow by 1.5x at least)
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        const hipError_t e = hipMalloc(&p, c * sizeof(T));
+        if (e == hipSuccess) cap = c;
+        return e;
+    }
+};
+
+// a device array that keeps its first `used` elements when it grows
+template <class T>
+hipError_t grow_keep(DevArr<T> &a, size_t used, size_t need) {
+    if (need <= a.cap) return hipSuccess;
+    const size_t c = std::max(need, a.cap + a.cap / 2);
+    T *p = nullptr;
+    hipError_t e = hipMalloc(&p, c * sizeof(T));
+    if (e != hipSuccess) return e;
+    if (used && a.p) {
+        e = hipMemcpy(p, a.p, used * sizeof(T), hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(p);
+            return e;
+        }
+    }
+    if (a.p) (void)hipFree(a.p);
+    a.p = p;
+    a.cap = c;
+    return hipSuccess;
+}
+
+// is `device` one this process may use?  (defined in bgzf.hip, as launch_scan)
+int check_device(int device);
+
+// k_scan on stream s: out[0..n] = exclusive prefix of in[0..n) (out[n] = the total); *total too unless NULL
+void launch_scan(hipStream_t s, const uint32_t *in, uint32_t n, u64 *out, u64 *total);
 
 // ---- device-side view of the index -------------------------------------------------------------
 // One entry per root interval (utils/tree.rs:5-10), seqid after seqid, each seqid sorted stably by

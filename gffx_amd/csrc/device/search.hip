@@ -4,8 +4,8 @@
 // index_loader/a2f.rs:77-113, index_loader/prt.rs:54-72, utils/common.rs:289-465).  The rules of one value, one chase and
 // one line are search_core.hpp's and ids_core.hpp's, shared with the host.
 //
-//   k_attr_insert       the string table of ids.hip (ids_insert_device.hpp) over the `.atn` values, once per handle, and over
-//                       the wanted strings of every exact match.
+//   k_table_insert      the string table (string_table.hpp) over the `.atn` values, once per handle, and over the wanted
+//                       strings of every exact match.
 //   k_attr_classes      one thread per aid: class[aid] = the largest aid with the same string (table_find on the value table).
 //   k_attr_match_exact  one thread per aid: the value is looked up in the table of the wanted strings; every aid of a
 //                       wanted string matches (search.rs:105-110).  One atomicOr into the matched bitmap per match.
@@ -30,28 +30,16 @@
 #include <string>
 #include <vector>
 
-#include "bgzf_device.hpp"
 #include "engine_private.hpp"
-#include "ids_core.hpp"
-#include "ids_insert_device.hpp"
 #include "search_core.hpp"
+#include "string_table.hpp"
+#include "table_handle.hpp"
 
 namespace gffx {
 
 using ids::kNone;
 
 constexpr uint32_t kLdsBudget = 65536;  // bytes of LDS a block of k_attr_match_dfa<true> may take
-
-__global__ __launch_bounds__(256) void k_attr_fill(u64 *slot, uint32_t *val, uint32_t slots) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < slots) ids::table_clear_one(slot, val, i);
-}
-
-__global__ __launch_bounds__(256) void k_attr_insert(u64 *slot, uint32_t *val, const uint8_t *bytes, const u64 *off, uint32_t n,
-                                                     uint32_t mask, uint32_t hash_mask) {
-    const uint32_t f = blockIdx.x * 256u + threadIdx.x;
-    if (f < n) ids::table_insert_one(slot, val, bytes, off, f, mask, hash_mask);
-}
 
 __global__ __launch_bounds__(256) void k_attr_classes(ids::Table values, uint32_t n, uint32_t *cls) {
     const uint32_t a = blockIdx.x * 256u + threadIdx.x;
@@ -125,64 +113,32 @@ __global__ __launch_bounds__(64) void k_attr_filter(ids::Table values, const u64
 
 using namespace gffx;
 
-struct gffx_hip_attrs {
+struct gffx_hip_attrs : StreamEvents<2> {
     int device = 0;
     int hash_bits = 32;
     int dfa_path = 0;                        // 0: by size; 1: LDS (an error when the tables do not fit); 2: global
     uint32_t n = 0, n_a2f = 0, n_prt = 0;    // `.atn` values; `.a2f` words; `.prt` words
     uint32_t n_bits = 0;                     // max(n_a2f, n_prt): bits of the fid, root and invalid bitmaps
-    uint32_t mask = 0, hash_mask = 0xFFFFFFFFu, pair_mask = 0, key_len = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    DevArr<u64> slot, off, pairs, w_slot, w_off, line_off;
-    DevArr<uint32_t> val, cls, a2f, prt, matched, fid_bits, root_bits, invalid_bits, w_val, line_root, type_off;
-    DevArr<uint8_t> bytes, key, w_bytes, dfa_cls, text, type_bytes, keep;
+    uint32_t pair_mask = 0, key_len = 0;
+    ids::StringTable values, wanted;
+    LineChunk lines;
+    DevArr<u64> pairs;
+    DevArr<uint32_t> cls, a2f, prt, matched, fid_bits, root_bits, invalid_bits;
+    DevArr<uint8_t> key, dfa_cls;
     DevArr<uint16_t> dfa_trans;
     const char *last_dfa_kernel = "";
-    double ms[4] = {0, 0, 0, 0};  // table build, match, resolve, line filter (HIP events)
+    double ms[4] = {0, 0, 0, 0};  // table build, match, resolve, line filter (HIP events; a failing read of the events adds nothing)
 
-    ids::Table table() const { return ids::Table{slot.p, val.p, bytes.p, off.p, mask, hash_mask}; }
     uint64_t matched_words32() const { return 2 * (((uint64_t)n + 63) / 64); }
     uint64_t bitmap_words32() const { return 2 * (((uint64_t)n_bits + 63) / 64); }
-
-    ~gffx_hip_attrs() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 namespace {
-int check_offsets(const char *who, const char *what, const uint64_t *off, uint64_t n, uint64_t *total) {
-    *total = 0;
-    if (!n) return GFFX_OK;
-    if (off[0] != 0) return fail(GFFX_E_INVALID, "%s: %s[0] is not 0", who, what);
-    for (uint64_t i = 0; i < n; ++i)
-        if (off[i + 1] < off[i]) return fail(GFFX_E_INVALID, "%s: %s is not ascending at %llu", who, what, (unsigned long long)i);
-    *total = off[n];
-    return GFFX_OK;
-}
-
-void add_ms(gffx_hip_attrs *h, int k) {
-    float t = 0;
-    if (hipEventElapsedTime(&t, h->ev[0], h->ev[1]) == hipSuccess) h->ms[k] += t;
-}
-
 int clear_resolved(gffx_hip_attrs *h) {
     GFFX_HIP_TRY(hipMemsetAsync(h->fid_bits.p, 0, h->bitmap_words32() * 4, h->stream));
     GFFX_HIP_TRY(hipMemsetAsync(h->root_bits.p, 0, h->bitmap_words32() * 4, h->stream));
     GFFX_HIP_TRY(hipMemsetAsync(h->invalid_bits.p, 0, h->bitmap_words32() * 4, h->stream));
     GFFX_HIP_TRY(hipMemsetAsync(h->pairs.p, 0xFF, ((uint64_t)h->pair_mask + 1) * 8, h->stream));
-    return GFFX_OK;
-}
-
-int copy_bitmap(gffx_hip_attrs *h, const uint32_t *d, uint64_t need, uint64_t *host, uint64_t n_words, const char *who) {
-    if (n_words < need) return fail(GFFX_E_INVALID, "%s: %llu words given, %llu needed", who, (unsigned long long)n_words, (unsigned long long)need);
-    if (need && !host) return fail(GFFX_E_INVALID, "%s: host is NULL", who);
-    GFFX_HIP_TRY(hipSetDevice(h->device));
-    GFFX_HIP_TRY(hipStreamSynchronize(h->stream));
-    if (need) GFFX_HIP_TRY(hipMemcpy(host, d, need * 8, hipMemcpyDeviceToHost));
     return GFFX_OK;
 }
 }  // namespace
@@ -211,22 +167,14 @@ extern "C" int gffx_hip_attrs_create(int device, uint64_t n_values, const uint8_
     if (!h) return fail(GFFX_E_OOM, "%s: out of host memory", who);
     h->device = device;
     h->hash_bits = hash_bits < 0 ? 32 : hash_bits;
-    h->hash_mask = ids::hash_mask_of(h->hash_bits);
     h->dfa_path = dfa_path;
     h->n = (uint32_t)n_values;
     h->n_a2f = (uint32_t)n_a2f;
     h->n_prt = (uint32_t)n_prt;
     h->n_bits = std::max(h->n_a2f, h->n_prt);
     h->key_len = key_len;
-    const uint32_t slots = ids::table_slots(n_values);
-    h->mask = slots - 1;
     h->pair_mask = ids::table_slots(n_a2f) - 1;  // >= 2 x the fids, so >= 2 x the matched ones: a probe always ends
-    GFFX_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    for (hipEvent_t &e : h->ev) GFFX_HIP_TRY(hipEventCreate(&e));
-    GFFX_HIP_TRY(h->slot.ensure(slots));
-    GFFX_HIP_TRY(h->val.ensure(slots));
-    GFFX_HIP_TRY(h->bytes.ensure(n_bytes + ids::kPad));
-    GFFX_HIP_TRY(h->off.ensure(n_values + 1));
+    GFFX_HIP_TRY(h->create_stream());
     GFFX_HIP_TRY(h->cls.ensure(std::max<uint64_t>(n_values, 1)));
     GFFX_HIP_TRY(h->a2f.ensure(std::max<uint64_t>(n_a2f, 1)));
     GFFX_HIP_TRY(h->prt.ensure(std::max<uint64_t>(n_prt, 1)));
@@ -237,29 +185,17 @@ extern "C" int gffx_hip_attrs_create(int device, uint64_t n_values, const uint8_
     GFFX_HIP_TRY(h->invalid_bits.ensure(std::max<uint64_t>(h->bitmap_words32(), 2)));
     GFFX_HIP_TRY(h->pairs.ensure((uint64_t)h->pair_mask + 1));
     hipStream_t s = h->stream;
-    GFFX_HIP_TRY(hipMemsetAsync(h->bytes.p + n_bytes, 0, ids::kPad, s));
-    if (n_bytes) GFFX_HIP_TRY(hipMemcpyAsync(h->bytes.p, values, n_bytes, hipMemcpyHostToDevice, s));
-    if (n_values) {
-        GFFX_HIP_TRY(hipMemcpyAsync(h->off.p, value_off, (n_values + 1) * 8, hipMemcpyHostToDevice, s));
-    } else {
-        GFFX_HIP_TRY(hipMemsetAsync(h->off.p, 0, 8, s));
-    }
     if (n_a2f) GFFX_HIP_TRY(hipMemcpyAsync(h->a2f.p, a2f, n_a2f * 4, hipMemcpyHostToDevice, s));
     if (n_prt) GFFX_HIP_TRY(hipMemcpyAsync(h->prt.p, prt, n_prt * 4, hipMemcpyHostToDevice, s));
     if (key_len) GFFX_HIP_TRY(hipMemcpyAsync(h->key.p, key, key_len, hipMemcpyHostToDevice, s));
     GFFX_HIP_TRY(hipMemsetAsync(h->matched.p, 0, h->matched_words32() * 4, s));
     if (int rc = clear_resolved(h.get())) return rc;
-    GFFX_HIP_TRY(hipEventRecord(h->ev[0], s));
-    hipLaunchKernelGGL(k_attr_fill, dim3((slots + 255) / 256), dim3(256), 0, s, h->slot.p, h->val.p, slots);
-    if (h->n) {
-        hipLaunchKernelGGL(k_attr_insert, dim3((h->n + 255) / 256), dim3(256), 0, s, h->slot.p, h->val.p, h->bytes.p, h->off.p, h->n, h->mask,
-                           h->hash_mask);
-        hipLaunchKernelGGL(k_attr_classes, dim3((h->n + 255) / 256), dim3(256), 0, s, h->table(), h->n, h->cls.p);
-    }
+    if (int rc = h->values.build(s, n_values, values, value_off, ids::hash_mask_of(h->hash_bits), h->ev[0])) return rc;
+    if (h->n) hipLaunchKernelGGL(k_attr_classes, dim3((h->n + 255) / 256), dim3(256), 0, s, h->values.table(), h->n, h->cls.p);
     GFFX_HIP_TRY(hipGetLastError());
     GFFX_HIP_TRY(hipEventRecord(h->ev[1], s));
     GFFX_HIP_TRY(hipStreamSynchronize(s));  // (the caller's arrays have been read)
-    add_ms(h.get(), 0);
+    (void)h->add_ms(&h->ms[0]);
     *out = h.release();
     return GFFX_OK;
 }
@@ -286,24 +222,14 @@ extern "C" int gffx_hip_attrs_match_exact(gffx_hip_attrs *h, uint64_t n_wanted, 
     if (n_bytes && !wanted) return fail(GFFX_E_INVALID, "%s: wanted is NULL", who);
     if (!n_wanted || !h->n) return GFFX_OK;
     GFFX_HIP_TRY(hipSetDevice(h->device));
-    const uint32_t slots = ids::table_slots(n_wanted), nw = (uint32_t)n_wanted;
-    GFFX_HIP_TRY(h->w_slot.ensure(slots));
-    GFFX_HIP_TRY(h->w_val.ensure(slots));
-    GFFX_HIP_TRY(h->w_bytes.ensure(n_bytes + ids::kPad));
-    GFFX_HIP_TRY(h->w_off.ensure(n_wanted + 1));
     hipStream_t s = h->stream;
-    if (n_bytes) GFFX_HIP_TRY(hipMemcpyAsync(h->w_bytes.p, wanted, n_bytes, hipMemcpyHostToDevice, s));
-    GFFX_HIP_TRY(hipMemcpyAsync(h->w_off.p, wanted_off, (n_wanted + 1) * 8, hipMemcpyHostToDevice, s));
-    GFFX_HIP_TRY(hipEventRecord(h->ev[0], s));
-    hipLaunchKernelGGL(k_attr_fill, dim3((slots + 255) / 256), dim3(256), 0, s, h->w_slot.p, h->w_val.p, slots);
-    hipLaunchKernelGGL(k_attr_insert, dim3((nw + 255) / 256), dim3(256), 0, s, h->w_slot.p, h->w_val.p, h->w_bytes.p, h->w_off.p, nw, slots - 1,
-                       h->hash_mask);
-    const ids::Table wt{h->w_slot.p, h->w_val.p, h->w_bytes.p, h->w_off.p, slots - 1, h->hash_mask};
-    hipLaunchKernelGGL(k_attr_match_exact, dim3((h->n + 255) / 256), dim3(256), 0, s, wt, h->bytes.p, h->off.p, h->n, h->matched.p);
+    if (int rc = h->wanted.build(s, n_wanted, wanted, wanted_off, h->values.hash_mask, h->ev[0])) return rc;
+    hipLaunchKernelGGL(k_attr_match_exact, dim3((h->n + 255) / 256), dim3(256), 0, s, h->wanted.table(), h->values.bytes.p, h->values.off.p, h->n,
+                       h->matched.p);
     GFFX_HIP_TRY(hipGetLastError());
     GFFX_HIP_TRY(hipEventRecord(h->ev[1], s));
     GFFX_HIP_TRY(hipStreamSynchronize(s));
-    add_ms(h, 1);
+    (void)h->add_ms(&h->ms[1]);
     return GFFX_OK;
 }
 
@@ -336,14 +262,15 @@ extern "C" int gffx_hip_attrs_match_dfa(gffx_hip_attrs *h, uint32_t n_states, ui
     const search::Dfa d{h->dfa_cls.p, h->dfa_trans.p, n_states, n_classes, init};
     GFFX_HIP_TRY(hipEventRecord(h->ev[0], s));
     if (use_lds)
-        hipLaunchKernelGGL(k_attr_match_dfa<true>, dim3((h->n + 255) / 256), dim3(256), (size_t)lds_bytes, s, d, h->bytes.p, h->off.p, h->n,
+        hipLaunchKernelGGL(k_attr_match_dfa<true>, dim3((h->n + 255) / 256), dim3(256), (size_t)lds_bytes, s, d, h->values.bytes.p, h->values.off.p, h->n,
                            h->matched.p);
     else
-        hipLaunchKernelGGL(k_attr_match_dfa<false>, dim3((h->n + 255) / 256), dim3(256), 0, s, d, h->bytes.p, h->off.p, h->n, h->matched.p);
+        hipLaunchKernelGGL(k_attr_match_dfa<false>, dim3((h->n + 255) / 256), dim3(256), 0, s, d, h->values.bytes.p, h->values.off.p, h->n,
+                           h->matched.p);
     GFFX_HIP_TRY(hipGetLastError());
     GFFX_HIP_TRY(hipEventRecord(h->ev[1], s));
     GFFX_HIP_TRY(hipStreamSynchronize(s));  // (the caller's tables have been read)
-    add_ms(h, 1);
+    (void)h->add_ms(&h->ms[1]);
     return GFFX_OK;
 }
 
@@ -370,25 +297,25 @@ extern "C" int gffx_hip_attrs_resolve(gffx_hip_attrs *h) {
     GFFX_HIP_TRY(hipGetLastError());
     GFFX_HIP_TRY(hipEventRecord(h->ev[1], s));
     GFFX_HIP_TRY(hipStreamSynchronize(s));
-    add_ms(h, 2);
+    (void)h->add_ms(&h->ms[2]);
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_attrs_copy_matched_bitmap(gffx_hip_attrs *h, uint64_t *host, uint64_t n_words) {
     if (!h) return fail(GFFX_E_INVALID, "gffx_hip_attrs_copy_matched_bitmap: NULL handle");
-    return copy_bitmap(h, h->matched.p, h->matched_words32() / 2, host, n_words, "gffx_hip_attrs_copy_matched_bitmap");
+    return copy_bitmap("gffx_hip_attrs_copy_matched_bitmap", h->device, h->stream, h->matched.p, h->matched_words32() / 2, host, n_words);
 }
 extern "C" int gffx_hip_attrs_copy_fid_bitmap(gffx_hip_attrs *h, uint64_t *host, uint64_t n_words) {
     if (!h) return fail(GFFX_E_INVALID, "gffx_hip_attrs_copy_fid_bitmap: NULL handle");
-    return copy_bitmap(h, h->fid_bits.p, h->bitmap_words32() / 2, host, n_words, "gffx_hip_attrs_copy_fid_bitmap");
+    return copy_bitmap("gffx_hip_attrs_copy_fid_bitmap", h->device, h->stream, h->fid_bits.p, h->bitmap_words32() / 2, host, n_words);
 }
 extern "C" int gffx_hip_attrs_copy_root_bitmap(gffx_hip_attrs *h, uint64_t *host, uint64_t n_words) {
     if (!h) return fail(GFFX_E_INVALID, "gffx_hip_attrs_copy_root_bitmap: NULL handle");
-    return copy_bitmap(h, h->root_bits.p, h->bitmap_words32() / 2, host, n_words, "gffx_hip_attrs_copy_root_bitmap");
+    return copy_bitmap("gffx_hip_attrs_copy_root_bitmap", h->device, h->stream, h->root_bits.p, h->bitmap_words32() / 2, host, n_words);
 }
 extern "C" int gffx_hip_attrs_copy_invalid_bitmap(gffx_hip_attrs *h, uint64_t *host, uint64_t n_words) {
     if (!h) return fail(GFFX_E_INVALID, "gffx_hip_attrs_copy_invalid_bitmap: NULL handle");
-    return copy_bitmap(h, h->invalid_bits.p, h->bitmap_words32() / 2, host, n_words, "gffx_hip_attrs_copy_invalid_bitmap");
+    return copy_bitmap("gffx_hip_attrs_copy_invalid_bitmap", h->device, h->stream, h->invalid_bits.p, h->bitmap_words32() / 2, host, n_words);
 }
 
 extern "C" int gffx_hip_attrs_filter_lines(gffx_hip_attrs *h, const uint8_t *text, uint64_t n_bytes, uint64_t n_lines, const uint64_t *line_off,
@@ -396,46 +323,20 @@ extern "C" int gffx_hip_attrs_filter_lines(gffx_hip_attrs *h, const uint8_t *tex
                                            const uint32_t *type_off, uint8_t *keep_out) {
     static const char *who = "gffx_hip_attrs_filter_lines";
     if (!h) return fail(GFFX_E_INVALID, "%s: NULL handle", who);
-    if (n_lines && (!line_off || !line_root || !keep_out)) return fail(GFFX_E_INVALID, "%s: line_off, line_root or keep_out is NULL", who);
-    if (n_lines > (1ull << 32)) return fail(GFFX_E_INVALID, "%s: %llu lines in one call (at most 2^32)", who, (unsigned long long)n_lines);
-    uint64_t end = 0;
-    if (int rc = check_offsets(who, "line_off", line_off, n_lines, &end)) return rc;
-    if (end > n_bytes) return fail(GFFX_E_INVALID, "%s: the last line ends at %llu, the text has %llu bytes", who, (unsigned long long)end,
-                                   (unsigned long long)n_bytes);
-    if (n_bytes && !text) return fail(GFFX_E_INVALID, "%s: text is NULL", who);
-    uint32_t type_bytes = 0;
-    if (n_types) {
-        if (!type_off) return fail(GFFX_E_INVALID, "%s: type_off is NULL", who);
-        if (n_types > 65536) return fail(GFFX_E_INVALID, "%s: %u type names (at most 65536)", who, n_types);
-        if (type_off[0] != 0) return fail(GFFX_E_INVALID, "%s: type_off[0] is not 0", who);
-        for (uint32_t k = 0; k < n_types; ++k)
-            if (type_off[k + 1] < type_off[k]) return fail(GFFX_E_INVALID, "%s: type_off is not ascending at %u", who, k);
-        type_bytes = type_off[n_types];
-        if (type_bytes && !types) return fail(GFFX_E_INVALID, "%s: types is NULL", who);
-    }
+    const LineArgs a{text, n_bytes, n_lines, line_off, line_root, by_type, n_types, types, type_off, keep_out};
+    if (int rc = LineChunk::check(who, a)) return rc;
     if (!n_lines) return GFFX_OK;
     GFFX_HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    GFFX_HIP_TRY(h->text.ensure(n_bytes + ids::kPad));
-    GFFX_HIP_TRY(h->line_off.ensure(n_lines + 1));
-    GFFX_HIP_TRY(h->line_root.ensure(n_lines));
-    GFFX_HIP_TRY(h->keep.ensure(n_lines));
-    GFFX_HIP_TRY(h->type_bytes.ensure(std::max<uint32_t>(type_bytes, 1)));
-    GFFX_HIP_TRY(h->type_off.ensure(n_types + 1));
-    if (n_bytes) GFFX_HIP_TRY(hipMemcpyAsync(h->text.p, text, n_bytes, hipMemcpyHostToDevice, s));
-    GFFX_HIP_TRY(hipMemcpyAsync(h->line_off.p, line_off, (n_lines + 1) * 8, hipMemcpyHostToDevice, s));
-    GFFX_HIP_TRY(hipMemcpyAsync(h->line_root.p, line_root, n_lines * 4, hipMemcpyHostToDevice, s));
-    if (type_bytes) GFFX_HIP_TRY(hipMemcpyAsync(h->type_bytes.p, types, type_bytes, hipMemcpyHostToDevice, s));
-    if (n_types) GFFX_HIP_TRY(hipMemcpyAsync(h->type_off.p, type_off, (n_types + 1) * 4, hipMemcpyHostToDevice, s));
-    const ids::Types ty{h->type_bytes.p, h->type_off.p, n_types, by_type || n_types ? 1 : 0};
+    ids::Types ty;
+    if (int rc = h->lines.upload(s, a, &ty)) return rc;
     GFFX_HIP_TRY(hipEventRecord(h->ev[0], s));
-    hipLaunchKernelGGL(k_attr_filter, dim3((unsigned)((n_lines + 63) / 64)), dim3(64), 0, s, h->table(), h->pairs.p, h->pair_mask, ty, h->key.p,
-                       h->key_len, h->text.p, h->line_off.p, h->line_root.p, (u64)n_lines, h->keep.p);
+    hipLaunchKernelGGL(k_attr_filter, dim3((unsigned)((n_lines + 63) / 64)), dim3(64), 0, s, h->values.table(), h->pairs.p, h->pair_mask, ty, h->key.p,
+                       h->key_len, h->lines.text.p, h->lines.line_off.p, h->lines.line_root.p, (u64)n_lines, h->lines.keep.p);
     GFFX_HIP_TRY(hipGetLastError());
     GFFX_HIP_TRY(hipEventRecord(h->ev[1], s));
-    GFFX_HIP_TRY(hipMemcpyAsync(keep_out, h->keep.p, n_lines, hipMemcpyDeviceToHost, s));
-    GFFX_HIP_TRY(hipStreamSynchronize(s));
-    add_ms(h, 3);
+    if (int rc = h->lines.download(s, a)) return rc;
+    (void)h->add_ms(&h->ms[3]);
     return GFFX_OK;
 }
 

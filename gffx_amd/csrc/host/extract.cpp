@@ -149,7 +149,7 @@ void run_extract(const ExtractArgs &args) {
     if (gffx_hip_ids_create(args.device, fts.size(), reinterpret_cast<const uint8_t *>(fts.bytes.data()), fts.off.data(), prt.size(),
                             prt.data(), -1, OutPtr(ids)) != GFFX_OK)
         hip_fail("gffx_hip_ids_create");
-    timer.lap("ID table on the device (names H2D, k_ids_insert)");
+    timer.lap("ID table on the device (names H2D, k_table_insert)");
     // Phase A (extract.rs:84-111): names -> fids -> roots
     std::vector<uint32_t> fid(std::max<size_t>(names.size(), 1)), root(std::max<size_t>(names.size(), 1));
     if (gffx_hip_ids_resolve(ids.get(), names.size(), reinterpret_cast<const uint8_t *>(names.bytes.data()), names.off.data(), fid.data(),

@@ -141,7 +141,7 @@ void run_search(const SearchArgs &args) {
                               prt.size(), prt.data(), reinterpret_cast<const uint8_t *>(attr_name.data()), static_cast<uint32_t>(attr_name.size()),
                               -1, 0, OutPtr(attrs)) != GFFX_OK)
         hip_fail("gffx_hip_attrs_create");
-    timer.lap("Value table on the device (values H2D, k_attr_insert, k_attr_classes)");
+    timer.lap("Value table on the device (values H2D, k_table_insert, k_attr_classes)");
     // Step 1 (search.rs:89-116): the aids whose value matches
     if (args.regex) {
         for (const regex::Dfa &d : dfas.groups)

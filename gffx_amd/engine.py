@@ -811,6 +811,30 @@ def _cat(names) -> Tuple[bytes, np.ndarray]:
     return b"".join(nb), off
 
 
+def _bitmap_indices(fn, handle, words: int) -> np.ndarray:
+    """the set bits of the `words` 64-bit words that fn (a gffx_hip_*_copy_*_bitmap) downloads, ascending"""
+    w = np.zeros(max(words, 1), np.uint64)
+    check(fn(handle, w.ctypes.data_as(u64p), words))
+    return np.flatnonzero(np.unpackbits(w[:words].view(np.uint8), bitorder="little")).astype(np.uint32)
+
+
+def _filter_lines(fn, handle, text: bytes, line_off, line_root, types) -> np.ndarray:
+    """one call of fn (a gffx_hip_*_filter_lines): keep[i] of the lines text[line_off[i]:line_off[i + 1]]"""
+    lo = np.ascontiguousarray(line_off, dtype=np.uint64)
+    lr = _u32(line_root)
+    n = len(lr)
+    if len(lo) != n + 1:
+        raise ValueError("line_off needs one entry more than line_root")
+    keep = np.zeros(max(n, 1), np.uint8)
+    tb, toff = _cat(types or [])
+    toff32 = toff.astype(np.uint32)
+    buf, ptr = _u8(text)
+    tbuf, tptr = _u8(tb)
+    check(fn(handle, ptr, len(text), n, lo.ctypes.data_as(u64p), _p(lr) if n else None, int(types is not None), len(toff) - 1, tptr,
+             _p(toff32), keep.ctypes.data_as(_ffi.u8p)))
+    return keep[:n]
+
+
 class FeatureIds:
     """gffx_hip_ids_*: the feature-ID table of `.fts` with the parent pointers of `.prt` on the device (the reference's FtsMap +
     PrtMap, index_loader/fts.rs:9-93, prt.rs:18-102).  A name's fid is the LAST line that holds it; a fid's root is where the
@@ -869,9 +893,7 @@ class FeatureIds:
         return fids[:nq], roots[:nq]
 
     def _bits(self, fn) -> np.ndarray:
-        w = np.zeros(max(self._words, 1), np.uint64)
-        check(fn(self._h, w.ctypes.data_as(u64p), self._words))
-        return np.flatnonzero(np.unpackbits(w[:self._words].view(np.uint8), bitorder="little")).astype(np.uint32)
+        return _bitmap_indices(fn, self._h, self._words)
 
     def unique_roots(self) -> np.ndarray:
         return self._bits(lib().gffx_hip_ids_copy_root_bitmap)
@@ -886,20 +908,7 @@ class FeatureIds:
         """keep[i] for line i = text[line_off[i]:line_off[i + 1]] (whole lines back to back, each with its line ending) in the
         block of root line_root[i]: write_gff_output_filtered's test with the key "ID" (utils/common.rs:418-431).  types: None,
         or the allowed column-3 names (-T already split at ',', trimmed, the empty ones dropped; an empty list keeps nothing)."""
-        lo = np.ascontiguousarray(line_off, dtype=np.uint64)
-        lr = _u32(line_root)
-        n = len(lr)
-        if len(lo) != n + 1:
-            raise ValueError("line_off needs one entry more than line_root")
-        keep = np.zeros(max(n, 1), np.uint8)
-        tb, toff = _cat(types or [])
-        toff32 = toff.astype(np.uint32)
-        buf, ptr = _u8(text)
-        tbuf, tptr = _u8(tb)
-        check(lib().gffx_hip_ids_filter_lines(self._h, ptr, len(text), n, lo.ctypes.data_as(u64p), _p(lr) if n else None,
-                                              int(types is not None), len(toff) - 1, tptr, _p(toff32),
-                                              keep.ctypes.data_as(_ffi.u8p)))
-        return keep[:n]
+        return _filter_lines(lib().gffx_hip_ids_filter_lines, self._h, text, line_off, line_root, types)
 
     def stage_ms(self) -> Dict[str, float]:
         v = [C.c_double() for _ in range(3)]
@@ -1032,9 +1041,7 @@ class AttrSearch:
         check(lib().gffx_hip_attrs_resolve(self._h))
 
     def _bits(self, fn, words) -> np.ndarray:
-        w = np.zeros(max(words, 1), np.uint64)
-        check(fn(self._h, w.ctypes.data_as(u64p), words))
-        return np.flatnonzero(np.unpackbits(w[:words].view(np.uint8), bitorder="little")).astype(np.uint32)
+        return _bitmap_indices(fn, self._h, words)
 
     def matched_aids(self) -> np.ndarray:
         return self._bits(lib().gffx_hip_attrs_copy_matched_bitmap, self._mwords)
@@ -1052,19 +1059,7 @@ class AttrSearch:
         """keep[i] for line i = text[line_off[i]:line_off[i + 1]] in the block of root line_root[i]: write_gff_output_filtered's
         test with the key `<attribute name>` (utils/common.rs:418-431) against the pairs of the last resolve().  types as for
         FeatureIds.filter_lines."""
-        lo = np.ascontiguousarray(line_off, dtype=np.uint64)
-        lr = _u32(line_root)
-        n = len(lr)
-        if len(lo) != n + 1:
-            raise ValueError("line_off needs one entry more than line_root")
-        keep = np.zeros(max(n, 1), np.uint8)
-        tb, toff = _cat(types or [])
-        toff32 = toff.astype(np.uint32)
-        buf, ptr = _u8(text)
-        tbuf, tptr = _u8(tb)
-        check(lib().gffx_hip_attrs_filter_lines(self._h, ptr, len(text), n, lo.ctypes.data_as(u64p), _p(lr) if n else None,
-                                                int(types is not None), len(toff) - 1, tptr, _p(toff32), keep.ctypes.data_as(_ffi.u8p)))
-        return keep[:n]
+        return _filter_lines(lib().gffx_hip_attrs_filter_lines, self._h, text, line_off, line_root, types)
 
     def stage_ms(self) -> Dict[str, float]:
         v = [C.c_double() for _ in range(4)]

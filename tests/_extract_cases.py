@@ -45,3 +45,28 @@ FILTER_LINES = [                        # (line, kept without -T)
     (NINE + b"ID=x", 1),                              # the last line has no newline
 ]
 TYPE_CASES = [None, " exon , CDS,,\t", ",", "gene", "exon,gene"]
+
+
+def refused_chunks(fn, who, handle):
+    """the four chunks the front half of a filter_lines call refuses, through fn (gffx_hip_ids_filter_lines or
+    gffx_hip_attrs_filter_lines of _ffi.lib()) on a live handle: [(return code, last error, the message it has to be)]"""
+    import numpy as np
+    from gffx_amd import _ffi
+    text = np.frombuffer(b"abcdef\n", np.uint8).copy()
+    cases = [([0, 4, 2], 0, None, "line_off is not ascending at 1"),
+             ([0, len(text) + 1], 0, None, "the last line ends at 8, the text has 7 bytes"),
+             ([0, len(text)], 65537, [0] * 65538, "65537 type names (at most 65536)"),
+             ([0, len(text)], 2, [0, 3, 1], "type_off is not ascending at 1")]
+    out = []
+    for line_off, n_types, type_off, message in cases:
+        lo = np.array(line_off, np.uint64)
+        n = len(lo) - 1
+        root, keep = np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+        to = None if type_off is None else np.array(type_off, np.uint32)
+        rc = fn(handle, text.ctypes.data_as(_ffi.u8p), len(text), n, lo.ctypes.data_as(_ffi.u64p), root.ctypes.data_as(_ffi.u32p), 0, n_types,
+                text.ctypes.data_as(_ffi.u8p), None if to is None else to.ctypes.data_as(_ffi.u32p), keep.ctypes.data_as(_ffi.u8p))
+        out.append((rc, _ffi.lib().gffx_hip_last_error().decode(), "%s: %s" % (who, message)))
+    return out
+
+
+REUSE_SIZES = (65, 1, 0, 65)  # lines per call on one handle: past the wave edge at 64, one, none, and 65 again

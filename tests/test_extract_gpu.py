@@ -10,8 +10,10 @@ import numpy as np
 import pytest
 
 import _extract_oracle as xo
-from _extract_cases import FILTER_LINES, FILTER_NAMES, FILTER_PRT, FILTER_REQUESTED, TYPE_CASES, edge_names, edge_queries
-from gffx_amd import engine, synth
+import _index_cases as ic
+from _extract_cases import (FILTER_LINES, FILTER_NAMES, FILTER_PRT, FILTER_REQUESTED, REUSE_SIZES, TYPE_CASES, edge_names, edge_queries,
+                            refused_chunks)
+from gffx_amd import _ffi, engine, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -221,6 +223,47 @@ def test_one_line_of_a_megabyte(filter_ids):
     got = filter_ids.filter_lines(b"".join(lines), offsets(lines), [0] * 4)
     assert got.tolist() == [1, 0, 1, 1] == [int(xo.keeps_line(l, KEEP_OF_ROOT[0], None)) for l in lines]
     assert filter_ids.filter_lines(b"".join(lines), offsets(lines), [0] * 4, ["exon"]).tolist() == [1, 0, 1, 0]
+
+
+def test_filter_lines_refusals_on_a_live_handle(filter_ids):
+    for rc, message, want in refused_chunks(_ffi.lib().gffx_hip_ids_filter_lines, "gffx_hip_ids_filter_lines", filter_ids._h):
+        assert rc == -1 and message == want
+    lines = [l for l, _ in FILTER_LINES]
+    assert filter_ids.filter_lines(b"".join(lines), offsets(lines), [0] * len(lines)).tolist() == [k for _, k in FILTER_LINES]
+
+
+def test_a_handle_filters_chunks_of_65_1_0_and_65_lines():
+    ids = engine.FeatureIds.from_arrays(FILTER_NAMES, FILTER_PRT)
+    ids.resolve(FILTER_REQUESTED)
+    pool = [l for l, _ in FILTER_LINES][:-1] * 4  # (without the line that has no newline)
+    for n in REUSE_SIZES:
+        lines, roots = pool[:n], [(0, 4)[i % 2] for i in range(n)]
+        got = ids.filter_lines(b"".join(lines), offsets(lines), roots)
+        assert got.tolist() == [int(xo.keeps_line(l, KEEP_OF_ROOT[r], None)) for l, r in zip(lines, roots)], n
+        assert n != 65 or 0 < got.sum() < n
+    ids.close()
+
+
+@pytest.mark.parametrize("hash_bits", [-1, 0, 2])
+def test_the_last_row_of_an_id_and_the_first_row_of_a_value(hash_bits):
+    """the same 258 strings, two insert blocks, with the pairs (0, 256) and (255, 257) equal: as IDs the LAST row of a string
+    is its fid (the table keeps the largest), as attribute values they are numbered by their FIRST row (it keeps the smallest)"""
+    k = 1
+    names = ["s%03d" % i for i in range(256 + k + 1)]
+    names[256], names[256 + k] = names[0], names[255]
+    ids = engine.FeatureIds.from_arrays(names, np.arange(len(names), dtype=np.uint32), hash_bits=None if hash_bits < 0 else hash_bits)
+    fids, _ = ids.resolve(names)
+    ids.close()
+    idx = xo.fts_index([n.encode() for n in names])
+    assert fids.tolist() == [idx[n.encode()] for n in names] and fids[0] == 256 and fids[255] == 256 + k and fids[1] == 1
+    text = b"".join(ic.gene_line(i, id_=n, name=n) + b"\n" for i, n in enumerate(names))
+    kind, want = ic.oracle_outcome(text, "gene_name", ic.DEFAULT_SKIP)
+    assert kind == "ok" and want.a2f[256] == 0 and want.a2f[256 + k] == 255 and len(want.atn) == 256 and want.fid[0] == 256
+    g = engine.gff_index(text, "gene_name", ic.DEFAULT_SKIP, hash_bits=hash_bits)
+    try:
+        assert g.built().astuple() == ic.built_tuple(want)
+    finally:
+        g.close()
 
 
 # ---- the command --------------------------------------------------------------------------------------------------------

@@ -12,7 +12,8 @@ import pytest
 
 import _search_cases as sc
 import _search_oracle as so
-from gffx_amd import engine, synth
+from _extract_cases import REUSE_SIZES, refused_chunks
+from gffx_amd import _ffi, engine, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -230,6 +231,47 @@ def test_line_classes(filter_attrs, types, wanted):
         if wanted == ["TP53"] and root == 0 and types is None:
             assert got.tolist() == [k for _, k in sc.VALUE_LINES]  # fid 1 carries aid 2, the second TP53: the string keys the set
     assert a.filter_lines(b"", offsets([]), []).tolist() == []
+
+
+def test_filter_lines_refusals_on_a_live_handle(filter_attrs):
+    a, values, a2f, prt = filter_attrs
+    for rc, message, want in refused_chunks(_ffi.lib().gffx_hip_attrs_filter_lines, "gffx_hip_attrs_filter_lines", a._h):
+        assert rc == -1 and message == want
+    a.reset()
+    a.match(["TP53"])
+    a.resolve()
+    lines = [l for l, _ in sc.VALUE_LINES]
+    assert a.filter_lines(b"".join(lines), offsets(lines), [0] * len(lines)).tolist() == [k for _, k in sc.VALUE_LINES]
+
+
+@pytest.mark.parametrize("hash_bits", [None, 0])
+def test_a_handle_reused_across_sizes(hash_bits):
+    """257 values (two insert blocks, aids 255 and 256 the same string); a wanted table of 1024 slots, then one of 2; chunks of
+    65, 1, 0 and 65 lines"""
+    values = ["V%03d" % i for i in range(257)]
+    values[256] = values[255]
+    a2f = list(range(257))
+    prt = [f - f % 2 for f in range(257)]  # fid 2 k + 1 hangs under the root 2 k
+    a = engine.AttrSearch.from_arrays(values, a2f, prt, hash_bits=hash_bits)
+    many = values[0:256:2] + [values[255]] + ["W%d" % i for i in range(171)]
+    one = [values[1]]
+    assert len(many) == 300 and one[0] not in many
+    a.match(many)
+    assert a.matched_aids().tolist() == so.match_aids(values, many, False) and a.matched_aids().tolist()[-2:] == [255, 256]
+    a.reset()
+    a.match(one)
+    assert a.matched_aids().tolist() == so.match_aids(values, one, False) == [1]
+    a.match([values[255]])
+    a.resolve()
+    S = so.steps(values, a2f, prt, one + [values[255]], False)
+    assert sorted(S.per_root) == [0, 254, 256]
+    pool = [sc.NINE + b"ID=e%d;gene_name=%s\n" % (i, values[(1, 255, 2)[i % 3]].encode()) for i in range(65)]
+    for n in REUSE_SIZES:
+        lines, roots = pool[:n], [(0, 254, 256, 2)[i % 4] for i in range(n)]
+        got = a.filter_lines(b"".join(lines), offsets(lines), roots)
+        assert got.tolist() == [int(so.xo.keeps_line(l, S.per_root.get(r, set()), None, b"gene_name")) for l, r in zip(lines, roots)], n
+        assert n != 65 or 0 < got.sum() < n
+    a.close()
 
 
 # ---- the command ----------------------------------------------------------------------------------------------------------------

@@ -162,7 +162,7 @@ def main():
     print("gffx extract on %d GFF lines (%.1f MB), %d table names; %d timed runs after one warm-up, median [min .. max]"
           % (n_lines, res["gff_MB"], len(names), a.repeats))
     b = res["build_ms"]
-    print("table build (k_ids_fill + k_ids_insert)  %.3f ms [%.3f .. %.3f]   algorithm bytes %.1f MB = %s %% of 8 TB/s"
+    print("table build (k_table_fill + k_table_insert)  %.3f ms [%.3f .. %.3f]   algorithm bytes %.1f MB = %s %% of 8 TB/s"
           % (b["median"], b["min"], b["max"], res["build_algorithm_bytes"] / 1e6, res["build_share_of_8TBps_pct"]))
     for size, o in res["lists"].items():
         r, f, h = o["resolve_ms"], o["filter_ms"], o["host_one_core"]

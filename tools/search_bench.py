@@ -120,7 +120,7 @@ def main():
                 else:
                     med, lo, hi = timed(h, "match", lambda: h.match(pats), a.repeats)
                     groups = 1
-                    what = "k_attr_insert + k_attr_match_exact"
+                    what = "k_table_insert + k_attr_match_exact"
                 limit = a.baseline_values if regex and k * n > 2e8 else 0
                 b = host_baseline(gff + ".atn", lst, "regex" if regex else "exact", limit)
                 scale = b["values"] / max(b["values_used"], 1)
