@@ -128,6 +128,14 @@ SIGNATURES = {
     "gffx_hip_sam_stage_ms": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gffx_hip_sam_copy_rows": (C.c_int, [vp, u32p]),
     "gffx_hip_sam_destroy": (None, [vp]),
+    "gffx_hip_bed_create": (C.c_int, [C.c_int, C.c_uint32, C.c_char_p, u64p, C.c_int, C.c_uint64, C.c_int, C.POINTER(vp)]),
+    "gffx_hip_bed_feed": (C.c_int, [vp, u8p, C.c_uint64]),
+    "gffx_hip_bed_finish": (C.c_int, [vp]),
+    "gffx_hip_bed_rows": (C.c_uint64, [vp]),
+    "gffx_hip_bed_counts": (C.c_int, [vp, u64p, u64p, u64p, u64p]),
+    "gffx_hip_bed_stage_ms": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gffx_hip_bed_copy_rows": (C.c_int, [vp, u32p]),
+    "gffx_hip_bed_destroy": (None, [vp]),
     "gffx_hip_ids_create": (C.c_int, [C.c_int, C.c_uint64, u8p, u64p, C.c_uint64, u32p, C.c_int, C.POINTER(vp)]),
     "gffx_hip_ids_destroy": (None, [vp]),
     "gffx_hip_ids_n": (C.c_uint64, [vp]),

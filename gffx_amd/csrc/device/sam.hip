@@ -15,9 +15,9 @@
 //   k_sam_rows       one wave per tile, over the lines that end in the tile: validate (sam_record), keep or skip, and compact
 //                    the kept rows in file order (count pass, scan over the tiles, write pass) -- the shape of k_bam_rows.
 // Staging, the sub-batches (BGZF members as in bgzf.hip, or plain text in pieces of chunk_bytes), the drain's sync, rows
-// and carry, and the sticky failure are the pipeline of source_stream.hpp, shared with bgzf.hip; this file keeps the
-// kernels, their enqueue, the pending text, the check of SamResult in the middle of the drain (the first malformed line)
-// and _finish (a last line without '\n').
+// and carry, and the sticky failure are the pipeline of source_stream.hpp, shared with bgzf.hip and bed.hip; the two line
+// kernels are line_scan.hpp's, shared with bed.hip; this file keeps k_sam_rows, the enqueue, the pending text, the check of
+// SamResult in the middle of the drain (the first malformed line) and _finish (a last line without '\n').
 //
 // LANE SHARING in k_sam_rows: one lane per line, and the lane runs sam_record() as the host does.  Reason: there is one code
 // path for a 60-byte line, a 1 MB line and a CIGAR of 70,000 operations -- the one tools/sam_check.cpp runs under the
@@ -35,14 +35,13 @@
 #include <string>
 #include <vector>
 
+#include "line_scan.hpp"  // kTile, kMaxText, nl_bits, k_sam_line_count, k_sam_line_list (shared with bed.hip)
 #include "source_stream.hpp"
 #include "sam_core.hpp"
 
 namespace gffx {
 
-constexpr uint32_t kTile = 4096;               // bytes per tile: 4 steps of 64 lanes x 16 bytes
 constexpr u64 kNoBad = 0xFFFFFFFFFFFFFFFFull;
-constexpr u64 kMaxText = 0xFFFFFFF0ull;        // a chunk with its carry: line ends are 32-bit offsets
 
 struct SamResult {  // what the host reads back after a chunk (pinned)
     u64 bad;            // (line in the chunk << 8) | sam::Reason of the malformed line with the lowest index (kNoBad: none)
@@ -53,85 +52,6 @@ struct SamResult {  // what the host reads back after a chunk (pinned)
     uint32_t bad_block; // first member that failed to inflate (UINT32_MAX: none)
     uint32_t pad;
 };
-
-// bit i = D[off + i] == '\n', i < 16, off + i < N (off: a multiple of 16; D: 16-byte aligned)
-__device__ __forceinline__ uint32_t nl_bits(const uint8_t *D, u64 N, u64 off) {
-    uint32_t m = 0;
-    if (off + 16 <= N) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(D + off);
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t x = w[k] ^ 0x0A0A0A0Au;
-            const uint32_t z = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);  // 0x80 in exactly the zero bytes of x
-            m |= (((z >> 7) * 0x10204080u) >> 28) << (4 * k);                            // bits 0, 8, 16, 24 -> 0 .. 3
-        }
-    } else {
-        for (uint32_t i = 0; off + i < N; ++i)
-            if (D[off + i] == '\n') m |= 1u << i;
-    }
-    return m;
-}
-// the bits of positions >= start
-__device__ __forceinline__ uint32_t from_start(uint32_t m, u64 off, u64 start) {
-    if (off >= start) return m;
-    return start - off >= 16 ? 0u : m & ~((1u << (uint32_t)(start - off)) - 1u);
-}
-
-// one wave per tile: count[t] = the '\n' at or after `start` in tile t (+ 1 in the last tile when final_line: the line end
-// at N); the header's '\n' into res->header_lines; res->tail = one past the last listed '\n' (the host set it to start)
-__global__ __launch_bounds__(64) void k_sam_line_count(const uint8_t *D, u64 N, u64 start, uint32_t n_tiles, int final_line,
-                                                       uint32_t *count, SamResult *res) {
-    const uint32_t t = blockIdx.x, lane = threadIdx.x;
-    if (t >= n_tiles || res->bad_block != 0xFFFFFFFFu) return;
-    uint32_t c = 0, hdr = 0;
-    u64 last = 0;
-    for (uint32_t it = 0; it < kTile / 1024; ++it) {
-        const u64 off = (u64)t * kTile + it * 1024 + lane * 16;
-        if (off >= N) break;
-        const uint32_t all = nl_bits(D, N, off), m = from_start(all, off, start);
-        c += __popc(m);
-        hdr += __popc(all ^ m);
-        if (m) last = off + (31 - __clz(m)) + 1;
-    }
-    for (int d = 32; d; d >>= 1) {
-        c += __shfl_xor(c, d);
-        hdr += __shfl_xor(hdr, d);
-        const u64 o = __shfl_xor(last, d);
-        last = o > last ? o : last;
-    }
-    if (lane == 0) {
-        count[t] = c + ((final_line && t == n_tiles - 1) ? 1u : 0u);
-        if (hdr) atomicAdd(&res->header_lines, (u64)hdr);
-        if (last) atomicMax(&res->tail, last);
-    }
-}
-
-// one wave per tile: nl[base[t] ..) = the offsets of the tile's listed '\n' in order (and N after them: see k_sam_line_count)
-__global__ __launch_bounds__(64) void k_sam_line_list(const uint8_t *D, u64 N, u64 start, uint32_t n_tiles, int final_line,
-                                                      const u64 *base, uint32_t *nl, const SamResult *res) {
-    const uint32_t t = blockIdx.x, lane = threadIdx.x;
-    if (t >= n_tiles || res->bad_block != 0xFFFFFFFFu) return;
-    u64 o = base[t];
-    for (uint32_t it = 0; it < kTile / 1024; ++it) {  // (wave-uniform trip count: the shuffles below need every lane)
-        const u64 off = (u64)t * kTile + it * 1024 + lane * 16;
-        uint32_t m = off < N ? from_start(nl_bits(D, N, off), off, start) : 0u;
-        const uint32_t mine = __popc(m);
-        uint32_t incl = mine;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t v = __shfl_up(incl, d);
-            if ((int)lane >= d) incl += v;
-        }
-        u64 at = o + incl - mine;
-        while (m) {
-            const uint32_t b = __ffs(m) - 1;
-            m &= m - 1;
-            nl[at++] = (uint32_t)(off + b);
-        }
-        o += __shfl(incl, 63);
-    }
-    if (final_line && t == n_tiles - 1 && lane == 0) nl[o] = (uint32_t)N;
-}
 
 // one wave per tile, one lane per line that ends in the tile.  WRITE = 0: kept rows per tile into kept_n, the skip tallies,
 // the malformed line with the lowest index (atomicMin: the same line whatever the order the waves run in).  WRITE = 1: the
@@ -253,9 +173,9 @@ int enqueue(gffx_hip_sam *h, int k, uint32_t nb, uint64_t T, uint64_t file_off, 
         GFFX_HIP_TRY(hipMemcpyAsync(D + C, S.in[k].p, T, hipMemcpyDeviceToDevice, s));
     }
     GFFX_HIP_TRY(hipEventRecord(S.ev[1], s));
-    hipLaunchKernelGGL(k_sam_line_count, dim3(n_tiles), dim3(64), 0, s, D, N, start, n_tiles, final_line, h->count.p, res);
+    hipLaunchKernelGGL(k_sam_line_count<SamResult>, dim3(n_tiles), dim3(64), 0, s, D, N, start, n_tiles, final_line, h->count.p, res);
     launch_scan(s, h->count.p, n_tiles, h->line_base.p, &res->lines);
-    hipLaunchKernelGGL(k_sam_line_list, dim3(n_tiles), dim3(64), 0, s, D, N, start, n_tiles, final_line, h->line_base.p, h->nl.p, res);
+    hipLaunchKernelGGL(k_sam_line_list<SamResult>, dim3(n_tiles), dim3(64), 0, s, D, N, start, n_tiles, final_line, h->line_base.p, h->nl.p, res);
     GFFX_HIP_TRY(hipGetLastError());
     GFFX_HIP_TRY(hipEventRecord(S.ev[2], s));
     const sam::Names names{h->table.p, h->name_bytes.p, h->table_mask};

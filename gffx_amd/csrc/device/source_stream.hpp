@@ -1,4 +1,4 @@
-// source_stream.hpp -- the streaming pipeline of the source readers (bgzf.hip: BAM, sam.hip: SAM), once: what a handle owns
+// source_stream.hpp -- the streaming pipeline of the source readers (bgzf.hip: BAM, sam.hip: SAM, bed.hip: BED), once: what a handle owns
 // and does whatever the format of its bytes.
 //
 // Fed bytes go to the device in sub-batches.  Staging is double-buffered: while the kernels work on one sub-batch, the host
@@ -47,7 +47,7 @@ struct SourceStream {
     uint64_t fl_file_off = 0;
     // results
     std::vector<uint32_t> out_rows;
-    uint64_t unmapped = 0, no_seq = 0, kept = 0;
+    uint64_t unmapped = 0, no_seq = 0, kept = 0;  // (unmapped: the format's first skip tally; BED: the skipped lines)
     double ms[3] = {0, 0, 0};  // ev[0] .. ev[1] (inflate), ev[1] .. ev[2], ev[2] .. ev[3]
     int error = GFFX_OK;
     std::string error_msg;

@@ -175,6 +175,13 @@ SourceKind source_kind(const std::string &path) {
     std::string ext;
     if (dot != std::string::npos && dot > 0) ext = base.substr(dot + 1);
     for (char &c : ext) c = static_cast<char>(std::tolower(static_cast<unsigned char>(c)));
+    if (ext == "gz" || ext == "bgz") {  // x.bed.gz / x.bed.bgz: a bgzip-compressed BED file (bed.cpp reads it on the device)
+        const std::string stem = base.substr(0, dot);
+        const size_t d2 = stem.find_last_of('.');
+        std::string inner = d2 != std::string::npos && d2 > 0 ? stem.substr(d2 + 1) : std::string();
+        for (char &c : inner) c = static_cast<char>(std::tolower(static_cast<unsigned char>(c)));
+        if (inner == "bed") return SourceKind::Bed;
+    }
     if (ext == "cram")
         throw Error("SAM/CRAM sources need htslib, which this build does not carry; use a .bam or .bed source");
     if (ext != "bed" && ext != "bam" && ext != "sam")
@@ -185,7 +192,10 @@ SourceKind source_kind(const std::string &path) {
 SourceRows read_source_rows(SourceKind kind, const std::string &path, const std::unordered_map<std::string, uint32_t> &seqid_to_num,
                             size_t threads, int device, bool verbose, DeviceWarmup &warm) {
     SourceRows r;
-    if (kind == SourceKind::Bed) {
+    if (kind == SourceKind::Bed && bed::route(path) == bed::Route::Device) {
+        warm.wait();  // the same rules on the device (bed_core.hpp kDepth): BGZF-compressed text, or GFFX_BED_DEVICE=1
+        r.part.push_back(bed::read_rows(path, seqid_to_num, bed::kDepth, device, verbose));
+    } else if (kind == SourceKind::Bed) {
         r.part = parse_bed_rows_flat(path, seqid_to_num, threads);  // depth.rs:450-495, coverage.rs:230-256
     } else {
         warm.wait();  // depth.rs:297-372, coverage.rs:125-168: the same (chr, start, end) rows, from BAM records or SAM lines

@@ -343,7 +343,7 @@ inline const char *source_lap(SourceKind k, bool with_index) {
         default: return with_index ? "Loading index + parsing BED" : "Parsing BED";
     }
 }
-SourceKind source_kind(const std::string &path);  // depth.rs:590-601 / coverage.rs:520-541: by the extension, any letter case; others: Error
+SourceKind source_kind(const std::string &path);  // depth.rs:590-601 / coverage.rs:520-541: by the extension, any letter case (.bed.gz / .bed.bgz: Bed); others: Error
 // the kept rows of a source as flat (seqid number, start, end) words, one vector per parsed piece, in file order
 struct SourceRows {
     std::vector<std::vector<uint32_t>> part;
@@ -352,7 +352,8 @@ struct SourceRows {
     // rows [a, a + n) of the file into stage: the tails / heads of the pieces they lie in, copied by up to `threads` threads
     void fill(uint32_t *stage, size_t a, size_t n, size_t threads) const;
 };
-// ... of a .bed (on `threads` host threads), a .bam or a .sam (read on `device` once `warm` is through)
+// ... of a .bed (on `threads` host threads; BGZF-compressed, or with GFFX_BED_DEVICE=1, on `device`: bed::route), a .bam or a
+// .sam (read on `device` once `warm` is through)
 SourceRows read_source_rows(SourceKind kind, const std::string &path, const std::unordered_map<std::string, uint32_t> &seqid_to_num,
                             size_t threads, int device, bool verbose, DeviceWarmup &warm);
 // Device d's share of the rows (of D devices, round robin in batches of kBatch) through its region store.  Batch i goes
@@ -475,6 +476,20 @@ namespace sam {
 std::vector<uint32_t> read_rows(const std::string &path, const std::unordered_map<std::string, uint32_t> &seqid_to_num, int device,
                                 bool verbose);
 }  // namespace sam
+
+// ---- BED sources read on the device (bed.cpp; the host parsers stay the default for plain text) --------------------------
+namespace bed {
+enum Dialect : int { kIntersect = 0, kDepth = 1 };  // GFFX_BED_INTERSECT / GFFX_BED_DEPTH: bed_parse.cpp's rules, depth.cpp's rules
+enum class Route { Host, Device };
+// By content: a file that begins with the gzip magic goes to the device reader (BGZF; plain gzip is refused there), other
+// text to the host parser unless GFFX_BED_DEVICE is set to something other than 0.  A file that does not open: Host.
+Route route(const std::string &path);
+// the kept (seqid number, start, end) rows of a BED file, flat, in file order, by the rules of `dialect` (lines, fields and
+// numbers read on `device`).  GFFX_BED_CHUNK_BYTES sets the fed bytes per device pass (default 64 MiB).  Throws Error: for a
+// malformed line (kIntersect) with the host parser's message.
+std::vector<uint32_t> read_rows(const std::string &path, const std::unordered_map<std::string, uint32_t> &seqid_to_num, int dialect,
+                                int device, bool verbose);
+}  // namespace bed
 
 // main.rs: `gffx <index|intersect|extract|search|depth|coverage> ...`; returns the process exit code
 int cli_main(int argc, char **argv);

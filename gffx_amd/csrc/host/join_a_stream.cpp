@@ -299,10 +299,14 @@ StreamResult stream_unique_roots(TreeIndexData &index_data, const std::string &b
                                  size_t threads, int device, int n_gpus, bool keep_store) {
     StreamResult res;
     StageTimer sub{verbose};
+    // BGZF-compressed, or GFFX_BED_DEVICE=1: the device reader's rows (bed.cpp) enter below as parsed chunks, a second
+    // producer beside ChunkParser
+    const bool device_rows = bed::route(bed_path) == bed::Route::Device;
     MappedFile f(bed_path);
     const std::string_view text = f.view();
     const SeqidTable seqids(index_data.seqid_to_num);
-    ChunkParser parser(text, seqids, threads);
+    std::optional<ChunkParser> parser;
+    if (!device_rows) parser.emplace(text, seqids, threads);
     DeviceSet devs = DeviceSet::resolve(device, n_gpus);
     const size_t D = devs.size();
     if (verbose) {  // (only to tell the process's one-off HIP costs from the index's in the stage timers)
@@ -314,15 +318,32 @@ StreamResult stream_unique_roots(TreeIndexData &index_data, const std::string &b
     for (size_t d = 0; d < D; ++d) ix[d] = devs.index_on(d, index_data.device_index.get());
     sub.lap("  index upload");
     const uint32_t n_seq = static_cast<uint32_t>(index_data.num_to_seqid.size());
-    const size_t chunk_rows = std::min(kChunkBytes, std::max<size_t>(text.size(), 1)) / kMinRowBytes + 16;
-    Lanes lanes = create_lanes(devs, ix, chunk_rows, keep_store ? text.size() / kMinRowBytes + 16 : 0);
+    std::vector<uint32_t> all_rows;  // device_rows: the file's rows (device -> host -> region stores, as BAM and SAM rows travel)
+    if (device_rows) {
+        all_rows = bed::read_rows(bed_path, index_data.seqid_to_num, bed::kIntersect, devs[0], verbose);
+        sub.lap("  BED rows read on the device");
+    }
+    const size_t n_all = all_rows.size() / 3, per_chunk = kChunkBytes / kMinRowBytes;
+    const size_t chunk_rows = device_rows ? std::min(per_chunk, std::max<size_t>(n_all, 1)) + 16
+                                          : std::min(kChunkBytes, std::max<size_t>(text.size(), 1)) / kMinRowBytes + 16;
+    Lanes lanes = create_lanes(devs, ix, chunk_rows, !keep_store ? 0 : device_rows ? n_all + 16 : text.size() / kMinRowBytes + 16);
+    size_t served = 0;
+    auto next_chunk = [&]() {
+        if (!device_rows) return parser->next();
+        ChunkParser::Parsed pc;
+        const size_t take = std::min(chunk_rows - 16, n_all - served);
+        pc.piece.emplace_back(all_rows.begin() + 3 * served, all_rows.begin() + 3 * (served + take));
+        served += take;
+        pc.last = served == n_all;
+        return pc;
+    };
     sub.lap("  region stores + batches");
     res.knobs = knobs_json(ix[0], lanes.batch[0].get());
     res.has_regions.assign(n_seq, 0);
     double t_fill = 0;
     for (size_t chunk = 0;; ++chunk) {
         const int k = static_cast<int>(chunk & 1);
-        ChunkParser::Parsed pc = parser.next();
+        ChunkParser::Parsed pc = next_chunk();
         const auto t1 = std::chrono::steady_clock::now();
         wait_staging(lanes, k);
         std::vector<uint64_t> n_dev(D, 0);
@@ -334,12 +355,12 @@ StreamResult stream_unique_roots(TreeIndexData &index_data, const std::string &b
             scatter_chunk_by_bucket(pc.piece, n_seq, keep_store, stage, n_dev, res.has_regions);
         }
         t_fill += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
-        parser.recycle(std::move(pc.piece));  // the rows are in the staging buffers: the parser may fill these vectors again
+        if (parser) parser->recycle(std::move(pc.piece));  // the rows are in the staging buffers: the parser may fill these vectors again
         res.n_regions += launch_chunk(lanes, k, n_dev, keep_store, mode, invert, res.wide_form_passes);
         if (pc.last) break;
     }
-    const double t_parse = parser.finish();  // (it pushed its last chunk)
-    if (verbose) {
+    const double t_parse = parser ? parser->finish() : 0;  // (it pushed its last chunk)
+    if (verbose && parser) {
         std::fprintf(stderr, "[TIMER] [run]   BED text parsing (host threads) took %.3f ms\n", t_parse);
         std::fprintf(stderr, "[TIMER] [run]   filling the pinned staging buffers took %.3f ms\n", t_fill);
     }

@@ -686,7 +686,7 @@ def bgzf_members(data: bytes) -> List[int]:
 
 
 class _SourceReader:
-    """What BamReader and SamReader share: the gffx_hip_<stem>_* calls on one handle (device/source_stream.hpp is the
+    """What BamReader, SamReader and BedReader share: the gffx_hip_<stem>_* calls on one handle (device/source_stream.hpp is the
     pipeline behind both).  A subclass creates self._h and names the four tallies and the three stages of its format."""
     _stem = ""
     _count_keys: Tuple[str, ...] = ()
@@ -787,6 +787,47 @@ def sam_rows(data: bytes, names, ref_seq, header_bytes: int, chunk_bytes: int = 
             for i in range(0, len(off) - 1, feed_members):
                 r.feed(data[off[i]:off[min(i + feed_members, len(off) - 1)]])
         elif not bgzf and feed_bytes > 0:
+            for i in range(0, len(data), feed_bytes):
+                r.feed(data[i:i + feed_bytes])
+        else:
+            r.feed(data)
+        r.finish()
+        if counts is not None:
+            counts.update(r.counts())
+        return r.rows()
+    finally:
+        r.close()
+
+
+# ---- BED sources (include/gffx_hip.h "BED sources"; device/bed.hip) ----------------------------------------------------
+BED_INTERSECT, BED_DEPTH = 0, 1  # the dialects: host/bed_parse.cpp (`gffx intersect`), host/depth.cpp (`gffx depth` / `coverage`)
+
+
+class BedReader(_SourceReader):
+    """gffx_hip_bed_*: the kept (seqid, start, end) rows of a BED stream, plain text or BGZF-compressed (bgzf=True), by the
+    rules of one of the two host parsers (dialect).  names[i] = the name of seqid number i."""
+    _stem, _count_keys, _stage_keys = "bed", ("lines", "skipped", "no_seq", "kept"), ("inflate", "lines", "rows")
+
+    def __init__(self, names, dialect: int, chunk_bytes: int = 0, bgzf: bool = False, device: int = 0):
+        nb = [n if isinstance(n, (bytes, bytearray)) else str(n).encode() for n in names]
+        off = np.zeros(len(nb) + 1, np.uint64)
+        off[1:] = np.cumsum([len(n) for n in nb], dtype=np.uint64) if nb else 0
+        self._h = C.c_void_p()
+        check(lib().gffx_hip_bed_create(device, len(nb), b"".join(nb), off.ctypes.data_as(_ffi.u64p), int(dialect), chunk_bytes,
+                                        int(bool(bgzf)), C.byref(self._h)))
+
+
+def bed_rows(data: bytes, names, dialect: int, chunk_bytes: int = 0, bgzf: bool = False, feed_bytes: int = 0, device: int = 0,
+             counts: Optional[dict] = None) -> np.ndarray:
+    """The rows of a whole BED stream in file order.  feed_bytes > 0: plain text fed in pieces of that many bytes, BGZF one
+    member per call.  counts: filled with BedReader.counts()."""
+    r = BedReader(names, dialect, chunk_bytes, bgzf, device)
+    try:
+        if bgzf and feed_bytes > 0:
+            off = bgzf_members(data)
+            for i in range(len(off) - 1):
+                r.feed(data[off[i]:off[i + 1]])
+        elif feed_bytes > 0:
             for i in range(0, len(data), feed_bytes):
                 r.feed(data[i:i + feed_bytes])
         else:

@@ -22,6 +22,7 @@
  *   bam::Reader records -> (chr, start, end) rows        gffx_hip_bgzf_inflate, gffx_hip_bam_* (BAM sources)
  *     (commands/depth.rs:297-372, coverage.rs:125-168)
  *   the same reader on a .sam file                       gffx_hip_sam_* (SAM sources, plain or BGZF-compressed)
+ *   BED text, plain or BGZF-compressed, to rows          gffx_hip_bed_* (BED sources, the two dialects of the commands)
  *     (commands/depth.rs:588-591, coverage.rs:520-541)
  *   FtsMap::map_fnames_to_fids, PrtMap::map_fids_to_roots, gffx_hip_ids_* (`gffx extract`)
  *   the ID test of write_gff_output_filtered
@@ -182,6 +183,7 @@ typedef struct gffx_hip_regions gffx_hip_regions;
 typedef struct gffx_hip_depth gffx_hip_depth;
 typedef struct gffx_hip_bam gffx_hip_bam;
 typedef struct gffx_hip_sam gffx_hip_sam;
+typedef struct gffx_hip_bed gffx_hip_bed;
 typedef struct gffx_hip_union gffx_hip_union;
 
 int gffx_hip_abi_version(void);
@@ -532,6 +534,45 @@ int gffx_hip_sam_counts(const gffx_hip_sam *, uint64_t *lines, uint64_t *unmappe
 int gffx_hip_sam_stage_ms(const gffx_hip_sam *, double *inflate_ms, double *lines_ms, double *rows_ms);
 int gffx_hip_sam_copy_rows(gffx_hip_sam *, uint32_t *rows /* 3 per row */);
 void gffx_hip_sam_destroy(gffx_hip_sam *);
+
+/* ---- BED sources of `gffx intersect -b`, `gffx depth -s` and `gffx coverage -s`: the text is cut into lines, the lines ----
+ * into fields, the two coordinates are read and the name is looked up on the device (device/bed.hip; the rules of one line,
+ * device/bed_core.hpp, are shared with the host).  The text is plain, or BGZF-compressed (bgzf != 0): then its members are
+ * inflated on the device as for BAM and the inflated bytes never leave it.
+ *
+ * _create takes the index's seqids in order: seqid number i's name is names[name_off[i], name_off[i + 1]) (no terminator);
+ * a name that occurs twice fails the call.  chunk_bytes bounds the fed bytes per device pass (0: 64 MiB).  dialect names
+ * the host parser whose rules hold, checked in this order:
+ *   GFFX_BED_INTERSECT (commands/intersect.rs:201-230): lines are the pieces between '\n'.  Empty or first byte '#':
+ *     skipped.  The whole line not valid UTF-8 (overlong forms, surrogates and > U+10FFFF are invalid): ERROR "invalid
+ *     utf-8 sequence in BED line".  Fields split on space, \t, \x0C, \r (not \x0B); fewer than three: skipped.  A name
+ *     the table does not have: no_seq -- before the coordinates are looked at.  A coordinate is an optional '+', at least
+ *     one digit, the whole field, <= 4294967295; else ERROR `lexical parse error: invalid BED coordinate in "<the line>"`.
+ *     Rows with start >= end are kept.
+ *   GFFX_BED_DEPTH (commands/depth.rs:450-495, commands/coverage.rs:230-256): the line includes its '\n'.  Empty or '#':
+ *     skipped.  Fields split on \t and space only; fewer than three: skipped.  One of the three fields not valid UTF-8:
+ *     skipped.  Field 2 by the same number rule, field 3 the same after its trailing Unicode White_Space is cut; not a
+ *     number, or start >= end: skipped.  A name the table does not have: no_seq.  Nothing is an error.
+ * _feed takes the stream in file order from byte 0: text in pieces of any size, cut anywhere; BGZF in whole members.
+ * _finish reads a last line that does not end in '\n'.
+ * Rows are (seqid, start, end), 3 x u32 each, in file order.  An ERROR fails the call with GFFX_E_INVALID and exactly the
+ * message above, always for the first such line of the file; after it every call on the object, _copy_rows included,
+ * returns the same code and message.
+ * _counts: lines read, lines skipped, lines whose name the table does not have, rows kept; each line is tallied once, by
+ * the first rule of its dialect that decides it, so lines == skipped + no_seq + kept on a run without error.
+ * _stage_ms: device time of the inflate (plain text: the copy behind the unfinished line), the line scan and the rows
+ * kernels so far (HIP events). */
+#define GFFX_BED_INTERSECT 0
+#define GFFX_BED_DEPTH 1
+int gffx_hip_bed_create(int device, uint32_t n_seq, const char *names /* concatenated */, const uint64_t *name_off /* n_seq + 1 */,
+                        int dialect, uint64_t chunk_bytes, int bgzf, gffx_hip_bed **out);
+int gffx_hip_bed_feed(gffx_hip_bed *, const uint8_t *bytes, uint64_t n_bytes); /* bgzf: whole members; text: any split */
+int gffx_hip_bed_finish(gffx_hip_bed *);
+uint64_t gffx_hip_bed_rows(const gffx_hip_bed *);
+int gffx_hip_bed_counts(const gffx_hip_bed *, uint64_t *lines, uint64_t *skipped, uint64_t *no_seq, uint64_t *kept);
+int gffx_hip_bed_stage_ms(const gffx_hip_bed *, double *inflate_ms, double *lines_ms, double *rows_ms);
+int gffx_hip_bed_copy_rows(gffx_hip_bed *, uint32_t *rows /* 3 per row */);
+void gffx_hip_bed_destroy(gffx_hip_bed *);
 
 /* ---- `gffx extract`: feature-ID lookup, parent chase and the per-line ID filter (commands/extract.rs:37-162, ------------
  * index_loader/fts.rs:16-31, index_loader/prt.rs:54-72, utils/common.rs:289-465; device/ids.hip, the rules of one name,

@@ -34,6 +34,10 @@ pub struct gffx_hip_sam {
     _p: [u8; 0],
 }
 #[repr(C)]
+pub struct gffx_hip_bed {
+    _p: [u8; 0],
+}
+#[repr(C)]
 pub struct gffx_hip_ids {
     _p: [u8; 0],
 }
@@ -164,6 +168,25 @@ extern "C" {
     pub fn gffx_hip_sam_stage_ms(h: *const gffx_hip_sam, inflate_ms: *mut f64, lines_ms: *mut f64, rows_ms: *mut f64) -> c_int;
     pub fn gffx_hip_sam_copy_rows(h: *mut gffx_hip_sam, rows: *mut u32) -> c_int;
     pub fn gffx_hip_sam_destroy(h: *mut gffx_hip_sam);
+    // BED sources (intersect.rs:201-230, depth.rs:450-495, coverage.rs:230-256): lines, fields, coordinates and the name lookup on the
+    // device; plain or BGZF text; dialect 0 = intersect's parser, 1 = depth's and coverage's
+    pub fn gffx_hip_bed_create(
+        device: c_int,
+        n_seq: u32,
+        names: *const c_char,
+        name_off: *const u64,
+        dialect: c_int,
+        chunk_bytes: u64,
+        bgzf: c_int,
+        out: *mut *mut gffx_hip_bed,
+    ) -> c_int;
+    pub fn gffx_hip_bed_feed(h: *mut gffx_hip_bed, bytes: *const u8, n_bytes: u64) -> c_int;
+    pub fn gffx_hip_bed_finish(h: *mut gffx_hip_bed) -> c_int;
+    pub fn gffx_hip_bed_rows(h: *const gffx_hip_bed) -> u64;
+    pub fn gffx_hip_bed_counts(h: *const gffx_hip_bed, lines: *mut u64, skipped: *mut u64, no_seq: *mut u64, kept: *mut u64) -> c_int;
+    pub fn gffx_hip_bed_stage_ms(h: *const gffx_hip_bed, inflate_ms: *mut f64, lines_ms: *mut f64, rows_ms: *mut f64) -> c_int;
+    pub fn gffx_hip_bed_copy_rows(h: *mut gffx_hip_bed, rows: *mut u32) -> c_int;
+    pub fn gffx_hip_bed_destroy(h: *mut gffx_hip_bed);
     // `gffx extract` (extract.rs:37-162): the `.fts` ID table, name -> fid -> root (fts.rs:16-93, prt.rs:54-102) and the ID test of
     // write_gff_output_filtered (common.rs:389-431) on the device; u32::MAX = a name that is not found / a fid without a valid root
     pub fn gffx_hip_ids_create(
