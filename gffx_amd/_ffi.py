@@ -105,6 +105,16 @@ SIGNATURES = {
     "gffx_hip_union_segments_covered": (C.c_int, [vp, C.c_uint64, u32p, u32p, u32p, u32p]),
     "gffx_hip_union_stats": (C.c_int, [vp, C.POINTER(C.c_double), u64p, u64p]),
     "gffx_hip_union_destroy": (None, [vp]),
+    "gffx_hip_pileup_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint64, u32p, u32p, u32p, C.POINTER(vp)]),
+    "gffx_hip_pileup_add_host": (C.c_int, [vp, u32p, C.c_uint64]),
+    "gffx_hip_pileup_add_store": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64]),
+    "gffx_hip_pileup_copy": (C.c_int, [vp, u64p]),
+    "gffx_hip_pileup_reset": (C.c_int, [vp]),
+    "gffx_hip_pileup_stats": (C.c_int, [vp, C.POINTER(C.c_double), u64p, u64p]),
+    "gffx_hip_pileup_stage_ms": (C.c_int, [vp] + [C.POINTER(C.c_double)] * 4),
+    "gffx_hip_pileup_fold_rows": (C.c_uint64, []),
+    "gffx_hip_pileup_scan_tile": (C.c_uint32, []),
+    "gffx_hip_pileup_destroy": (None, [vp]),
     "gffx_hip_depth_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, u64p, u32p, u32p, u32p, C.c_uint32, u32p,
                                         C.POINTER(vp)]),
     "gffx_hip_depth_destroy": (None, [vp]),

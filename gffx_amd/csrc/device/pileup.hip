@@ -1,0 +1,512 @@
+// pileup.hip -- `gffx coverage --mean-depth`: the bases that the source rows lay on feature segments.
+//      bases(a, b) = sum over the rows [s, e) of the segment's seqid of max(0, min(e, b) - max(s, a))
+// The quantity is a sum over rows, so the rows may arrive in any grouping: every fold of at most kPileupFold rows adds its
+// own share to the segments' totals, nothing is folded between batches, and the totals of several devices are added as
+// integers.  One fold, on the pileup's own stream (pileup_core.hpp has the rule and why it needs no array over the bases):
+//   k_pileup_keys       rows {seqid, s, e} -> two W = 2 record arrays {seqid, s} and {seqid, e}; a row with s >= e or
+//                       seqid >= n_seq sets the error word (the union builder's bits: coverage.hip)
+//   DeviceSort x 2      each array by (seqid, coordinate), on its own (radix_sort.hpp)
+//   k_pileup_tile_sums  per tile of kPileupScanTile records the sum of the coordinates (both arrays: blockIdx.y)
+//   k_pileup_carry      one block per array: exclusive sum over the tiles (reduce-then-scan: nothing spins anywhere)
+//   k_pileup_apply      the coordinates as a plain u32 array and their n + 1 exclusive u64 prefix sums
+//   k_pileup_offsets    off[c] = the records with seqid < c, c = 0 .. n_seq: one search per seqid
+//   k_pileup_segments   one thread per segment (resident since _create, in the order given: neighbours search neighbouring
+//                       keys): four lower bounds inside [off[c], off[c + 1]), acc[i] += B(b) - B(a) as a plain 64-bit store.
+//                       The thread owns its segment and folds are serialised on the stream: no atomics.
+// Roofline bound: the sorts HBM (8 W bytes per record and pass), the segment kernel latency (dependent gathers, like Join A).
+#include <algorithm>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "gffx_device.hpp"
+#include "pileup_core.hpp"
+#include "radix_sort.hpp"
+#include "regions_store.hpp"
+
+namespace gffx {
+
+constexpr int kPileupThreads = 256;
+constexpr uint32_t kPileupScanTile = 4 * kPileupThreads;  // 4 consecutive records per thread: two 16-byte loads
+constexpr uint64_t kPileupFold = 4ull << 20;              // rows per fold (the default batch of `gffx coverage`)
+constexpr uint32_t kPileupErrRange = 2u;                  // err word: a row with seqid >= n_seq (the sort's own bit for it)
+constexpr uint32_t kPileupErrInverted = 8u;               // ... with start >= end (4 is the sort's time-out)
+
+// rows [i0, i0 + 4) -> their key records.  wide: `rows` is 16-byte aligned (a region-store slot that starts at a row that is
+// no multiple of four is not)
+__global__ __launch_bounds__(kPileupThreads) void k_pileup_keys(const uint32_t *rows, u64 n, uint32_t n_seq, int wide, uint32_t *ks, uint32_t *ke,
+                                                                uint32_t *err) {
+    const u64 i0 = 4ull * ((u64)blockIdx.x * kPileupThreads + threadIdx.x);
+    if (i0 >= n) return;
+    const bool full = i0 + 4 <= n;
+    uint32_t w[12];
+    if (full && wide) {
+        const uint4 *p = reinterpret_cast<const uint4 *>(rows + 3 * i0);
+        const uint4 a = p[0], b = p[1], c = p[2];
+        w[0] = a.x, w[1] = a.y, w[2] = a.z, w[3] = a.w, w[4] = b.x, w[5] = b.y, w[6] = b.z, w[7] = b.w, w[8] = c.x, w[9] = c.y,
+        w[10] = c.z, w[11] = c.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) w[k] = (i0 + k / 3 < n) ? rows[3 * i0 + k] : 0u;
+    }
+    bool inverted = false, range = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (i0 + j < n) {
+            inverted |= w[3 * j + 1] >= w[3 * j + 2];
+            range |= w[3 * j] >= n_seq;
+        }
+    if (full) {  // (32 i0 bytes into a hipMalloc'd buffer: 16-byte aligned)
+        uint4 *ps = reinterpret_cast<uint4 *>(ks + 2 * i0), *pe = reinterpret_cast<uint4 *>(ke + 2 * i0);
+        ps[0] = make_uint4(w[0], w[1], w[3], w[4]);
+        ps[1] = make_uint4(w[6], w[7], w[9], w[10]);
+        pe[0] = make_uint4(w[0], w[2], w[3], w[5]);
+        pe[1] = make_uint4(w[6], w[8], w[9], w[11]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (i0 + j < n) {
+                ks[2 * (i0 + j)] = w[3 * j], ks[2 * (i0 + j) + 1] = w[3 * j + 1];
+                ke[2 * (i0 + j)] = w[3 * j], ke[2 * (i0 + j) + 1] = w[3 * j + 2];
+            }
+    }
+    if (range) atomicOr(err, kPileupErrRange);
+    if (inverted) atomicOr(err, kPileupErrInverted);
+}
+
+// the coordinate words of records [i0, i0 + 4) of a sorted {seqid, coordinate} array (0 beyond n)
+__device__ __forceinline__ void pileup_load(const uint32_t *rec, u64 n, u64 i0, uint32_t (&c)[4]) {
+    if (i0 + 4 <= n) {
+        const uint4 *p = reinterpret_cast<const uint4 *>(rec + 2 * i0);
+        const uint4 a = p[0], b = p[1];
+        c[0] = a.y, c[1] = a.w, c[2] = b.y, c[3] = b.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) c[j] = i0 + j < n ? rec[2 * (i0 + j) + 1] : 0u;
+    }
+}
+
+// exclusive sum of v over the block's 256 threads; *total = the block's whole.  s_w: 4 words
+__device__ __forceinline__ u64 pileup_block_scan(u64 v, u64 *s_w, u64 *total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    u64 inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const u64 t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+    }
+    if (lane == 63) s_w[wave] = inc;
+    __syncthreads();
+    u64 base = 0, all = 0;
+#pragma unroll
+    for (int x = 0; x < kPileupThreads / 64; ++x) {
+        if (x < wave) base += s_w[x];
+        all += s_w[x];
+    }
+    *total = all;
+    return base + inc - v;
+}
+
+// blockIdx.y = 0: the starts, 1: the ends.  tile_sum[y * tiles + tile]
+__global__ __launch_bounds__(kPileupThreads) void k_pileup_tile_sums(const uint32_t *rec_s, const uint32_t *rec_e, u64 n, u64 *tile_sum) {
+    __shared__ u64 s_w[kPileupThreads / 64];
+    const uint32_t *rec = blockIdx.y ? rec_e : rec_s;
+    uint32_t c[4];
+    pileup_load(rec, n, (u64)blockIdx.x * kPileupScanTile + 4ull * threadIdx.x, c);
+    u64 total;
+    (void)pileup_block_scan((u64)c[0] + c[1] + c[2] + c[3], s_w, &total);
+    if (threadIdx.x == 0) tile_sum[(u64)blockIdx.y * gridDim.x + blockIdx.x] = total;
+}
+
+// one block per array: its tile sums <- their exclusive sum, in place
+__global__ __launch_bounds__(kPileupThreads) void k_pileup_carry(u64 *tile_sum, uint32_t tiles) {
+    __shared__ u64 s_w[kPileupThreads / 64];
+    u64 *v = tile_sum + (u64)blockIdx.x * tiles;
+    u64 run = 0;
+    for (uint32_t base = 0; base < tiles; base += kPileupThreads) {
+        const uint32_t i = base + threadIdx.x;
+        u64 all;
+        const u64 ex = pileup_block_scan(i < tiles ? v[i] : 0ull, s_w, &all);
+        if (i < tiles) v[i] = run + ex;
+        run += all;
+        __syncthreads();  // (s_w is rewritten by the next step)
+    }
+}
+
+// co[i] = coordinate of sorted record i; pre[i] = sum of the coordinates of records [0, i), i = 0 .. n
+__global__ __launch_bounds__(kPileupThreads) void k_pileup_apply(const uint32_t *rec_s, const uint32_t *rec_e, u64 n, const u64 *carry, uint32_t *co_s,
+                                                                 uint32_t *co_e, u64 *pre_s, u64 *pre_e) {
+    __shared__ u64 s_w[kPileupThreads / 64];
+    const uint32_t *rec = blockIdx.y ? rec_e : rec_s;
+    uint32_t *co = blockIdx.y ? co_e : co_s;
+    u64 *pre = blockIdx.y ? pre_e : pre_s;
+    const u64 i0 = (u64)blockIdx.x * kPileupScanTile + 4ull * threadIdx.x;
+    uint32_t c[4];
+    pileup_load(rec, n, i0, c);
+    u64 total;
+    u64 run = carry[(u64)blockIdx.y * gridDim.x + blockIdx.x] + pileup_block_scan((u64)c[0] + c[1] + c[2] + c[3], s_w, &total);
+    if (i0 + 4 <= n) {  // (16 i0 and 32 i0 bytes into hipMalloc'd buffers)
+        *reinterpret_cast<uint4 *>(co + i0) = make_uint4(c[0], c[1], c[2], c[3]);
+        const u64 p1 = run + c[0], p2 = p1 + c[1], p3 = p2 + c[2];
+        ulonglong2 *pp = reinterpret_cast<ulonglong2 *>(pre + i0);
+        pp[0] = make_ulonglong2(run, p1);
+        pp[1] = make_ulonglong2(p2, p3);
+        if (i0 + 4 == n) pre[n] = p3 + c[3];
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (i0 + j < n) {
+                co[i0 + j] = c[j], pre[i0 + j] = run;
+                run += c[j];
+                if (i0 + j + 1 == n) pre[n] = run;
+            }
+    }
+}
+
+// off[c] = the records with seqid < c (the same for both arrays: they hold the same seqids)
+__global__ __launch_bounds__(kPileupThreads) void k_pileup_offsets(const uint32_t *rec, u64 n, uint32_t n_seq, u64 *off) {
+    const u64 c = (u64)blockIdx.x * kPileupThreads + threadIdx.x;
+    if (c > n_seq) return;
+    u64 lo = 0, hi = n;
+    while (lo < hi) {
+        const u64 mid = lo + ((hi - lo) >> 1);
+        if (rec[2 * mid] < c)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    off[c] = lo;
+}
+
+__global__ __launch_bounds__(kPileupThreads) void k_pileup_segments(pileup::Keys K, const u64 *off, uint32_t n_seq, u64 n_seg, const uint32_t *seg_seq,
+                                                                    const uint32_t *seg_start, const uint32_t *seg_end, u64 *acc) {
+    const u64 i = (u64)blockIdx.x * kPileupThreads + threadIdx.x;
+    if (i >= n_seg) return;
+    const uint32_t c = seg_seq[i];
+    if (c >= n_seq) return;  // (refused at _create)
+    const u64 add = pileup::segment_bases(K, off[c], off[c + 1], seg_start[i], seg_end[i]);
+    if (add) acc[i] += add;
+}
+
+}  // namespace gffx
+
+using namespace gffx;
+
+struct gffx_hip_pileup {
+    int device = 0;
+    uint32_t n_seq = 0;
+    uint64_t n_seg = 0;
+    int status = GFFX_OK;  // the first error: the object only reports it again
+    std::string message;
+    hipStream_t stream = nullptr;
+    // two folds in flight, each: 0 start, 1 keys done, 2 sorts start (the host looked at the error word in between), 3 sorts done,
+    // 4 scan done, 5 segments done, 6 the error word is on the host
+    hipEvent_t ev[2][7] = {};
+    hipEvent_t read = nullptr;  // the fold's rows have been read
+    bool pending[2] = {false, false};  // ev[j] and h_ctl[j] wait to be looked at
+    int next_set = 0;
+    uint32_t *d_seg[3] = {nullptr, nullptr, nullptr};
+    u64 *d_acc = nullptr;
+    uint32_t *d_rows = nullptr;  // _add_host: the fold's rows
+    uint64_t cap_rows = 0;
+    uint32_t *ks[2] = {nullptr, nullptr}, *ke[2] = {nullptr, nullptr};  // the key records and the sort's second buffer
+    uint32_t *co[2] = {nullptr, nullptr};                               // sorted coordinates: starts, ends
+    u64 *pre[2] = {nullptr, nullptr};                                   // ... their n + 1 prefix sums
+    u64 *tile_sum = nullptr, *off = nullptr;
+    uint32_t *work = nullptr;
+    uint64_t cap = 0, cap_work = 0, cap_tiles = 0;
+    uint32_t *ctl = nullptr;    // device words {err, 7 x pad}
+    uint32_t *h_ctl = nullptr;  // pinned, 3 x 8 words: the two folds in flight, the check after k_pileup_keys
+    uint32_t *h_stage = nullptr;  // pinned
+    uint64_t cap_stage = 0;
+    SortPlan plan{};
+    double stage_ms[4] = {0, 0, 0, 0};  // keys, the two sorts, scan (+ offsets), segments
+    uint64_t rows_added = 0, folds = 0;
+};
+
+namespace {
+
+int pileup_fail(gffx_hip_pileup *P, int rc) {  // rc came from fail(): keep it and its message
+    if (P->status == GFFX_OK) P->status = rc, P->message = g_last_error;
+    return rc;
+}
+#define GFFX_PILEUP_TRY(expr)                  \
+    do {                                       \
+        const int _rc = (expr);                \
+        if (_rc) return pileup_fail(P, _rc);   \
+    } while (0)
+
+// a HIP call of an entry point that works on the handle: its failure, too, is kept (argument errors are not: the call is
+// refused and the handle stays usable)
+#define GFFX_PILEUP_HIP(expr) GFFX_PILEUP_TRY([&]() -> int { GFFX_HIP_TRY(expr); return GFFX_OK; }())
+
+int pileup_enter(const gffx_hip_pileup *P, const char *who) {
+    if (!P) return fail(GFFX_E_INVALID, "%s: pileup is NULL", who);
+    if (P->status != GFFX_OK) return fail(P->status, "%s: the pileup failed earlier: %s", who, P->message.c_str());
+    GFFX_HIP_TRY(hipSetDevice(P->device));
+    return GFFX_OK;
+}
+
+template <typename T>
+int pileup_alloc(T **p, uint64_t n) {
+    *p = nullptr;
+    GFFX_HIP_TRY(hipMalloc((void **)p, std::max<uint64_t>(n, 4) * sizeof(T)));
+    return GFFX_OK;
+}
+
+// the fold behind event set j is through: its stage times, and what the sort said
+int pileup_collect(gffx_hip_pileup *P, int j) {
+    if (!P->pending[j]) return GFFX_OK;
+    P->pending[j] = false;
+    GFFX_HIP_TRY(hipEventSynchronize(P->ev[j][6]));
+    const int from[4] = {0, 2, 3, 4};
+    for (int s = 0; s < 4; ++s) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, P->ev[j][from[s]], P->ev[j][s == 0 ? 1 : from[s] + 1]) == hipSuccess) P->stage_ms[s] += ms;
+    }
+    if (P->h_ctl[8 * j] & 4u) return fail(GFFX_E_HIP, "gffx_hip_pileup: the device sort timed out waiting for an earlier tile");
+    return GFFX_OK;
+}
+
+// room for a fold of m rows
+int pileup_reserve(gffx_hip_pileup *P, uint64_t m) {
+    int rc;
+    if (m > P->cap) {
+        GFFX_HIP_TRY(hipStreamSynchronize(P->stream));  // (an earlier fold may still read what is freed here)
+        const uint64_t cap = std::min<uint64_t>(kPileupFold, m + m / 4 + 1024);
+        for (void *p : {(void *)P->ks[0], (void *)P->ks[1], (void *)P->ke[0], (void *)P->ke[1], (void *)P->co[0], (void *)P->co[1], (void *)P->pre[0],
+                        (void *)P->pre[1], (void *)P->tile_sum, (void *)P->work})
+            if (p) GFFX_HIP_TRY(hipFree(p));
+        P->ks[0] = P->ks[1] = P->ke[0] = P->ke[1] = P->co[0] = P->co[1] = P->work = nullptr;
+        P->pre[0] = P->pre[1] = P->tile_sum = nullptr;
+        P->cap = P->cap_work = P->cap_tiles = 0;
+        const uint64_t tiles = (cap + kPileupScanTile - 1) / kPileupScanTile;
+        const uint64_t work = DeviceSort::work_words(cap, P->plan.n_passes);
+        for (int k = 0; k < 2; ++k)
+            if ((rc = pileup_alloc(&P->ks[k], 2 * cap)) || (rc = pileup_alloc(&P->ke[k], 2 * cap)) || (rc = pileup_alloc(&P->co[k], cap)) ||
+                (rc = pileup_alloc(&P->pre[k], cap + 1)))
+                return rc;
+        if ((rc = pileup_alloc(&P->tile_sum, 2 * tiles)) || (rc = pileup_alloc(&P->work, work))) return rc;
+        P->cap = cap, P->cap_work = work, P->cap_tiles = tiles;
+    }
+    return GFFX_OK;
+}
+
+// one fold: the m <= kPileupFold rows at `rows` (device memory; their copy, if any, is enqueued on the stream).  Returns when
+// the rows have been read and found well-formed; the sorts, the scan and the segment kernel go on behind.  A refused row
+// keeps ITS fold out of the totals; the folds of the same _add before it (an _add of more than kPileupFold rows) are in.
+int pileup_fold(gffx_hip_pileup *P, const uint32_t *rows, uint64_t m) {
+    if (!m) return GFFX_OK;
+    const int j = P->next_set;
+    int rc = pileup_collect(P, j);
+    if (rc) return rc;
+    const unsigned long long n = m;
+    GFFX_HIP_TRY(hipMemsetAsync(P->ctl, 0, 32, P->stream));
+    GFFX_HIP_TRY(hipEventRecord(P->ev[j][0], P->stream));
+    const int wide = (reinterpret_cast<uintptr_t>(rows) & 15u) == 0;
+    hipLaunchKernelGGL(k_pileup_keys, dim3((uint32_t)((n + 4 * kPileupThreads - 1) / (4 * kPileupThreads))), dim3(kPileupThreads), 0, P->stream, rows, n,
+                       P->n_seq, wide, P->ks[0], P->ke[0], P->ctl);
+    GFFX_HIP_TRY(hipGetLastError());
+    GFFX_HIP_TRY(hipEventRecord(P->ev[j][1], P->stream));
+    uint32_t *h_now = P->h_ctl + 16;
+    GFFX_HIP_TRY(hipMemcpyAsync(h_now, P->ctl, 32, hipMemcpyDeviceToHost, P->stream));
+    GFFX_HIP_TRY(hipEventRecord(P->read, P->stream));
+    GFFX_HIP_TRY(hipEventSynchronize(P->read));
+    if (h_now[0] & kPileupErrRange) return fail(GFFX_E_CHR_RANGE, "gffx_hip_pileup: a row has chr >= %u", P->n_seq);
+    if (h_now[0] & kPileupErrInverted) return fail(GFFX_E_INVALID, "gffx_hip_pileup: a row has start >= end");
+    uint32_t *sorted_s = nullptr, *sorted_e = nullptr;
+    GFFX_HIP_TRY(hipEventRecord(P->ev[j][2], P->stream));
+    if ((rc = DeviceSort::run<2>(P->stream, P->ks[0], P->ks[1], n, P->plan, P->n_seq, P->work, P->ctl, &sorted_s))) return rc;
+    if ((rc = DeviceSort::run<2>(P->stream, P->ke[0], P->ke[1], n, P->plan, P->n_seq, P->work, P->ctl, &sorted_e))) return rc;
+    GFFX_HIP_TRY(hipEventRecord(P->ev[j][3], P->stream));
+    const uint32_t tiles = (uint32_t)((n + kPileupScanTile - 1) / kPileupScanTile);
+    hipLaunchKernelGGL(k_pileup_tile_sums, dim3(tiles, 2), dim3(kPileupThreads), 0, P->stream, sorted_s, sorted_e, n, P->tile_sum);
+    hipLaunchKernelGGL(k_pileup_carry, dim3(2), dim3(kPileupThreads), 0, P->stream, P->tile_sum, tiles);
+    hipLaunchKernelGGL(k_pileup_apply, dim3(tiles, 2), dim3(kPileupThreads), 0, P->stream, sorted_s, sorted_e, n, P->tile_sum, P->co[0], P->co[1], P->pre[0],
+                       P->pre[1]);
+    hipLaunchKernelGGL(k_pileup_offsets, dim3(P->n_seq / kPileupThreads + 1), dim3(kPileupThreads), 0, P->stream, sorted_s, n, P->n_seq, P->off);
+    GFFX_HIP_TRY(hipGetLastError());
+    GFFX_HIP_TRY(hipEventRecord(P->ev[j][4], P->stream));
+    if (P->n_seg) {
+        const pileup::Keys K{P->co[0], P->co[1], P->pre[0], P->pre[1]};
+        hipLaunchKernelGGL(k_pileup_segments, dim3((uint32_t)((P->n_seg + kPileupThreads - 1) / kPileupThreads)), dim3(kPileupThreads), 0, P->stream, K, P->off,
+                           P->n_seq, (u64)P->n_seg, P->d_seg[0], P->d_seg[1], P->d_seg[2], P->d_acc);
+        GFFX_HIP_TRY(hipGetLastError());
+    }
+    GFFX_HIP_TRY(hipEventRecord(P->ev[j][5], P->stream));
+    GFFX_HIP_TRY(hipMemcpyAsync(P->h_ctl + 8 * j, P->ctl, 32, hipMemcpyDeviceToHost, P->stream));
+    GFFX_HIP_TRY(hipEventRecord(P->ev[j][6], P->stream));
+    P->pending[j] = true;
+    P->next_set = j ^ 1;
+    P->rows_added += m;
+    P->folds++;
+    return GFFX_OK;
+}
+
+// every fold enqueued so far is through and looked at
+int pileup_drain(gffx_hip_pileup *P) {
+    GFFX_HIP_TRY(hipStreamSynchronize(P->stream));
+    for (int j = 0; j < 2; ++j) {
+        const int rc = pileup_collect(P, j);
+        if (rc) return rc;
+    }
+    return GFFX_OK;
+}
+
+}  // namespace
+
+extern "C" uint64_t gffx_hip_pileup_fold_rows(void) { return kPileupFold; }
+extern "C" uint32_t gffx_hip_pileup_scan_tile(void) { return kPileupScanTile; }
+
+extern "C" void gffx_hip_pileup_destroy(gffx_hip_pileup *P) {
+    if (!P) return;
+    (void)hipSetDevice(P->device);
+    if (P->stream) (void)hipStreamSynchronize(P->stream);
+    for (void *p : {(void *)P->d_seg[0], (void *)P->d_seg[1], (void *)P->d_seg[2], (void *)P->d_acc, (void *)P->d_rows, (void *)P->ks[0], (void *)P->ks[1],
+                    (void *)P->ke[0], (void *)P->ke[1], (void *)P->co[0], (void *)P->co[1], (void *)P->pre[0], (void *)P->pre[1], (void *)P->tile_sum,
+                    (void *)P->off, (void *)P->work, (void *)P->ctl})
+        if (p) (void)hipFree(p);
+    if (P->h_stage) (void)hipHostFree(P->h_stage);
+    if (P->h_ctl) (void)hipHostFree(P->h_ctl);
+    for (auto &set : P->ev)
+        for (hipEvent_t e : set)
+            if (e) (void)hipEventDestroy(e);
+    if (P->read) (void)hipEventDestroy(P->read);
+    if (P->stream) (void)hipStreamDestroy(P->stream);
+    delete P;
+}
+
+extern "C" int gffx_hip_pileup_create(int device, uint32_t n_seq, uint64_t n_seg, const uint32_t *seg_seq, const uint32_t *seg_start,
+                                      const uint32_t *seg_end, gffx_hip_pileup **out) {
+    if (!out) return fail(GFFX_E_INVALID, "gffx_hip_pileup_create: out is NULL");
+    *out = nullptr;
+    if (n_seg && (!seg_seq || !seg_start || !seg_end)) return fail(GFFX_E_INVALID, "gffx_hip_pileup_create: NULL segment array");
+    if (n_seg >= (1ull << 32)) return fail(GFFX_E_INVALID, "gffx_hip_pileup_create: %llu segments exceed the limit of 2^32 - 1", (unsigned long long)n_seg);
+    for (uint64_t i = 0; i < n_seg; i++)
+        if (seg_seq[i] >= n_seq)
+            return fail(GFFX_E_INVALID, "gffx_hip_pileup_create: segment %llu has chr %u >= %u", (unsigned long long)i, seg_seq[i], n_seq);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess) {
+        (void)hipGetLastError();
+        ndev = 0;
+    }
+    if (ndev <= 0) return fail(GFFX_E_NO_DEVICE, "no HIP device visible (the engine has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(GFFX_E_NO_DEVICE, "device %d out of range (%d visible)", device, ndev);
+    GFFX_HIP_TRY(hipSetDevice(device));
+    std::unique_ptr<gffx_hip_pileup, void (*)(gffx_hip_pileup *)> P(new gffx_hip_pileup, gffx_hip_pileup_destroy);
+    P->device = device;
+    P->n_seq = n_seq;
+    P->n_seg = n_seg;
+    // by (seqid, coordinate): the four bytes of the coordinate, then as many bytes of the seqid as n_seq needs (the union's rule)
+    int seq_bytes = 1;
+    while (seq_bytes < 4 && (n_seq > (1u << (8 * seq_bytes)))) seq_bytes++;
+    for (int b = 0; b < 4; ++b) P->plan.word[P->plan.n_passes] = 1, P->plan.shift[P->plan.n_passes++] = (uint8_t)(8 * b);
+    for (int b = 0; b < seq_bytes; ++b) P->plan.word[P->plan.n_passes] = 0, P->plan.shift[P->plan.n_passes++] = (uint8_t)(8 * b);
+    GFFX_HIP_TRY(hipStreamCreateWithFlags(&P->stream, hipStreamNonBlocking));
+    for (auto &set : P->ev)
+        for (hipEvent_t &e : set) GFFX_HIP_TRY(hipEventCreate(&e));
+    GFFX_HIP_TRY(hipEventCreateWithFlags(&P->read, hipEventDisableTiming));
+    GFFX_HIP_TRY(hipHostMalloc((void **)&P->h_ctl, 3 * 32, hipHostMallocDefault));
+    std::memset(P->h_ctl, 0, 3 * 32);
+    int rc;
+    if ((rc = pileup_alloc(&P->ctl, 8)) || (rc = pileup_alloc(&P->off, (uint64_t)n_seq + 1)) || (rc = pileup_alloc(&P->d_acc, n_seg))) return rc;
+    for (uint32_t *&p : P->d_seg)
+        if ((rc = pileup_alloc(&p, n_seg))) return rc;
+    GFFX_HIP_TRY(hipMemsetAsync(P->d_acc, 0, std::max<uint64_t>(n_seg, 4) * 8, P->stream));
+    if (n_seg) {
+        GFFX_HIP_TRY(hipMemcpyAsync(P->d_seg[0], seg_seq, n_seg * 4, hipMemcpyHostToDevice, P->stream));
+        GFFX_HIP_TRY(hipMemcpyAsync(P->d_seg[1], seg_start, n_seg * 4, hipMemcpyHostToDevice, P->stream));
+        GFFX_HIP_TRY(hipMemcpyAsync(P->d_seg[2], seg_end, n_seg * 4, hipMemcpyHostToDevice, P->stream));
+    }
+    GFFX_HIP_TRY(hipStreamSynchronize(P->stream));  // (the caller's arrays are free again)
+    *out = P.release();
+    return GFFX_OK;
+}
+
+extern "C" int gffx_hip_pileup_add_host(gffx_hip_pileup *P, const uint32_t *rows, uint64_t n_rows) {
+    int rc = pileup_enter(P, "gffx_hip_pileup_add_host");
+    if (rc) return rc;
+    if (n_rows && !rows) return fail(GFFX_E_INVALID, "gffx_hip_pileup_add_host: rows is NULL");
+    const uint64_t want = std::min<uint64_t>(n_rows, kPileupFold);
+    if (want > P->cap_stage) {
+        if (P->h_stage) (void)hipHostFree(P->h_stage);
+        P->h_stage = nullptr, P->cap_stage = 0;
+        hipError_t e = hipHostMalloc((void **)&P->h_stage, want * 12, hipHostMallocDefault);
+        if (e != hipSuccess)
+            return pileup_fail(P, fail(GFFX_E_OOM, "hipHostMalloc of a %llu-row staging buffer failed: %s", (unsigned long long)want, hipGetErrorString(e)));
+        P->cap_stage = want;
+    }
+    if (want > P->cap_rows) {
+        GFFX_PILEUP_HIP(hipStreamSynchronize(P->stream));
+        if (P->d_rows) GFFX_PILEUP_HIP(hipFree(P->d_rows));
+        P->d_rows = nullptr, P->cap_rows = 0;
+        GFFX_PILEUP_TRY(pileup_alloc(&P->d_rows, 3 * want));
+        P->cap_rows = want;
+    }
+    for (uint64_t at = 0; at < n_rows; at += kPileupFold) {
+        const uint64_t m = std::min<uint64_t>(kPileupFold, n_rows - at);
+        GFFX_PILEUP_TRY(pileup_reserve(P, m));
+        std::memcpy(P->h_stage, rows + 3 * at, m * 12);  // (a fold returns after its rows were read: the buffer is free again)
+        GFFX_PILEUP_HIP(hipMemcpyAsync(P->d_rows, P->h_stage, m * 12, hipMemcpyHostToDevice, P->stream));
+        GFFX_PILEUP_TRY(pileup_fold(P, P->d_rows, m));
+    }
+    return GFFX_OK;
+}
+
+extern "C" int gffx_hip_pileup_add_store(gffx_hip_pileup *P, const gffx_hip_regions *R, int k, uint64_t first, uint64_t n_rows) {
+    int rc = pileup_enter(P, "gffx_hip_pileup_add_store");
+    if (rc) return rc;
+    if (!R || (k != 0 && k != 1)) return fail(GFFX_E_INVALID, "gffx_hip_pileup_add_store: bad argument");
+    if (R->device != P->device) return fail(GFFX_E_INVALID, "gffx_hip_pileup_add_store: store and pileup on different devices");
+    if (first + n_rows > R->last_n[k]) return fail(GFFX_E_INVALID, "gffx_hip_pileup_add_store: rows beyond the last append");
+    if (R->pending[k]) GFFX_PILEUP_HIP(hipStreamWaitEvent(P->stream, R->copied[k], 0));
+    const uint32_t *src = R->d + 3 * (R->last_first[k] + first);
+    for (uint64_t at = 0; at < n_rows; at += kPileupFold) {
+        const uint64_t m = std::min<uint64_t>(kPileupFold, n_rows - at);
+        GFFX_PILEUP_TRY(pileup_reserve(P, m));
+        GFFX_PILEUP_TRY(pileup_fold(P, src + 3 * at, m));  // (the slot is read in place: no copy)
+    }
+    return GFFX_OK;
+}
+
+extern "C" int gffx_hip_pileup_copy(gffx_hip_pileup *P, uint64_t *bases) {
+    int rc = pileup_enter(P, "gffx_hip_pileup_copy");
+    if (rc) return rc;
+    if (P->n_seg && !bases) return fail(GFFX_E_INVALID, "gffx_hip_pileup_copy: bases is NULL");
+    GFFX_PILEUP_TRY(pileup_drain(P));
+    if (P->n_seg) GFFX_PILEUP_HIP(hipMemcpy(bases, P->d_acc, P->n_seg * 8, hipMemcpyDeviceToHost));
+    return GFFX_OK;
+}
+
+extern "C" int gffx_hip_pileup_reset(gffx_hip_pileup *P) {
+    int rc = pileup_enter(P, "gffx_hip_pileup_reset");
+    if (rc) return rc;
+    GFFX_PILEUP_HIP(hipMemsetAsync(P->d_acc, 0, std::max<uint64_t>(P->n_seg, 4) * 8, P->stream));  // (behind the folds enqueued so far)
+    return GFFX_OK;
+}
+
+// (const in the interface; the times of folds that are still in flight are fetched here, which waits for them)
+extern "C" int gffx_hip_pileup_stage_ms(const gffx_hip_pileup *Pc, double *keys, double *sorts, double *scan, double *segments) {
+    if (!Pc) return fail(GFFX_E_INVALID, "gffx_hip_pileup_stage_ms: pileup is NULL");
+    gffx_hip_pileup *P = const_cast<gffx_hip_pileup *>(Pc);
+    if (P->status == GFFX_OK && (P->pending[0] || P->pending[1])) {
+        GFFX_PILEUP_HIP(hipSetDevice(P->device));
+        GFFX_PILEUP_TRY(pileup_drain(P));
+    }
+    if (keys) *keys = P->stage_ms[0];
+    if (sorts) *sorts = P->stage_ms[1];
+    if (scan) *scan = P->stage_ms[2];
+    if (segments) *segments = P->stage_ms[3];
+    return GFFX_OK;
+}
+
+extern "C" int gffx_hip_pileup_stats(const gffx_hip_pileup *P, double *kernel_ms, uint64_t *rows, uint64_t *folds) {
+    if (!P) return fail(GFFX_E_INVALID, "gffx_hip_pileup_stats: pileup is NULL");
+    double s[4] = {0, 0, 0, 0};
+    const int rc = gffx_hip_pileup_stage_ms(P, &s[0], &s[1], &s[2], &s[3]);
+    if (rc) return rc;
+    if (kernel_ms) *kernel_ms = s[0] + s[1] + s[2] + s[3];
+    if (rows) *rows = P->rows_added;
+    if (folds) *folds = P->folds;
+    return GFFX_OK;
+}

@@ -14,10 +14,14 @@
 // along: Join A with root_fids + offsets over the same resident batches pairs rows with them, the host gathers the paired
 // rows per root and merges them -- exactly the reference's list (coverage.rs:258-268, :401), with work proportional to the
 // pairs instead of rows x such blocks.
+// --mean-depth adds a third consumer of the resident batch, a pileup (include/gffx_hip.h "pileup"): the segments of ALL
+// blocks are built before the rows stream (which blocks are hit is known only at the end) and stay on every device, each batch
+// adds the bases its rows lay on them, and the per-device totals are added here as integers.  Without the flag none of this runs.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <future>
 
 #include "gffx.hpp"
 
@@ -66,6 +70,50 @@ size_t batch_rows_from_env() {  // GFFX_COVERAGE_BATCH_ROWS (gffx.hpp)
     return 4u << 20;
 }
 
+struct Seg {
+    uint32_t group, start, end;
+    bool fast;  // (the caller's: evaluated on the device against the union of all rows)
+};
+
+// Per (block, ID) group of `blocks` (ascending: file order): the union of the group's lines as disjoint segments, block after
+// block and inside a block in line order; built on `threads` host threads over contiguous shares of the list and concatenated in
+// order.  g_min / g_max / g_hit (all three or none): the group's extent over ALL its lines (coverage.rs:345-346), and that its
+// block was in the list -- a group belongs to one block, so the shares write disjoint entries.
+std::vector<Seg> segments_of_blocks(const depth::BlockTable &t, const std::vector<uint32_t> &blocks, size_t threads, std::vector<uint32_t> *g_min,
+                                    std::vector<uint32_t> *g_max, std::vector<uint8_t> *g_hit) {
+    const size_t parts = blocks.size() < 4096 ? 1 : std::max<size_t>(1, std::min<size_t>(threads, 64));
+    std::vector<std::vector<Seg>> piece(parts);
+    parallel_for(parts, parts, [&](size_t p) {
+        std::vector<Seg> &segs = piece[p];
+        std::vector<Span> lines;
+        for (size_t k = blocks.size() * p / parts; k < blocks.size() * (p + 1) / parts; ++k) {
+            const uint32_t b = blocks[k];
+            uint64_t l = t.block_line_off[b];
+            const uint64_t le = t.block_line_off[b + 1];
+            while (l < le) {
+                const uint32_t g = t.line_group[l];
+                lines.clear();
+                for (; l < le && t.line_group[l] == g; ++l) {
+                    lines.emplace_back(t.line_start[l], t.line_end[l]);
+                    if (g_min) {
+                        (*g_min)[g] = std::min((*g_min)[g], t.line_start[l]);
+                        (*g_max)[g] = std::max((*g_max)[g], t.line_end[l]);
+                    }
+                }
+                if (g_hit) (*g_hit)[g] = 1;
+                for (const Span &sgm : merge_intervals(lines)) segs.push_back(Seg{g, sgm.first, sgm.second, false});
+            }
+        }
+    });
+    if (parts == 1) return std::move(piece[0]);
+    std::vector<Seg> all;
+    size_t total = 0;
+    for (const auto &v : piece) total += v.size();
+    all.reserve(total);
+    for (const auto &v : piece) all.insert(all.end(), v.begin(), v.end());
+    return all;
+}
+
 }  // namespace
 
 void run(const CoverageArgs &args) {
@@ -82,7 +130,7 @@ void run(const CoverageArgs &args) {
     if (verbose) std::fprintf(stderr, "[INFO] %zu %s rows kept\n", n_regions, depth::source_label(kind));
     timer.lap(depth::source_lap(kind, true));
 
-    std::string out = "id\tchr\tstart\tend\tbreadth\tfraction\n";  // :463
+    std::string out = args.mean_depth ? "id\tchr\tstart\tend\tbreadth\tfraction\tbases\tlength\tmean_depth\n" : "id\tchr\tstart\tend\tbreadth\tfraction\n";  // :463
     size_t written = 0;
     if (n_regions) {
         const depth::BlockTable t = depth::load_or_build_block_table(args.input, gof, gff.view(), threads, verbose);
@@ -124,6 +172,39 @@ void run(const CoverageArgs &args) {
             side_off[c + 1] = static_cast<uint32_t>(side_start.size());
         }
         const bool have_side = !side_start.empty();
+        std::vector<uint32_t> group_block(t.group_id.size(), 0);
+        for (uint32_t b = 0; b + 1 < t.block_line_off.size(); ++b)
+            for (uint64_t l = t.block_line_off[b]; l < t.block_line_off[b + 1]; ++l) group_block[t.line_group[l]] = b;
+
+        // --mean-depth: the segments of every block, and the ones whose seqid the index knows as the pileup's arrays (a chrom the
+        // index does not know has no rows: 0 bases).  A segment's seqid is its group's chrom column, not its root's.  Built on
+        // host threads of their own WHILE the devices come up below (runtime, index upload, stores, batches): every device's
+        // thread waits for `segs_ready` just before it creates its pileup, the last thing it sets up.
+        std::vector<Seg> all_segs;
+        std::vector<uint32_t> chrom_num, p_seq, p_start, p_end;
+        std::shared_future<void> segs_ready;
+        if (args.mean_depth) segs_ready = std::async(std::launch::async, [&] {
+            const auto t0 = std::chrono::steady_clock::now();
+            std::vector<uint32_t> all_blocks(t.block_line_off.size() - 1);
+            for (uint32_t b = 0; b < all_blocks.size(); ++b) all_blocks[b] = b;
+            all_segs = segments_of_blocks(t, all_blocks, threads, nullptr, nullptr, nullptr);
+            chrom_num.assign(t.chroms.size(), 0xFFFFFFFFu);
+            for (size_t k = 0; k < t.chroms.size(); ++k) {
+                const auto it = index_data.seqid_to_num.find(t.chroms[k]);
+                if (it != index_data.seqid_to_num.end() && it->second < n_seq) chrom_num[k] = it->second;
+            }
+            p_seq.reserve(all_segs.size()), p_start.reserve(all_segs.size()), p_end.reserve(all_segs.size());
+            for (const Seg &sg : all_segs) {
+                const uint32_t c = chrom_num[t.group_chrom[sg.group]];
+                if (c == 0xFFFFFFFFu) continue;
+                p_seq.push_back(c), p_start.push_back(sg.start), p_end.push_back(sg.end);
+            }
+            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            if (verbose)
+                std::fprintf(stderr, "[INFO] pileup: %zu segments of all blocks (%zu on seqids of the index)\n[TIMER] [run] Segments of all blocks (pileup; beside the device set-up) took %.3f ms\n",
+                             all_segs.size(), p_seq.size(), ms);
+            g_run_stats.stage("Segments of all blocks (pileup; beside the device set-up)", ms);
+        }).share();
 
         // --gpus N: the rows go to the devices in batches, round robin (the root bitmap is an OR and the union does not depend
         // on how the rows are grouped, so any partition gives the same rows out); one host thread drives each device
@@ -139,6 +220,10 @@ void run(const CoverageArgs &args) {
             BatchHandle b[2], c[2];  // Join A on the index (root bitmap) / on the index of the roots above (pairs)
             IndexHandle side;
             UnionHandle u;
+            PileupHandle p;
+            std::vector<uint64_t> bases;  // (--mean-depth) the device's totals, one per pileup segment
+            double pileup_ms = 0, pileup_stage_ms[4] = {0, 0, 0, 0};
+            uint64_t pileup_folds = 0;
             std::vector<uint64_t> words;
             RootRows root_rows;
             std::vector<uint64_t> u_off;
@@ -161,6 +246,11 @@ void run(const CoverageArgs &args) {
                 if (gffx_hip_batch_create(ix, cap, OutPtr(P.b[k])) != GFFX_OK) hip_fail("gffx_hip_batch_create");
                 if (have_side && gffx_hip_batch_create(P.side.get(), cap, OutPtr(P.c[k])) != GFFX_OK) hip_fail("gffx_hip_batch_create");
             }
+            if (args.mean_depth) {
+                std::shared_future<void>(segs_ready).get();  // (a copy per thread; rethrows what the builder threw)
+                if (gffx_hip_pileup_create(devs[d], n_seq, p_seq.size(), p_seq.data(), p_start.data(), p_end.data(), OutPtr(P.p)) != GFFX_OK)
+                    hip_fail("gffx_hip_pileup_create");
+            }
             P.words.assign(n_words, 0);
             bool used[2] = {false, false};
             size_t rows_in[2] = {0, 0};
@@ -179,6 +269,8 @@ void run(const CoverageArgs &args) {
                 }
                 used[k] = true;
                 rows_in[k] = n;
+                // (--mean-depth) the same resident rows into the pileup: returns when they are read, its fold runs beside the union's
+                if (args.mean_depth && gffx_hip_pileup_add_store(P.p.get(), P.store.get(), k, 0, n) != GFFX_OK) hip_fail("gffx_hip_pileup_add_store");
                 // the same resident rows into the union (on the union's own stream, beside Join A; returns when they are read)
                 if (gffx_hip_union_add_store(P.u.get(), P.store.get(), k, 0, n) != GFFX_OK) hip_fail("gffx_hip_union_add_store");
             };
@@ -222,6 +314,13 @@ void run(const CoverageArgs &args) {
                 if (gffx_hip_union_copy_spans(P.u.get(), P.u_off.data(), P.us.data(), P.ue.data(), nullptr) != GFFX_OK) hip_fail("gffx_hip_union_copy_spans");
             }
             if (gffx_hip_union_stats(P.u.get(), &P.union_ms, nullptr, nullptr) != GFFX_OK) hip_fail("gffx_hip_union_stats");
+            if (args.mean_depth) {
+                P.bases.assign(std::max<size_t>(p_seq.size(), 1), 0);
+                if (gffx_hip_pileup_copy(P.p.get(), P.bases.data()) != GFFX_OK) hip_fail("gffx_hip_pileup_copy");
+                if (gffx_hip_pileup_stats(P.p.get(), &P.pileup_ms, nullptr, &P.pileup_folds) != GFFX_OK) hip_fail("gffx_hip_pileup_stats");
+                if (gffx_hip_pileup_stage_ms(P.p.get(), &P.pileup_stage_ms[0], &P.pileup_stage_ms[1], &P.pileup_stage_ms[2], &P.pileup_stage_ms[3]) != GFFX_OK)
+                    hip_fail("gffx_hip_pileup_stage_ms");
+            }
         });
         // merge over the devices: OR of the bitmaps, the spans into device 0's union
         std::vector<uint64_t> words(n_words, 0);
@@ -264,13 +363,38 @@ void run(const CoverageArgs &args) {
         g_run_stats.count("union_kernels_ms", union_ms);
         g_run_stats.extra("devices", per_device);
         timer.lap("Join A + union build on the device (one upload per batch, kernels, bitmaps and spans D2H)");
+        // (--mean-depth) the devices' totals added as integers, then per group: its bases and the bases of its segments
+        std::vector<uint64_t> group_bases, group_len;
+        if (args.mean_depth) {
+            group_bases.assign(t.group_id.size(), 0), group_len.assign(t.group_id.size(), 0);
+            double pileup_ms = 0, st[4] = {0, 0, 0, 0};
+            size_t pi = 0;
+            uint64_t folds = 0;
+            for (const Seg &sg : all_segs) {
+                if (sg.end > sg.start) group_len[sg.group] += sg.end - sg.start;
+                if (chrom_num[t.group_chrom[sg.group]] == 0xFFFFFFFFu) continue;
+                for (const PerDevice &P : pd) group_bases[sg.group] += P.bases[pi];
+                ++pi;
+            }
+            for (const PerDevice &P : pd) {
+                pileup_ms += P.pileup_ms;
+                folds += P.pileup_folds;
+                for (int k = 0; k < 4; ++k) st[k] += P.pileup_stage_ms[k];
+            }
+            if (verbose)
+                std::fprintf(stderr, "[INFO] pileup of %zu segments: %llu folds, kernels %.3f ms (keys %.3f, two sorts %.3f, prefix sums %.3f, segments %.3f)\n",
+                             p_seq.size(), (unsigned long long)folds, pileup_ms, st[0], st[1], st[2], st[3]);
+            g_run_stats.count("pileup_segments", static_cast<double>(p_seq.size()));
+            g_run_stats.count("pileup_kernels_ms", pileup_ms);
+            g_run_stats.count("pileup_folds", static_cast<double>(folds));
+            g_run_stats.count("pileup_keys_ms", st[0]);
+            g_run_stats.count("pileup_sorts_ms", st[1]);
+            g_run_stats.count("pileup_scan_ms", st[2]);
+            g_run_stats.count("pileup_segments_ms", st[3]);
+            timer.lap("Pileup (device)");
+        }
 
         // per (block, ID) group of the hit blocks: the union of its lines as disjoint segments, and its extent
-        struct Seg {
-            uint32_t group, start, end;
-            bool fast;
-        };
-        std::vector<Seg> segs;
         std::vector<uint32_t> seg_seq, seg_start, seg_end;  // the device's share
         std::vector<uint32_t> g_min(t.group_id.size(), 0xFFFFFFFFu), g_max(t.group_id.size(), 0);
         std::vector<uint8_t> g_hit(t.group_id.size(), 0);
@@ -278,33 +402,27 @@ void run(const CoverageArgs &args) {
         for (uint32_t fid : hit_roots)
             if (fid < t.block_of_fid.size() && t.block_of_fid[fid] != 0xFFFFFFFFu) hit_blocks.push_back(t.block_of_fid[fid]);
         std::sort(hit_blocks.begin(), hit_blocks.end());  // file order
-        std::vector<Span> lines;
-        for (uint32_t b : hit_blocks) {
-            const auto &root_iv = ivs[block_fid[b]];
-            bool one_seq = !root_iv.empty();
-            for (const auto &iv : root_iv) one_seq = one_seq && std::get<0>(iv) == std::get<0>(root_iv[0]);
-            uint64_t l = t.block_line_off[b];
-            const uint64_t le = t.block_line_off[b + 1];
-            while (l < le) {
-                const uint32_t g = t.line_group[l];
-                lines.clear();
-                for (; l < le && t.line_group[l] == g; ++l) {
-                    lines.emplace_back(t.line_start[l], t.line_end[l]);
-                    g_min[g] = std::min(g_min[g], t.line_start[l]);  // extents over ALL lines (coverage.rs:345-346)
-                    g_max[g] = std::max(g_max[g], t.line_end[l]);
+        std::vector<Seg> segs = segments_of_blocks(t, hit_blocks, 1, &g_min, &g_max, &g_hit);
+        {
+            uint32_t cur = 0xFFFFFFFFu;
+            const std::vector<std::tuple<uint32_t, uint32_t, uint32_t>> *root_iv = nullptr;
+            bool one_seq = false;
+            for (Seg &sg : segs) {
+                const uint32_t b = group_block[sg.group];
+                if (b != cur) {
+                    cur = b;
+                    root_iv = &ivs[block_fid[b]];
+                    one_seq = !root_iv->empty();
+                    for (const auto &iv : *root_iv) one_seq = one_seq && std::get<0>(iv) == std::get<0>((*root_iv)[0]);
                 }
-                g_hit[g] = 1;
-                for (const Span &sgm : merge_intervals(lines)) {
-                    bool inside = false;
-                    if (one_seq)
-                        for (const auto &iv : root_iv)
-                            inside = inside || (sgm.first >= std::get<1>(iv) && sgm.second <= std::get<2>(iv));
-                    segs.push_back(Seg{g, sgm.first, sgm.second, inside});
-                    if (inside) {
-                        seg_seq.push_back(std::get<0>(root_iv[0]));
-                        seg_start.push_back(sgm.first);
-                        seg_end.push_back(sgm.second);
-                    }
+                bool inside = false;
+                if (one_seq)
+                    for (const auto &iv : *root_iv) inside = inside || (sg.start >= std::get<1>(iv) && sg.end <= std::get<2>(iv));
+                sg.fast = inside;
+                if (inside) {
+                    seg_seq.push_back(std::get<0>((*root_iv)[0]));
+                    seg_start.push_back(sg.start);
+                    seg_end.push_back(sg.end);
                 }
             }
         }
@@ -321,9 +439,6 @@ void run(const CoverageArgs &args) {
         // Join A paired with the root on the side index, from all devices
         std::vector<uint64_t> breadth(t.group_id.size(), 0);
         std::unordered_map<uint32_t, std::vector<Span>> root_cov;  // block -> merged regions that hit its root
-        std::vector<uint32_t> group_block(t.group_id.size(), 0);
-        for (uint32_t b = 0; b + 1 < t.block_line_off.size(); ++b)
-            for (uint64_t l = t.block_line_off[b]; l < t.block_line_off[b + 1]; ++l) group_block[t.line_group[l]] = b;
         size_t fi = 0;
         for (const Seg &sg : segs) {
             if (sg.fast) {
@@ -352,6 +467,7 @@ void run(const CoverageArgs &args) {
             uint64_t b = 0;
         };
         std::vector<Row> rows(t.n_ids());
+        std::vector<uint64_t> id_bases(args.mean_depth ? t.n_ids() : 0, 0), id_len(id_bases.size(), 0);  // (--mean-depth; empty without it)
         std::vector<uint32_t> order;
         for (uint32_t g = 0; g < t.group_id.size(); ++g) {
             if (!g_hit[g]) continue;
@@ -370,6 +486,7 @@ void run(const CoverageArgs &args) {
                 r.e = std::max(r.e, g_max[g]);
                 r.b += breadth[g];
             }
+            if (args.mean_depth) id_bases[t.group_id[g]] += group_bases[g], id_len[t.group_id[g]] += group_len[g];
         }
         append_rows_parallel(out, order.size(), threads, [&](size_t k, std::string &o) {  // coverage.rs:465-473
             const uint32_t i = order[k];
@@ -386,6 +503,14 @@ void run(const CoverageArgs &args) {
             o += std::to_string(r.e);
             o.push_back('\t');
             o += std::to_string(r.b);
+            if (args.mean_depth) {
+                char more[128];
+                const uint64_t bases = id_bases[i], len = id_len[i];
+                const double mean = len > 0 ? static_cast<double>(bases) / static_cast<double>(len) : 0.0;
+                std::snprintf(more, sizeof more, "\t%.6f\t%llu\t%llu\t%.6f\n", fraction, static_cast<unsigned long long>(bases), static_cast<unsigned long long>(len), mean);
+                o += more;
+                return;
+            }
             std::snprintf(num, sizeof num, "\t%.6f\n", fraction);
             o += num;
         });

@@ -414,6 +414,7 @@ struct CoverageArgs {  // coverage.rs:37-57
     bool verbose = false;               // -v/--verbose
     int device = 0;                     // --device (addition)
     int gpus = 1;                       // --gpus (addition: the BED, BAM or SAM rows in batches over N MI355X, bitmaps and unions merged)
+    bool mean_depth = false;            // --mean-depth (addition: three more columns, bases / length / mean_depth, from a device pileup)
 };
 
 // GFFX_COVERAGE_BATCH_ROWS sets the rows per device batch (default 4 Mi rows; a positive decimal number, anything else is

@@ -161,6 +161,7 @@ const char *kCoverageUsage =
     "  -v, --verbose            Enable verbose output\n"
     "      --device <N>         HIP device to run on [default: 0]\n"
     "      --gpus <N>           Spread the BED, BAM or SAM rows over N devices [default: 1]\n"
+    "      --mean-depth         Add the columns bases, length and mean_depth (per-base depth of the feature's lines)\n"
     "      --stats-json <FILE>  Write the run's stage timers and counts as one JSON object\n";
 
 const char *kIndexUsage =
@@ -309,7 +310,8 @@ int run_depth_cli(int argc, char **argv) {
 int run_coverage_cli(int argc, char **argv) {
     static const std::vector<OptSpec> specs = {{'i', "input", true},   {'s', "source", true},   {'o', "output", true},
                                                {'t', "threads", true}, {'v', "verbose", false}, {0, "device", true},
-                                               {0, "gpus", true},      {0, "stats-json", true}, {'h', "help", false}};
+                                               {0, "gpus", true},      {0, "stats-json", true}, {0, "mean-depth", false},
+                                               {'h', "help", false}};
     const auto o = parse_opts(argc, argv, 2, specs);
     if (o.count("help")) {
         std::fputs(kCoverageUsage, stdout);
@@ -327,6 +329,7 @@ int run_coverage_cli(int argc, char **argv) {
     if (o.count("device")) a.device = static_cast<int>(parse_size(o.at("device")[0], "--device <N>"));
     if (o.count("gpus")) a.gpus = static_cast<int>(std::max<size_t>(1, std::min<size_t>(64, parse_size(o.at("gpus")[0], "--gpus <N>"))));
     if (o.count("stats-json")) g_run_stats.path = o.at("stats-json")[0];
+    a.mean_depth = o.count("mean-depth") > 0;
     commands::coverage::run(a);
     return 0;
 }

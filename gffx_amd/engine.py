@@ -594,6 +594,73 @@ class RegionUnion:
         return {"kernel_ms": ms.value, "rows": rows.value, "folds": folds.value}
 
 
+def _pileup_constants() -> Tuple[int, int]:
+    """(rows per fold, records per block of the prefix-sum kernels) of the library as it was built."""
+    return int(lib().gffx_hip_pileup_fold_rows()), int(lib().gffx_hip_pileup_scan_tile())
+
+
+def __getattr__(name: str):
+    # PILEUP_FOLD / PILEUP_SCAN_TILE: asked of the library on first use, so that importing this module loads nothing
+    if name in ("PILEUP_FOLD", "PILEUP_SCAN_TILE"):
+        fold, tile = _pileup_constants()
+        globals().update(PILEUP_FOLD=fold, PILEUP_SCAN_TILE=tile)
+        return fold if name == "PILEUP_FOLD" else tile
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
+class Pileup:
+    """gffx_hip_pileup_*: the bases the rows added so far lay on every segment (`gffx coverage --mean-depth`),
+    bases[i] = sum over the rows (seqid, s, e) of seqid seg_seq[i] of max(0, min(e, seg_end[i]) - max(s, seg_start[i])).
+    A sum over rows: any grouping of the rows into ``add`` calls, or over several objects whose totals are added, gives the
+    same numbers."""
+
+    def __init__(self, n_seq: int, seg_seq, seg_start, seg_end, device: int = 0):
+        self.n_seq = int(n_seq)
+        q, s, e = _u32(seg_seq).ravel(), _u32(seg_start).ravel(), _u32(seg_end).ravel()
+        if not (len(q) == len(s) == len(e)):
+            raise ValueError("seg_seq, seg_start and seg_end must have the same length")
+        self.n_seg = len(q)
+        self._h = C.c_void_p()
+        check(lib().gffx_hip_pileup_create(int(device), self.n_seq, self.n_seg, _p(q), _p(s), _p(e), C.byref(self._h)))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().gffx_hip_pileup_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, rows) -> None:
+        r = _u32(rows).reshape(-1, 3)
+        check(lib().gffx_hip_pileup_add_host(self._h, _p(r), r.shape[0]))
+
+    def add_store(self, store, k: int, first: int, n_rows: int) -> None:
+        """Rows [first, first + n_rows) of the last append from staging buffer k of ``store`` (a RegionStore or a raw handle)."""
+        handle = store.handle if isinstance(store, RegionStore) else store
+        check(lib().gffx_hip_pileup_add_store(self._h, handle, int(k), int(first), int(n_rows)))
+
+    def bases(self) -> np.ndarray:
+        """The running totals, one u64 per segment (waits for the folds in flight)."""
+        out = np.zeros(max(self.n_seg, 1), dtype=np.uint64)
+        check(lib().gffx_hip_pileup_copy(self._h, out.ctypes.data_as(u64p)))
+        return out[: self.n_seg]
+
+    def reset(self) -> None:
+        check(lib().gffx_hip_pileup_reset(self._h))
+
+    def stats(self) -> Dict[str, float]:
+        ms, rows, folds = C.c_double(0), C.c_uint64(0), C.c_uint64(0)
+        check(lib().gffx_hip_pileup_stats(self._h, C.byref(ms), C.byref(rows), C.byref(folds)))
+        st = [C.c_double(0) for _ in range(4)]
+        check(lib().gffx_hip_pileup_stage_ms(self._h, *[C.byref(x) for x in st]))
+        return {"kernel_ms": ms.value, "rows": rows.value, "folds": folds.value, "keys_ms": st[0].value, "sorts_ms": st[1].value,
+                "scan_ms": st[2].value, "segments_ms": st[3].value}
+
+
 def run_batches(batches: Sequence["QueryBatch"], mode: int = OverlapMode.Overlap, invert: bool = False, out_flags: int = OUT_FIDS,
                 strategy: int = STRATEGY_AUTO, n_passes: Optional[int] = None) -> None:
     """gffx_hip_batches_run_n: pass i over batches[i % len(batches)], enqueued by ONE call.  Distinct batches of one index that

@@ -19,6 +19,7 @@
  *     (commands/depth.rs:121-293)
  *   merge_intervals + the two-pointer walk              gffx_hip_segments_covered, gffx_hip_union_* (`gffx coverage`)
  *     (commands/coverage.rs:92-124, :339-364)
+ *   (no reference item: the reference reports no per-base depth)  gffx_hip_pileup_* (`gffx coverage --mean-depth`)
  *   bam::Reader records -> (chr, start, end) rows        gffx_hip_bgzf_inflate, gffx_hip_bam_* (BAM sources)
  *     (commands/depth.rs:297-372, coverage.rs:125-168)
  *   the same reader on a .sam file                       gffx_hip_sam_* (SAM sources, plain or BGZF-compressed)
@@ -185,6 +186,7 @@ typedef struct gffx_hip_bam gffx_hip_bam;
 typedef struct gffx_hip_sam gffx_hip_sam;
 typedef struct gffx_hip_bed gffx_hip_bed;
 typedef struct gffx_hip_union gffx_hip_union;
+typedef struct gffx_hip_pileup gffx_hip_pileup;
 
 int gffx_hip_abi_version(void);
 /* number of visible HIP devices (0 when none / no driver); never fails */
@@ -467,6 +469,40 @@ int gffx_hip_union_segments_covered(gffx_hip_union *, uint64_t n_seg, const uint
                                     const uint32_t *seg_end, uint32_t *covered_out);
 int gffx_hip_union_stats(const gffx_hip_union *, double *kernel_ms, uint64_t *rows, uint64_t *folds);
 void gffx_hip_union_destroy(gffx_hip_union *);
+
+/* ---- pileup: the bases the source rows lay on feature segments (`gffx coverage --mean-depth`; an addition, the reference
+ * has no such figure) --
+ * For segment i = [seg_start[i], seg_end[i]) on seqid seg_seq[i] and the rows (seqid, s, e) added so far (0-based, half-open):
+ *     bases[i] = sum over the rows of that seqid of max(0, min(e, seg_end[i]) - max(s, seg_start[i]))
+ * a 64-bit integer; a segment with start >= end has 0.  Mean depth = bases / segment length.  The figure is a sum over rows:
+ * ANY grouping of the rows into _add calls, and rows spread over several pileups whose totals are added, give the same numbers.
+ * Rows must have seqid < n_seq (else GFFX_E_CHR_RANGE) and start < end (else GFFX_E_INVALID), as for the union builder.
+ * Nothing is allocated per base: every fold of at most gffx_hip_pileup_fold_rows() rows sorts the rows' starts and ends on the
+ * device, takes their prefix sums and answers every segment with four searches (device/pileup_core.hpp).
+ *   _create      the segments are copied to the device and stay; seg_seq[i] >= n_seq: GFFX_E_INVALID; n_seg == 0 is legal
+ *   _add_host    rows in host memory (copied through a pinned staging buffer inside), any number of calls
+ *   _add_store   rows [first, first + n_rows) of the chunk last appended to a region store from staging buffer k, read in place.
+ *                Both _add calls return when the rows have been read and checked; the device goes on behind the call.
+ *                A call of more than _fold_rows() rows is cut into folds: a refused row keeps its own fold out of the totals,
+ *                the folds before it are in (the object has failed by then, so the totals can no longer be read).
+ *   _copy        waits for the folds, then bases[0 .. n_seg): the running totals, legal between adds
+ *   _reset       the totals back to zero; the segments stay
+ *   _stats       HIP-event milliseconds of all kernels so far, rows added, folds run (waits for the folds);
+ *   _stage_ms    the same time by stage: the key kernel, the two sorts, the prefix sums and offsets, the segment kernel
+ *   _fold_rows / _scan_tile   constants of the build: rows per fold, records per block of the prefix-sum kernels
+ * After a refused row or a failed HIP call the object only reports that error again; a refused ARGUMENT (NULL rows, rows beyond
+ * the last append, a store on another device) leaves it usable. */
+int gffx_hip_pileup_create(int device, uint32_t n_seq, uint64_t n_seg, const uint32_t *seg_seq, const uint32_t *seg_start,
+                           const uint32_t *seg_end, gffx_hip_pileup **out);
+int gffx_hip_pileup_add_host(gffx_hip_pileup *, const uint32_t *rows /* 3 per row */, uint64_t n_rows);
+int gffx_hip_pileup_add_store(gffx_hip_pileup *, const gffx_hip_regions *, int k, uint64_t first, uint64_t n_rows);
+int gffx_hip_pileup_copy(gffx_hip_pileup *, uint64_t *bases /* n_seg */);
+int gffx_hip_pileup_reset(gffx_hip_pileup *);
+int gffx_hip_pileup_stats(const gffx_hip_pileup *, double *kernel_ms, uint64_t *rows, uint64_t *folds);
+int gffx_hip_pileup_stage_ms(const gffx_hip_pileup *, double *keys, double *sorts, double *scan, double *segments);
+uint64_t gffx_hip_pileup_fold_rows(void);
+uint32_t gffx_hip_pileup_scan_tile(void);
+void gffx_hip_pileup_destroy(gffx_hip_pileup *);
 
 /* ---- BAM sources of `gffx depth` / `gffx coverage` (commands/depth.rs:297-427, commands/coverage.rs:125-204) --
  * BGZF members are inflated on the device (one wave per member, device/bgzf.hip; the decoder, device/bgzf_core.hpp, is

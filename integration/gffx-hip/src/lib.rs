@@ -45,6 +45,10 @@ pub struct gffx_hip_ids {
 pub struct gffx_hip_union {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct gffx_hip_pileup {
+    _p: [u8; 0],
+}
 
 pub const GFFX_MODE_CONTAINED: c_int = 0; // OverlapMode::Contained       intersect.rs:75
 pub const GFFX_MODE_CONTAINS_REGION: c_int = 1; // OverlapMode::ContainsRegion  intersect.rs:76
@@ -232,6 +236,18 @@ extern "C" {
                                            seg_end: *const u32, covered_out: *mut u32) -> c_int;
     pub fn gffx_hip_union_stats(u: *const gffx_hip_union, kernel_ms: *mut f64, rows: *mut u64, folds: *mut u64) -> c_int;
     pub fn gffx_hip_union_destroy(u: *mut gffx_hip_union);
+    // the bases the rows lay on feature segments (`gffx coverage --mean-depth`): a sum over rows, any grouping gives the same totals
+    pub fn gffx_hip_pileup_create(device: c_int, n_seq: u32, n_seg: u64, seg_seq: *const u32, seg_start: *const u32, seg_end: *const u32,
+                                  out: *mut *mut gffx_hip_pileup) -> c_int;
+    pub fn gffx_hip_pileup_add_host(p: *mut gffx_hip_pileup, rows: *const u32, n_rows: u64) -> c_int;
+    pub fn gffx_hip_pileup_add_store(p: *mut gffx_hip_pileup, r: *const gffx_hip_regions, k: c_int, first: u64, n_rows: u64) -> c_int;
+    pub fn gffx_hip_pileup_copy(p: *mut gffx_hip_pileup, bases: *mut u64) -> c_int;
+    pub fn gffx_hip_pileup_reset(p: *mut gffx_hip_pileup) -> c_int;
+    pub fn gffx_hip_pileup_stats(p: *const gffx_hip_pileup, kernel_ms: *mut f64, rows: *mut u64, folds: *mut u64) -> c_int;
+    pub fn gffx_hip_pileup_stage_ms(p: *const gffx_hip_pileup, keys: *mut f64, sorts: *mut f64, scan: *mut f64, segments: *mut f64) -> c_int;
+    pub fn gffx_hip_pileup_fold_rows() -> u64;
+    pub fn gffx_hip_pileup_scan_tile() -> u32;
+    pub fn gffx_hip_pileup_destroy(p: *mut gffx_hip_pileup);
 }
 
 fn last_error() -> String {

@@ -2,8 +2,10 @@
 GENCODE-shaped GFF with its index, runs `gffx coverage -v --stats-json` on them and prints the stage timers, the union's
 HIP-event kernel time and its fraction of the HBM roofline (algorithmic bytes: 12 per row in + 16 per span out) as one JSON
 object.  The files are kept in --dir between runs (the name carries N and the seed), so another build of the binary can be
-timed on the same input with --gffx.
-Usage: python tools/coverage_bench.py [--rows 20000000] [--gpus 1] [--genes 63000] [--seed 5] [--dir DIR] [--gffx PATH] [--runs 2]"""
+timed on the same input with --gffx.  --mean-depth times the run with that flag (the pileup's stage times are in `counts`);
+`wall_runs_s` lists every run, so a median of five after a warm-up is --runs 6 without its first entry.
+Usage: python tools/coverage_bench.py [--rows 20000000] [--gpus 1] [--genes 63000] [--seed 5] [--dir DIR] [--gffx PATH] [--runs 2]
+                                      [--threads N] [--mean-depth]"""
 import argparse
 import json
 import os
@@ -45,6 +47,8 @@ def main():
     ap.add_argument("--dir", default=None, help="directory for the files (default: a temporary one, removed)")
     ap.add_argument("--gffx", default=os.path.join(ROOT, "gffx_amd", "bin", "gffx"), help="the binary to time")
     ap.add_argument("--runs", type=int, default=2, help="timed runs; the last one is reported (the first warms the page cache)")
+    ap.add_argument("--threads", type=int, default=0, help="-t of the command (default: the command's own)")
+    ap.add_argument("--mean-depth", action="store_true", help="run with --mean-depth")
     a = ap.parse_args()
     if a.dir is None:
         import atexit
@@ -66,16 +70,21 @@ def main():
     cmd = [a.gffx, "coverage", "-v", "-i", gff, "-s", bed, "-o", out, "--stats-json", stats]
     if a.gpus != 1:
         cmd += ["--gpus", str(a.gpus)]
-    wall = 0.0
+    if a.threads:
+        cmd += ["-t", str(a.threads)]
+    if a.mean_depth:
+        cmd += ["--mean-depth"]
+    wall, walls = 0.0, []
     for _ in range(max(1, a.runs)):
         t0 = time.time()
         r = subprocess.run(cmd, capture_output=True)
         wall = time.time() - t0
+        walls.append(round(wall, 3))
         if r.returncode != 0:
             sys.stderr.write(r.stderr.decode(errors="replace"))
             sys.exit(r.returncode)
     st = json.load(open(stats))
-    res = {"rows": a.rows, "gpus": a.gpus, "bed_bytes": os.path.getsize(bed), "wall_s": round(wall, 3),
+    res = {"rows": a.rows, "gpus": a.gpus, "bed_bytes": os.path.getsize(bed), "wall_s": round(wall, 3), "wall_runs_s": walls,
            "total_ms": st["total_ms"], "stages_ms": st["stages_ms"], "counts": st.get("counts", {}),
            "output_rows": sum(1 for _ in open(out, "rb")) - 1}
     c = res["counts"]
