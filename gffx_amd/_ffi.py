@@ -115,6 +115,20 @@ SIGNATURES = {
     "gffx_hip_pileup_fold_rows": (C.c_uint64, []),
     "gffx_hip_pileup_scan_tile": (C.c_uint32, []),
     "gffx_hip_pileup_destroy": (None, [vp]),
+    "gffx_hip_profile_create": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(vp)]),
+    "gffx_hip_profile_add_host": (C.c_int, [vp, u32p, C.c_uint64]),
+    "gffx_hip_profile_add_store": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64]),
+    "gffx_hip_profile_add_points": (C.c_int, [vp, u64p, u32p, u32p]),
+    "gffx_hip_profile_finish": (C.c_int, [vp]),
+    "gffx_hip_profile_n_points": (C.c_uint64, [vp]),
+    "gffx_hip_profile_copy_points": (C.c_int, [vp, u64p, u32p, u32p]),
+    "gffx_hip_profile_union_at_least": (C.c_int, [vp, C.c_uint32, C.POINTER(vp)]),
+    "gffx_hip_profile_reset": (C.c_int, [vp]),
+    "gffx_hip_profile_stats": (C.c_int, [vp, C.POINTER(C.c_double), u64p, u64p]),
+    "gffx_hip_profile_stage_ms": (C.c_int, [vp] + [C.POINTER(C.c_double)] * 4),
+    "gffx_hip_profile_fold_rows": (C.c_uint64, []),
+    "gffx_hip_profile_scan_tile": (C.c_uint32, []),
+    "gffx_hip_profile_destroy": (None, [vp]),
     "gffx_hip_depth_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, u64p, u32p, u32p, u32p, C.c_uint32, u32p,
                                         C.POINTER(vp)]),
     "gffx_hip_depth_destroy": (None, [vp]),

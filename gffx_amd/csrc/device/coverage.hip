@@ -19,6 +19,7 @@
 #include "gffx_device.hpp"
 #include "radix_sort.hpp"
 #include "regions_store.hpp"
+#include "union_private.hpp"  // struct gffx_hip_union
 
 namespace gffx {
 
@@ -377,34 +378,6 @@ __global__ __launch_bounds__(kUnionThreads) void k_union_emit(const uint32_t *re
 }
 
 }  // namespace gffx
-
-struct gffx_hip_union {
-    int device = 0;
-    uint32_t n_seq = 0;
-    int status = GFFX_OK;  // the first error: the object only reports it again
-    std::string message;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    uint32_t *rec_a = nullptr, *rec_b = nullptr;  // rec_a[0 .. n_spans) = the spans so far as {seqid, start, end} records
-    uint64_t cap = 0, n_spans = 0;
-    uint32_t *work = nullptr;
-    uint64_t cap_work = 0;
-    unsigned long long *tile_a = nullptr, *tile_b = nullptr;
-    uint64_t cap_tiles = 0;
-    uint32_t *ctl = nullptr;  // device words {err x 4, span count (64 bits), pad}
-    uint32_t *h_stage = nullptr;  // pinned
-    uint64_t cap_stage = 0;
-    SortPlan plan{};
-    double kernel_ms = 0.0;
-    uint64_t rows_added = 0, folds = 0;
-    // after _finish
-    bool finished = false;
-    std::vector<unsigned long long> u_off, pb;
-    std::vector<uint32_t> us, ue;
-    void *tables[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    uint32_t *d_seg[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint64_t cap_seg = 0;
-};
 
 namespace {
 

@@ -17,6 +17,11 @@
 // --mean-depth adds a third consumer of the resident batch, a pileup (include/gffx_hip.h "pileup"): the segments of ALL
 // blocks are built before the rows stream (which blocks are hit is known only at the end) and stay on every device, each batch
 // adds the bases its rows lay on them, and the per-device totals are added here as integers.  Without the flag none of this runs.
+// --thresholds / --bedgraph add a fourth, a depth profile (include/gffx_hip.h "depth profile"): every batch is folded into
+// the device's canonical points, the points of devices 1 .. N-1 travel to device 0's profile like the spans, and there each threshold T
+// becomes a union "depth >= T" on the device against which the segments of the hit blocks are evaluated by the same kernel that serves
+// `breadth`.  The depth is that of ALL rows of the segment's seqid (its group's chrom column), as for --mean-depth.  Without the flags
+// none of this runs: no object, no kernel, the same bytes out.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -130,7 +135,12 @@ void run(const CoverageArgs &args) {
     if (verbose) std::fprintf(stderr, "[INFO] %zu %s rows kept\n", n_regions, depth::source_label(kind));
     timer.lap(depth::source_lap(kind, true));
 
-    std::string out = args.mean_depth ? "id\tchr\tstart\tend\tbreadth\tfraction\tbases\tlength\tmean_depth\n" : "id\tchr\tstart\tend\tbreadth\tfraction\n";  // :463
+    const std::vector<uint32_t> &thresholds = args.thresholds;
+    const bool want_profile = !thresholds.empty() || args.bedgraph.has_value();
+    std::string out = args.mean_depth ? "id\tchr\tstart\tend\tbreadth\tfraction\tbases\tlength\tmean_depth" : "id\tchr\tstart\tend\tbreadth\tfraction";  // :463
+    for (const uint32_t T : thresholds) out += "\tbases_ge" + std::to_string(T) + "\tfraction_ge" + std::to_string(T);
+    out.push_back('\n');
+    std::string bedgraph;  // (--bedgraph) an empty source gives an empty file
     size_t written = 0;
     if (n_regions) {
         const depth::BlockTable t = depth::load_or_build_block_table(args.input, gof, gff.view(), threads, verbose);
@@ -221,6 +231,11 @@ void run(const CoverageArgs &args) {
             IndexHandle side;
             UnionHandle u;
             PileupHandle p;
+            ProfileHandle prof;  // (--thresholds / --bedgraph)
+            std::vector<uint64_t> p_off;  // ... the device's points (devices 1 .. N-1: they travel to device 0's profile)
+            std::vector<uint32_t> p_pos, p_depth;
+            double profile_ms = 0, profile_stage_ms[4] = {0, 0, 0, 0};
+            uint64_t profile_folds = 0;
             std::vector<uint64_t> bases;  // (--mean-depth) the device's totals, one per pileup segment
             double pileup_ms = 0, pileup_stage_ms[4] = {0, 0, 0, 0};
             uint64_t pileup_folds = 0;
@@ -251,6 +266,7 @@ void run(const CoverageArgs &args) {
                 if (gffx_hip_pileup_create(devs[d], n_seq, p_seq.size(), p_seq.data(), p_start.data(), p_end.data(), OutPtr(P.p)) != GFFX_OK)
                     hip_fail("gffx_hip_pileup_create");
             }
+            if (want_profile && gffx_hip_profile_create(devs[d], n_seq, OutPtr(P.prof)) != GFFX_OK) hip_fail("gffx_hip_profile_create");
             P.words.assign(n_words, 0);
             bool used[2] = {false, false};
             size_t rows_in[2] = {0, 0};
@@ -271,6 +287,8 @@ void run(const CoverageArgs &args) {
                 rows_in[k] = n;
                 // (--mean-depth) the same resident rows into the pileup: returns when they are read, its fold runs beside the union's
                 if (args.mean_depth && gffx_hip_pileup_add_store(P.p.get(), P.store.get(), k, 0, n) != GFFX_OK) hip_fail("gffx_hip_pileup_add_store");
+                // (--thresholds / --bedgraph) ... and into the depth profile, on its own stream: returns when they are read
+                if (want_profile && gffx_hip_profile_add_store(P.prof.get(), P.store.get(), k, 0, n) != GFFX_OK) hip_fail("gffx_hip_profile_add_store");
                 // the same resident rows into the union (on the union's own stream, beside Join A; returns when they are read)
                 if (gffx_hip_union_add_store(P.u.get(), P.store.get(), k, 0, n) != GFFX_OK) hip_fail("gffx_hip_union_add_store");
             };
@@ -320,6 +338,20 @@ void run(const CoverageArgs &args) {
                 if (gffx_hip_pileup_stats(P.p.get(), &P.pileup_ms, nullptr, &P.pileup_folds) != GFFX_OK) hip_fail("gffx_hip_pileup_stats");
                 if (gffx_hip_pileup_stage_ms(P.p.get(), &P.pileup_stage_ms[0], &P.pileup_stage_ms[1], &P.pileup_stage_ms[2], &P.pileup_stage_ms[3]) != GFFX_OK)
                     hip_fail("gffx_hip_pileup_stage_ms");
+            }
+            if (want_profile) {
+                gffx_hip_profile *pr = P.prof.get();
+                if (d > 0) {  // the points travel to device 0's profile
+                    if (gffx_hip_profile_finish(pr) != GFFX_OK) hip_fail("gffx_hip_profile_finish");
+                    const uint64_t np = gffx_hip_profile_n_points(pr);
+                    P.p_off.assign(n_seq + 1, 0);
+                    P.p_pos.assign(std::max<uint64_t>(np, 1), 0);
+                    P.p_depth.assign(std::max<uint64_t>(np, 1), 0);
+                    if (gffx_hip_profile_copy_points(pr, P.p_off.data(), P.p_pos.data(), P.p_depth.data()) != GFFX_OK) hip_fail("gffx_hip_profile_copy_points");
+                }
+                if (gffx_hip_profile_stats(pr, &P.profile_ms, nullptr, &P.profile_folds) != GFFX_OK) hip_fail("gffx_hip_profile_stats");
+                if (gffx_hip_profile_stage_ms(pr, &P.profile_stage_ms[0], &P.profile_stage_ms[1], &P.profile_stage_ms[2], &P.profile_stage_ms[3]) != GFFX_OK)
+                    hip_fail("gffx_hip_profile_stage_ms");
             }
         });
         // merge over the devices: OR of the bitmaps, the spans into device 0's union
@@ -430,6 +462,74 @@ void run(const CoverageArgs &args) {
             std::fprintf(stderr, "[INFO] %zu hit blocks, %zu segments (%zu evaluated on the host)\n", hit_blocks.size(),
                          segs.size(), segs.size() - seg_seq.size());
         timer.lap("Segments of the hit blocks");
+        // (--thresholds / --bedgraph) the merged profile on device 0; per threshold the bases at depth >= T of every segment of the
+        // hit blocks, on the seqid of the segment's group (a chrom the index does not know has no rows: 0), summed per group
+        std::vector<std::vector<uint64_t>> group_ge(thresholds.size());
+        std::vector<uint64_t> group_seg_len;
+        if (want_profile) {
+            gffx_hip_profile *pr = pd[0].prof.get();
+            for (size_t d = 1; d < D; ++d)
+                if (gffx_hip_profile_add_points(pr, pd[d].p_off.data(), pd[d].p_pos.data(), pd[d].p_depth.data()) != GFFX_OK) hip_fail("gffx_hip_profile_add_points");
+            if (gffx_hip_profile_finish(pr) != GFFX_OK) hip_fail("gffx_hip_profile_finish");
+            const uint64_t n_points = gffx_hip_profile_n_points(pr);
+            std::vector<uint32_t> cn(t.chroms.size(), 0xFFFFFFFFu);
+            for (size_t k = 0; k < t.chroms.size(); ++k) {
+                const auto it = index_data.seqid_to_num.find(t.chroms[k]);
+                if (it != index_data.seqid_to_num.end() && it->second < n_seq) cn[k] = it->second;
+            }
+            std::vector<uint32_t> q_seq, q_start, q_end, q_group;
+            group_seg_len.assign(t.group_id.size(), 0);
+            for (const Seg &sg : segs) {
+                if (sg.end > sg.start) group_seg_len[sg.group] += sg.end - sg.start;
+                const uint32_t c = cn[t.group_chrom[sg.group]];
+                if (c == 0xFFFFFFFFu) continue;
+                q_seq.push_back(c), q_start.push_back(sg.start), q_end.push_back(sg.end), q_group.push_back(sg.group);
+            }
+            std::vector<uint32_t> ge(std::max<size_t>(q_seq.size(), 1), 0);
+            for (size_t k = 0; k < thresholds.size(); ++k) {
+                UnionHandle at_least;
+                if (gffx_hip_profile_union_at_least(pr, thresholds[k], OutPtr(at_least)) != GFFX_OK) hip_fail("gffx_hip_profile_union_at_least");
+                if (gffx_hip_union_segments_covered(at_least.get(), q_seq.size(), q_seq.data(), q_start.data(), q_end.data(), ge.data()) != GFFX_OK)
+                    hip_fail("gffx_hip_union_segments_covered");
+                group_ge[k].assign(t.group_id.size(), 0);
+                for (size_t i = 0; i < q_seq.size(); ++i) group_ge[k][q_group[i]] += ge[i];
+            }  // (the handle destroys the union)
+            if (args.bedgraph) {
+                std::vector<uint64_t> p_off(n_seq + 1, 0);
+                std::vector<uint32_t> pos(std::max<uint64_t>(n_points, 1), 0), dep(std::max<uint64_t>(n_points, 1), 0);
+                if (gffx_hip_profile_copy_points(pr, p_off.data(), pos.data(), dep.data()) != GFFX_OK) hip_fail("gffx_hip_profile_copy_points");
+                for (uint32_t c = 0; c < n_seq; ++c)
+                    for (uint64_t i = p_off[c]; i + 1 < p_off[c + 1]; ++i) {  // (a seqid's last point has depth 0)
+                        if (!dep[i]) continue;
+                        bedgraph += index_data.num_to_seqid[c];
+                        bedgraph.push_back('\t');
+                        bedgraph += std::to_string(pos[i]);
+                        bedgraph.push_back('\t');
+                        bedgraph += std::to_string(pos[i + 1]);
+                        bedgraph.push_back('\t');
+                        bedgraph += std::to_string(dep[i]);
+                        bedgraph.push_back('\n');
+                    }
+            }
+            double profile_ms = 0, st[4] = {0, 0, 0, 0};
+            uint64_t folds = 0;
+            for (const PerDevice &P : pd) {
+                profile_ms += P.profile_ms;
+                folds += P.profile_folds;
+                for (int k = 0; k < 4; ++k) st[k] += P.profile_stage_ms[k];
+            }
+            if (verbose)
+                std::fprintf(stderr, "[INFO] depth profile of %llu points: %llu folds, kernels %.3f ms (events %.3f, sort %.3f, running depth %.3f, points %.3f); %zu thresholds over %zu segments\n",
+                             (unsigned long long)n_points, (unsigned long long)folds, profile_ms, st[0], st[1], st[2], st[3], thresholds.size(), q_seq.size());
+            g_run_stats.count("profile_points", static_cast<double>(n_points));
+            g_run_stats.count("profile_folds", static_cast<double>(folds));
+            g_run_stats.count("profile_kernels_ms", profile_ms);
+            g_run_stats.count("profile_events_ms", st[0]);
+            g_run_stats.count("profile_sort_ms", st[1]);
+            g_run_stats.count("profile_scan_ms", st[2]);
+            g_run_stats.count("profile_points_ms", st[3]);
+            timer.lap("Depth profile (device)");
+        }
         // device 0: covered bases of the segments inside their root, under the union of all regions of the seqid
         std::vector<uint32_t> cov_fast(std::max<size_t>(seg_seq.size(), 1), 0);
         if (gffx_hip_union_segments_covered(U, seg_seq.size(), seg_seq.data(), seg_start.data(), seg_end.data(), cov_fast.data()) != GFFX_OK)
@@ -468,6 +568,8 @@ void run(const CoverageArgs &args) {
         };
         std::vector<Row> rows(t.n_ids());
         std::vector<uint64_t> id_bases(args.mean_depth ? t.n_ids() : 0, 0), id_len(id_bases.size(), 0);  // (--mean-depth; empty without it)
+        std::vector<std::vector<uint64_t>> id_ge(thresholds.size(), std::vector<uint64_t>(t.n_ids(), 0));  // (--thresholds)
+        std::vector<uint64_t> id_seg_len(thresholds.empty() ? 0 : t.n_ids(), 0);
         std::vector<uint32_t> order;
         for (uint32_t g = 0; g < t.group_id.size(); ++g) {
             if (!g_hit[g]) continue;
@@ -487,6 +589,10 @@ void run(const CoverageArgs &args) {
                 r.b += breadth[g];
             }
             if (args.mean_depth) id_bases[t.group_id[g]] += group_bases[g], id_len[t.group_id[g]] += group_len[g];
+            if (!thresholds.empty()) {
+                id_seg_len[t.group_id[g]] += group_seg_len[g];
+                for (size_t k = 0; k < thresholds.size(); ++k) id_ge[k][t.group_id[g]] += group_ge[k][g];
+            }
         }
         append_rows_parallel(out, order.size(), threads, [&](size_t k, std::string &o) {  // coverage.rs:465-473
             const uint32_t i = order[k];
@@ -507,12 +613,18 @@ void run(const CoverageArgs &args) {
                 char more[128];
                 const uint64_t bases = id_bases[i], len = id_len[i];
                 const double mean = len > 0 ? static_cast<double>(bases) / static_cast<double>(len) : 0.0;
-                std::snprintf(more, sizeof more, "\t%.6f\t%llu\t%llu\t%.6f\n", fraction, static_cast<unsigned long long>(bases), static_cast<unsigned long long>(len), mean);
+                std::snprintf(more, sizeof more, "\t%.6f\t%llu\t%llu\t%.6f", fraction, static_cast<unsigned long long>(bases), static_cast<unsigned long long>(len), mean);
                 o += more;
-                return;
+            } else {
+                std::snprintf(num, sizeof num, "\t%.6f", fraction);
+                o += num;
             }
-            std::snprintf(num, sizeof num, "\t%.6f\n", fraction);
-            o += num;
+            for (size_t k = 0; k < thresholds.size(); ++k) {
+                const uint64_t ge = id_ge[k][i], len = id_seg_len[i];
+                std::snprintf(num, sizeof num, "\t%llu\t%.6f", static_cast<unsigned long long>(ge), len > 0 ? static_cast<double>(ge) / static_cast<double>(len) : 0.0);
+                o += num;
+            }
+            o.push_back('\n');
         });
         written = order.size();
     }
@@ -522,6 +634,7 @@ void run(const CoverageArgs &args) {
         std::fwrite(out.data(), 1, out.size(), stdout);
         std::fflush(stdout);
     }
+    if (args.bedgraph) write_whole_file(*args.bedgraph, bedgraph);
     if (verbose) std::fprintf(stderr, "[INFO] Wrote %zu feature coverage rows.\n", written);
     timer.lap("Merging groups and writing rows");
     g_run_stats.write("coverage", timer.total());

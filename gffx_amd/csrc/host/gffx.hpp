@@ -415,6 +415,8 @@ struct CoverageArgs {  // coverage.rs:37-57
     int device = 0;                     // --device (addition)
     int gpus = 1;                       // --gpus (addition: the BED, BAM or SAM rows in batches over N MI355X, bitmaps and unions merged)
     bool mean_depth = false;            // --mean-depth (addition: three more columns, bases / length / mean_depth, from a device pileup)
+    std::vector<uint32_t> thresholds;   // --thresholds (addition: bases_ge<T> / fraction_ge<T> per T, from a device depth profile)
+    std::optional<std::string> bedgraph;  // --bedgraph (addition: the depth profile itself as a bedGraph file)
 };
 
 // GFFX_COVERAGE_BATCH_ROWS sets the rows per device batch (default 4 Mi rows; a positive decimal number, anything else is

@@ -162,6 +162,10 @@ const char *kCoverageUsage =
     "      --device <N>         HIP device to run on [default: 0]\n"
     "      --gpus <N>           Spread the BED, BAM or SAM rows over N devices [default: 1]\n"
     "      --mean-depth         Add the columns bases, length and mean_depth (per-base depth of the feature's lines)\n"
+    "      --thresholds <T1,T2,...>  Add the columns bases_ge<T> and fraction_ge<T> for one to eight depths T >= 1: the bases of\n"
+    "                           the feature's lines at depth >= T among ALL rows of the seqid (so bases_ge1 can exceed breadth,\n"
+    "                           which counts only rows that hit the feature's root) and their share of the lines' bases\n"
+    "      --bedgraph <FILE>    Write the per-base depth of the source rows as a bedGraph (seqid, start, end, depth; depth > 0)\n"
     "      --stats-json <FILE>  Write the run's stage timers and counts as one JSON object\n";
 
 const char *kIndexUsage =
@@ -307,11 +311,33 @@ int run_depth_cli(int argc, char **argv) {
     return 0;
 }
 
+// --thresholds T1,T2,...: one to eight integers in 1 .. 4294967295, no duplicates
+std::vector<uint32_t> parse_thresholds(const std::string &v) {
+    const char *flag = "'--thresholds <T1,T2,...>'";
+    std::vector<uint32_t> out;
+    size_t at = 0;
+    while (true) {
+        const size_t comma = v.find(',', at);
+        const std::string item = v.substr(at, comma == std::string::npos ? std::string::npos : comma - at);
+        const bool digits = !item.empty() && item.size() <= 10 && item.find_first_not_of("0123456789") == std::string::npos;
+        const unsigned long long x = digits ? std::strtoull(item.c_str(), nullptr, 10) : 0ull;
+        if (!digits || x == 0 || x > 0xFFFFFFFFull)
+            throw Error("invalid value '" + v + "' for " + flag + ": '" + item + "' is not an integer in 1 .. 4294967295");
+        if (std::find(out.begin(), out.end(), static_cast<uint32_t>(x)) != out.end())
+            throw Error("invalid value '" + v + "' for " + flag + ": " + item + " is given twice");
+        out.push_back(static_cast<uint32_t>(x));
+        if (out.size() > 8) throw Error("invalid value '" + v + "' for " + flag + ": more than eight thresholds");
+        if (comma == std::string::npos) break;
+        at = comma + 1;
+    }
+    return out;
+}
+
 int run_coverage_cli(int argc, char **argv) {
     static const std::vector<OptSpec> specs = {{'i', "input", true},   {'s', "source", true},   {'o', "output", true},
                                                {'t', "threads", true}, {'v', "verbose", false}, {0, "device", true},
                                                {0, "gpus", true},      {0, "stats-json", true}, {0, "mean-depth", false},
-                                               {'h', "help", false}};
+                                               {0, "thresholds", true}, {0, "bedgraph", true},  {'h', "help", false}};
     const auto o = parse_opts(argc, argv, 2, specs);
     if (o.count("help")) {
         std::fputs(kCoverageUsage, stdout);
@@ -330,6 +356,8 @@ int run_coverage_cli(int argc, char **argv) {
     if (o.count("gpus")) a.gpus = static_cast<int>(std::max<size_t>(1, std::min<size_t>(64, parse_size(o.at("gpus")[0], "--gpus <N>"))));
     if (o.count("stats-json")) g_run_stats.path = o.at("stats-json")[0];
     a.mean_depth = o.count("mean-depth") > 0;
+    if (o.count("thresholds")) a.thresholds = parse_thresholds(o.at("thresholds")[0]);
+    if (o.count("bedgraph")) a.bedgraph = o.at("bedgraph")[0];
     commands::coverage::run(a);
     return 0;
 }

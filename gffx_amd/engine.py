@@ -599,12 +599,22 @@ def _pileup_constants() -> Tuple[int, int]:
     return int(lib().gffx_hip_pileup_fold_rows()), int(lib().gffx_hip_pileup_scan_tile())
 
 
+def _profile_constants() -> Tuple[int, int]:
+    """(new rows per fold, records per block of the scan kernels) of the depth profile as the library was built."""
+    return int(lib().gffx_hip_profile_fold_rows()), int(lib().gffx_hip_profile_scan_tile())
+
+
 def __getattr__(name: str):
-    # PILEUP_FOLD / PILEUP_SCAN_TILE: asked of the library on first use, so that importing this module loads nothing
+    # PILEUP_FOLD / PILEUP_SCAN_TILE, PROFILE_FOLD / PROFILE_SCAN_TILE: asked of the library on first use, so that importing
+    # this module loads nothing
     if name in ("PILEUP_FOLD", "PILEUP_SCAN_TILE"):
         fold, tile = _pileup_constants()
         globals().update(PILEUP_FOLD=fold, PILEUP_SCAN_TILE=tile)
         return fold if name == "PILEUP_FOLD" else tile
+    if name in ("PROFILE_FOLD", "PROFILE_SCAN_TILE"):
+        fold, tile = _profile_constants()
+        globals().update(PROFILE_FOLD=fold, PROFILE_SCAN_TILE=tile)
+        return fold if name == "PROFILE_FOLD" else tile
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -659,6 +669,81 @@ class Pileup:
         check(lib().gffx_hip_pileup_stage_ms(self._h, *[C.byref(x) for x in st]))
         return {"kernel_ms": ms.value, "rows": rows.value, "folds": folds.value, "keys_ms": st[0].value, "sorts_ms": st[1].value,
                 "scan_ms": st[2].value, "segments_ms": st[3].value}
+
+
+class DepthProfile:
+    """gffx_hip_profile_*: the per-base depth of the rows added so far as canonical points per seqid (`gffx coverage
+    --thresholds / --bedgraph`): (pos_i, d_i) with d_i the depth on [pos_i, pos_{i+1}), d_i != d_{i-1}, the last depth 0.
+    A function of the multiset of rows: any grouping into ``add`` calls, any order and profiles merged with ``add_points``
+    give the same points bit for bit."""
+
+    def __init__(self, n_seq: int, device: int = 0):
+        self.n_seq = int(n_seq)
+        self._h = C.c_void_p()
+        check(lib().gffx_hip_profile_create(int(device), self.n_seq, C.byref(self._h)))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().gffx_hip_profile_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, rows) -> None:
+        r = _u32(rows).reshape(-1, 3)
+        check(lib().gffx_hip_profile_add_host(self._h, _p(r), r.shape[0]))
+
+    def add_store(self, store, k: int, first: int, n_rows: int) -> None:
+        """Rows [first, first + n_rows) of the last append from staging buffer k of ``store`` (a RegionStore or a raw handle)."""
+        handle = store.handle if isinstance(store, RegionStore) else store
+        check(lib().gffx_hip_profile_add_store(self._h, handle, int(k), int(first), int(n_rows)))
+
+    def add_points(self, p_off, pos, depth) -> None:
+        """Another profile's ``points()``: the merge over devices.  Points that are not canonical are refused."""
+        o = np.ascontiguousarray(p_off, dtype=np.uint64)
+        a, b = _u32(pos), _u32(depth)
+        if len(o) != self.n_seq + 1 or len(a) != len(b) or (len(o) and int(o[-1]) != len(a)):
+            raise ValueError("p_off must have n_seq + 1 entries and end at the number of points")
+        check(lib().gffx_hip_profile_add_points(self._h, o.ctypes.data_as(u64p), _p(a), _p(b)))
+
+    def finish(self) -> None:
+        check(lib().gffx_hip_profile_finish(self._h))
+
+    @property
+    def n_points(self) -> int:
+        return int(lib().gffx_hip_profile_n_points(self._h))
+
+    def points(self):
+        """(p_off, pos, depth) after ``finish``."""
+        o = np.zeros(self.n_seq + 1, dtype=np.uint64)
+        check(lib().gffx_hip_profile_copy_points(self._h, o.ctypes.data_as(u64p), None, None))  # (GFFX_E_STATE before finish)
+        n = int(o[-1])
+        a, b = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+        check(lib().gffx_hip_profile_copy_points(self._h, None, _p(a), _p(b)))
+        return o, a[:n], b[:n]
+
+    def union_at_least(self, T: int) -> "RegionUnion":
+        """The spans "depth >= T" as a finished RegionUnion on the profile's device (written there, never copied out)."""
+        h = C.c_void_p()
+        check(lib().gffx_hip_profile_union_at_least(self._h, int(T), C.byref(h)))
+        u = RegionUnion.__new__(RegionUnion)
+        u.n_seq, u._h = self.n_seq, h
+        return u
+
+    def reset(self) -> None:
+        check(lib().gffx_hip_profile_reset(self._h))
+
+    def stats(self) -> Dict[str, float]:
+        ms, rows, folds = C.c_double(0), C.c_uint64(0), C.c_uint64(0)
+        check(lib().gffx_hip_profile_stats(self._h, C.byref(ms), C.byref(rows), C.byref(folds)))
+        st = [C.c_double(0) for _ in range(4)]
+        check(lib().gffx_hip_profile_stage_ms(self._h, *[C.byref(x) for x in st]))
+        return {"kernel_ms": ms.value, "rows": rows.value, "folds": folds.value, "events_ms": st[0].value, "sort_ms": st[1].value,
+                "scan_ms": st[2].value, "points_ms": st[3].value}
 
 
 def run_batches(batches: Sequence["QueryBatch"], mode: int = OverlapMode.Overlap, invert: bool = False, out_flags: int = OUT_FIDS,

@@ -20,6 +20,7 @@
  *   merge_intervals + the two-pointer walk              gffx_hip_segments_covered, gffx_hip_union_* (`gffx coverage`)
  *     (commands/coverage.rs:92-124, :339-364)
  *   (no reference item: the reference reports no per-base depth)  gffx_hip_pileup_* (`gffx coverage --mean-depth`)
+ *   (no reference item)                                           gffx_hip_profile_* (`gffx coverage --thresholds / --bedgraph`)
  *   bam::Reader records -> (chr, start, end) rows        gffx_hip_bgzf_inflate, gffx_hip_bam_* (BAM sources)
  *     (commands/depth.rs:297-372, coverage.rs:125-168)
  *   the same reader on a .sam file                       gffx_hip_sam_* (SAM sources, plain or BGZF-compressed)
@@ -187,6 +188,7 @@ typedef struct gffx_hip_sam gffx_hip_sam;
 typedef struct gffx_hip_bed gffx_hip_bed;
 typedef struct gffx_hip_union gffx_hip_union;
 typedef struct gffx_hip_pileup gffx_hip_pileup;
+typedef struct gffx_hip_profile gffx_hip_profile;
 
 int gffx_hip_abi_version(void);
 /* number of visible HIP devices (0 when none / no driver); never fails */
@@ -503,6 +505,57 @@ int gffx_hip_pileup_stage_ms(const gffx_hip_pileup *, double *keys, double *sort
 uint64_t gffx_hip_pileup_fold_rows(void);
 uint32_t gffx_hip_pileup_scan_tile(void);
 void gffx_hip_pileup_destroy(gffx_hip_pileup *);
+
+/* ---- depth profile: how deep every base is covered (`gffx coverage --thresholds / --bedgraph`; an addition, the reference has
+ * no such figure) --
+ * Coordinates are 0-based and half-open.  For seqid c and the rows [s, e) added so far, depth_c(x) = #{rows with s <= x < e}.
+ * The CANONICAL profile of a seqid is the list of points (pos_i, d_i): pos strictly ascending, d_i the depth on
+ * [pos_i, pos_{i+1}), d_i != d_{i-1} (d_{-1} = 0, so d_0 != 0), the last depth 0; a seqid without rows has no points.  It is a
+ * function of the multiset of rows only: ANY grouping of the rows into _add calls, any order, and profiles merged with
+ * _add_points give the same points bit for bit.  Rows must have seqid < n_seq (else GFFX_E_CHR_RANGE, looked at first) and
+ * start < end (else GFFX_E_INVALID), as for the union builder and the pileup.
+ * Depths are uint32_t: a profile that has been given 2^32 - 1 rows refuses further rows with GFFX_E_INVALID (for points merged
+ * in with _add_points their largest depth counts as that many rows).  One fold sorts the points carried so far plus two records
+ * per new row; together they must stay below the device sort's limit of 2^30 records, beyond it the add fails with
+ * GFFX_E_INVALID and a message that says so.  Nothing is allocated per base (device/profile.hip, device/profile_core.hpp).
+ *   _create       one object per device, on a stream of its own
+ *   _add_host     rows in host memory (copied through a pinned staging buffer inside), any number of calls
+ *   _add_store    rows [first, first + n_rows) of the chunk last appended to a region store from staging buffer k, read in place.
+ *                 Both return when the rows have been read and checked (an event behind the first kernels of the fold): the
+ *                 caller may refill the slot, the device goes on behind the call.  A call of more than _fold_rows() rows is cut
+ *                 into folds; nothing of a refused fold enters the profile.
+ *   _add_points   another profile's points as _copy_points gives them (the merge over devices).  Points that are not canonical
+ *                 are refused with GFFX_E_INVALID: positions not strictly ascending inside a seqid, a seqid whose last depth is
+ *                 not 0, a first depth of 0, two equal consecutive depths, a p_off that does not ascend from 0.  The points are
+ *                 checked on the device through the fold's error word.
+ *   _finish       waits for the folds and builds p_off (the points with seqid < c, c = 0 .. n_seq) on the device.  A later add
+ *                 makes the profile unfinished again.
+ *   _n_points     the points so far (waits for the fold in flight)
+ *   _copy_points  p_off[n_seq + 1], pos[n_points], depth[n_points]; any pointer may be NULL.  GFFX_E_STATE before _finish.
+ *   _union_at_least   the spans "depth >= T" as a union object on the profile's device: finished, the caller's to use
+ *                 (gffx_hip_union_segments_covered, _copy_spans, ...) and to destroy.  The spans are written on the device and
+ *                 never leave it.  T == 0: GFFX_E_INVALID; a T above every depth gives a union of no spans.  GFFX_E_STATE
+ *                 before _finish.  T = 1 gives exactly the union builder's spans of the same rows.
+ *   _reset        no points; the buffers stay
+ *   _stats        HIP-event milliseconds of all fold kernels so far, rows added, folds run (waits for the fold in flight)
+ *   _stage_ms     the same time by stage: the event kernels, the sort, the running depth, the compaction to points
+ *   _fold_rows / _scan_tile   constants of the build: new rows per fold, records per block of the scan kernels
+ * After a refused row, refused points or a failed HIP call the object only reports that error again; a refused ARGUMENT (NULL
+ * rows, a store on another device, rows beyond the last append, T == 0) leaves it usable. */
+int gffx_hip_profile_create(int device, uint32_t n_seq, gffx_hip_profile **out);
+int gffx_hip_profile_add_host(gffx_hip_profile *, const uint32_t *rows /* 3 per row */, uint64_t n_rows);
+int gffx_hip_profile_add_store(gffx_hip_profile *, const gffx_hip_regions *, int k, uint64_t first, uint64_t n_rows);
+int gffx_hip_profile_add_points(gffx_hip_profile *, const uint64_t *p_off, const uint32_t *pos, const uint32_t *depth);
+int gffx_hip_profile_finish(gffx_hip_profile *);
+uint64_t gffx_hip_profile_n_points(const gffx_hip_profile *);
+int gffx_hip_profile_copy_points(gffx_hip_profile *, uint64_t *p_off, uint32_t *pos, uint32_t *depth);
+int gffx_hip_profile_union_at_least(gffx_hip_profile *, uint32_t T, gffx_hip_union **out);
+int gffx_hip_profile_reset(gffx_hip_profile *);
+int gffx_hip_profile_stats(const gffx_hip_profile *, double *kernel_ms, uint64_t *rows, uint64_t *folds);
+int gffx_hip_profile_stage_ms(const gffx_hip_profile *, double *events, double *sort, double *scan, double *points);
+uint64_t gffx_hip_profile_fold_rows(void);
+uint32_t gffx_hip_profile_scan_tile(void);
+void gffx_hip_profile_destroy(gffx_hip_profile *);
 
 /* ---- BAM sources of `gffx depth` / `gffx coverage` (commands/depth.rs:297-427, commands/coverage.rs:125-204) --
  * BGZF members are inflated on the device (one wave per member, device/bgzf.hip; the decoder, device/bgzf_core.hpp, is

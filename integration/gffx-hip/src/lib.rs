@@ -49,6 +49,10 @@ pub struct gffx_hip_union {
 pub struct gffx_hip_pileup {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct gffx_hip_profile {
+    _p: [u8; 0],
+}
 
 pub const GFFX_MODE_CONTAINED: c_int = 0; // OverlapMode::Contained       intersect.rs:75
 pub const GFFX_MODE_CONTAINS_REGION: c_int = 1; // OverlapMode::ContainsRegion  intersect.rs:76
@@ -248,6 +252,21 @@ extern "C" {
     pub fn gffx_hip_pileup_fold_rows() -> u64;
     pub fn gffx_hip_pileup_scan_tile() -> u32;
     pub fn gffx_hip_pileup_destroy(p: *mut gffx_hip_pileup);
+    // the per-base depth as canonical points per seqid (`gffx coverage --thresholds / --bedgraph`): any grouping gives the same points
+    pub fn gffx_hip_profile_create(device: c_int, n_seq: u32, out: *mut *mut gffx_hip_profile) -> c_int;
+    pub fn gffx_hip_profile_add_host(p: *mut gffx_hip_profile, rows: *const u32, n_rows: u64) -> c_int;
+    pub fn gffx_hip_profile_add_store(p: *mut gffx_hip_profile, r: *const gffx_hip_regions, k: c_int, first: u64, n_rows: u64) -> c_int;
+    pub fn gffx_hip_profile_add_points(p: *mut gffx_hip_profile, p_off: *const u64, pos: *const u32, depth: *const u32) -> c_int;
+    pub fn gffx_hip_profile_finish(p: *mut gffx_hip_profile) -> c_int;
+    pub fn gffx_hip_profile_n_points(p: *const gffx_hip_profile) -> u64;
+    pub fn gffx_hip_profile_copy_points(p: *mut gffx_hip_profile, p_off: *mut u64, pos: *mut u32, depth: *mut u32) -> c_int;
+    pub fn gffx_hip_profile_union_at_least(p: *mut gffx_hip_profile, t: u32, out: *mut *mut gffx_hip_union) -> c_int;
+    pub fn gffx_hip_profile_reset(p: *mut gffx_hip_profile) -> c_int;
+    pub fn gffx_hip_profile_stats(p: *const gffx_hip_profile, kernel_ms: *mut f64, rows: *mut u64, folds: *mut u64) -> c_int;
+    pub fn gffx_hip_profile_stage_ms(p: *const gffx_hip_profile, events: *mut f64, sort: *mut f64, scan: *mut f64, points: *mut f64) -> c_int;
+    pub fn gffx_hip_profile_fold_rows() -> u64;
+    pub fn gffx_hip_profile_scan_tile() -> u32;
+    pub fn gffx_hip_profile_destroy(p: *mut gffx_hip_profile);
 }
 
 fn last_error() -> String {

@@ -2,10 +2,11 @@
 GENCODE-shaped GFF with its index, runs `gffx coverage -v --stats-json` on them and prints the stage timers, the union's
 HIP-event kernel time and its fraction of the HBM roofline (algorithmic bytes: 12 per row in + 16 per span out) as one JSON
 object.  The files are kept in --dir between runs (the name carries N and the seed), so another build of the binary can be
-timed on the same input with --gffx.  --mean-depth times the run with that flag (the pileup's stage times are in `counts`);
+timed on the same input with --gffx.  --mean-depth times the run with that flag (the pileup's stage times are in `counts`),
+--thresholds T1,T2,... and --bedgraph the run with those (the depth profile's stage times are in `counts` as profile_*);
 `wall_runs_s` lists every run, so a median of five after a warm-up is --runs 6 without its first entry.
 Usage: python tools/coverage_bench.py [--rows 20000000] [--gpus 1] [--genes 63000] [--seed 5] [--dir DIR] [--gffx PATH] [--runs 2]
-                                      [--threads N] [--mean-depth]"""
+                                      [--threads N] [--mean-depth] [--thresholds 1,10,30] [--bedgraph]"""
 import argparse
 import json
 import os
@@ -49,6 +50,8 @@ def main():
     ap.add_argument("--runs", type=int, default=2, help="timed runs; the last one is reported (the first warms the page cache)")
     ap.add_argument("--threads", type=int, default=0, help="-t of the command (default: the command's own)")
     ap.add_argument("--mean-depth", action="store_true", help="run with --mean-depth")
+    ap.add_argument("--thresholds", default=None, help="run with --thresholds LIST")
+    ap.add_argument("--bedgraph", action="store_true", help="run with --bedgraph (the file goes beside the output)")
     a = ap.parse_args()
     if a.dir is None:
         import atexit
@@ -74,6 +77,10 @@ def main():
         cmd += ["-t", str(a.threads)]
     if a.mean_depth:
         cmd += ["--mean-depth"]
+    if a.thresholds:
+        cmd += ["--thresholds", a.thresholds]
+    if a.bedgraph:
+        cmd += ["--bedgraph", os.path.join(a.dir, "coverage.bedgraph")]
     wall, walls = 0.0, []
     for _ in range(max(1, a.runs)):
         t0 = time.time()
@@ -87,6 +94,8 @@ def main():
     res = {"rows": a.rows, "gpus": a.gpus, "bed_bytes": os.path.getsize(bed), "wall_s": round(wall, 3), "wall_runs_s": walls,
            "total_ms": st["total_ms"], "stages_ms": st["stages_ms"], "counts": st.get("counts", {}),
            "output_rows": sum(1 for _ in open(out, "rb")) - 1}
+    if a.bedgraph:
+        res["bedgraph_bytes"] = os.path.getsize(os.path.join(a.dir, "coverage.bedgraph"))
     c = res["counts"]
     if c.get("union_kernels_ms"):
         algo = 12.0 * c["rows"] + 16.0 * c["union_spans"]
