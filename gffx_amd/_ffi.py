@@ -115,6 +115,20 @@ SIGNATURES = {
     "gffx_hip_pileup_fold_rows": (C.c_uint64, []),
     "gffx_hip_pileup_scan_tile": (C.c_uint32, []),
     "gffx_hip_pileup_destroy": (None, [vp]),
+    "gffx_hip_closest_create": (C.c_int, [vp, C.c_uint64, C.POINTER(vp)]),
+    "gffx_hip_closest_run_host": (C.c_int, [vp, u32p, C.c_uint64, C.c_uint32]),
+    "gffx_hip_closest_run_store": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32]),
+    "gffx_hip_closest_wait": (C.c_int, [vp]),
+    "gffx_hip_closest_total_pairs": (C.c_int, [vp, u64p]),
+    "gffx_hip_closest_copy_counts": (C.c_int, [vp, u32p]),
+    "gffx_hip_closest_copy_offsets": (C.c_int, [vp, u64p]),
+    "gffx_hip_closest_copy_triples": (C.c_int, [vp, u32p]),
+    "gffx_hip_closest_copy_gaps": (C.c_int, [vp, u32p]),
+    "gffx_hip_closest_copy_end_table": (C.c_int, [vp, u32p, u32p]),
+    "gffx_hip_closest_last_kernel_ms": (C.c_int, [vp, C.POINTER(C.c_double)]),
+    "gffx_hip_closest_last_grid": (C.c_int, [vp, u32p, u64p]),
+    "gffx_hip_closest_stats": (C.c_int, [vp, C.POINTER(C.c_double), u64p]),
+    "gffx_hip_closest_destroy": (None, [vp]),
     "gffx_hip_profile_create": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(vp)]),
     "gffx_hip_profile_add_host": (C.c_int, [vp, u32p, C.c_uint64]),
     "gffx_hip_profile_add_store": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64]),

@@ -13,6 +13,7 @@
 //   gffx::sam::read_rows                                                         depth.rs:588-591 / coverage.rs:520-541 (SAM source)
 //   gffx::commands::extract::{ExtractArgs, run_extract}                          commands/extract.rs (extract.cpp)
 //   gffx::commands::search::{SearchArgs, run_search}                             commands/search.rs (search.cpp, regex_dfa.cpp)
+//   gffx::commands::closest::{ClosestArgs, run}                                  (no reference item; closest.cpp)
 // Compute (Join A, Join B) goes through include/gffx_hip.h only; there is no CPU join here.
 #pragma once
 #include <algorithm>
@@ -460,6 +461,28 @@ struct SearchArgs {  // search.rs:25-51
 void run_search(const SearchArgs &args);
 
 }  // namespace search
+
+// ---- `gffx closest` (an addition: the reference has no such command) -------------------------------------------------------
+namespace closest {
+
+enum class Side { Both, Left, Right };
+
+struct ClosestArgs {
+    CommonArgs common;                  // -i, -o, -t, -v (no -e, no -T: the output is a table, not GFF lines)
+    std::optional<std::string> region;  // -r/--region chr:start-end
+    std::optional<std::string> bed;     // -b/--bed (what `intersect -b` accepts)
+    bool ignore_overlaps = false;       // --ignore-overlaps
+    Side side = Side::Both;             // --side both|left|right
+    int device = 0;                     // --device
+};
+
+// For every region the root features nearest to it (device/closest_core.hpp has the rule), one output line per answered root:
+// chr, start, end as parsed, the root's ID, its 0-based half-open coordinates and the signed distance; a region without an
+// answer gives one line with "." in the last four columns.  A BED file streams chunk by chunk (GFFX_CHUNK_BYTES / GFFX_CHUNK_MB);
+// results never depend on the chunk size or on -t.
+void run(const ClosestArgs &args);
+
+}  // namespace closest
 }  // namespace commands
 
 // ---- BAM sources of depth / coverage (bam.cpp; commands/depth.rs:297-372, coverage.rs:125-168) ------------------------
@@ -494,7 +517,7 @@ std::vector<uint32_t> read_rows(const std::string &path, const std::unordered_ma
                                 int device, bool verbose);
 }  // namespace bed
 
-// main.rs: `gffx <index|intersect|extract|search|depth|coverage> ...`; returns the process exit code
+// main.rs: `gffx <index|intersect|extract|search|depth|coverage|closest> ...`; returns the process exit code
 int cli_main(int argc, char **argv);
 
 }  // namespace gffx

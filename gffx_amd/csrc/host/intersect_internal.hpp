@@ -1,5 +1,6 @@
 // intersect_internal.hpp -- shared by the files of `gffx intersect` (bed_parse, shard, join_a_stream, match_lines), not in gffx.hpp
 #pragma once
+#include <cstdlib>
 #include <cstring>
 
 #include "fast_fields.hpp"
@@ -59,6 +60,21 @@ class SeqidTable {
 // in file order, as in the serial loop of the reference.  (bed_parse.cpp)
 void parse_bed_pieces(std::string_view d, size_t a, size_t z, bool last, const SeqidTable &seqid_map, size_t threads,
                       std::vector<std::vector<uint32_t>> &piece, WorkerPool *workers = nullptr);
+
+// BED text per streamed chunk (join_a_stream.cpp has the measurements behind the 16 MB).  GFFX_CHUNK_MB (1..1024) overrides
+// it for experiments.  GFFX_CHUNK_BYTES (a decimal number, 1..1 << 30; anything else is ignored) gives the size in bytes and goes
+// before GFFX_CHUNK_MB: a few hundred bytes put a chunk boundary after every few rows of a small file; results never depend on either.
+inline size_t stream_chunk_bytes() {
+    if (const char *b = std::getenv("GFFX_CHUNK_BYTES"); b && *b >= '0' && *b <= '9') {  // (strtoull alone takes "-5" and " 7")
+        char *end = nullptr;
+        const unsigned long long v = std::strtoull(b, &end, 10);
+        if (end && !*end && v >= 1 && v <= (1ull << 30)) return static_cast<size_t>(v);
+    }
+    const char *e = std::getenv("GFFX_CHUNK_MB");
+    const long v = e ? std::atol(e) : 0;
+    return static_cast<size_t>(v >= 1 && v <= 1024 ? v : 16) << 20;
+}
+constexpr size_t kMinBedRowBytes = 6;  // a row is at least "a\t1\t2\n"
 
 // The text in chunks of about chunk_bytes that end at a line start (or at the end of the text): fn(pos, end, last) for each,
 // in file order, until fn returns false.  An empty text is one empty, last chunk.

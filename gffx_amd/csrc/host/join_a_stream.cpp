@@ -76,20 +76,10 @@ namespace {
 // BED text per chunk; a row is at least 6 bytes ("a\t1\t2\n"), and the two pinned staging buffers and the two batches of a
 // device are sized for a chunk of such rows: creating them is on the critical path once the parser is fast (100 M rows,
 // "region stores + batches": 101 ms with 128 MB chunks, 70 with 64, 43 with 32, 36 with 16; whole run 0.73 / 0.65 / 0.58 /
-// 0.53 s).  GFFX_CHUNK_MB (1..1024) overrides the 16 MB for experiments.  GFFX_CHUNK_BYTES (a decimal number, 1..1 << 30;
-// anything else is ignored) gives the size in bytes and goes before GFFX_CHUNK_MB: a few hundred bytes put a chunk boundary
-// after every few rows of a small file (tests/test_chunked_cli_gpu.py); results never depend on either.
-static const size_t kChunkBytes = [] {
-    if (const char *b = std::getenv("GFFX_CHUNK_BYTES"); b && *b >= '0' && *b <= '9') {  // (strtoull alone takes "-5" and " 7")
-        char *end = nullptr;
-        const unsigned long long v = std::strtoull(b, &end, 10);
-        if (end && !*end && v >= 1 && v <= (1ull << 30)) return static_cast<size_t>(v);
-    }
-    const char *e = std::getenv("GFFX_CHUNK_MB");
-    const long v = e ? std::atol(e) : 0;
-    return static_cast<size_t>(v >= 1 && v <= 1024 ? v : 16) << 20;
-}();
-constexpr size_t kMinRowBytes = 6;
+// 0.53 s).  GFFX_CHUNK_MB / GFFX_CHUNK_BYTES override the 16 MB (stream_chunk_bytes, intersect_internal.hpp;
+// tests/test_chunked_cli_gpu.py); results never depend on either.
+static const size_t kChunkBytes = stream_chunk_bytes();
+constexpr size_t kMinRowBytes = kMinBedRowBytes;
 
 using Pieces = std::vector<std::vector<uint32_t>>;  // the rows of one chunk, as parse_bed_pieces leaves them
 

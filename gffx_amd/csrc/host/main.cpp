@@ -1,5 +1,5 @@
 // main.cpp -- `gffx` command line for the intersect path: `gffx index` (prerequisite),
-// `gffx intersect`, `gffx extract`, `gffx search` and `gffx depth` (BED source) (reference: main.rs:11-39, commands/depth.rs:34-72, commands/extract.rs:16-35, commands/search.rs:18-51, commands/index.rs:11-23, commands/intersect.rs:32-70,
+// `gffx intersect`, `gffx extract`, `gffx search`, `gffx depth` (BED source) and `gffx closest` (an addition) (reference: main.rs:11-39, commands/depth.rs:34-72, commands/extract.rs:16-35, commands/search.rs:18-51, commands/index.rs:11-23, commands/intersect.rs:32-70,
 // utils/common.rs:17-52).  Flag names, short flags, defaults and groups follow the reference's
 // clap derive; usage errors exit 2 like clap, run-time errors print `Error: <msg>` and exit 1.
 #include <unistd.h>
@@ -94,6 +94,7 @@ const char *kTopUsage =
     "  search     Search features by attribute values (MI355X engine)\n"
     "  depth      Compute coverage depth across genomic features from a BED, BAM or SAM file (MI355X engine)\n"
     "  coverage   Compute coverage breadth across genomic features from a BED, BAM or SAM file (MI355X engine)\n"
+    "  closest    Report the nearest root features of a region or of the regions of a BED file (MI355X engine)\n"
     "  help       Print this message\n";
 
 const char *kIntersectUsage =
@@ -167,6 +168,24 @@ const char *kCoverageUsage =
     "                           which counts only rows that hit the feature's root) and their share of the lines' bases\n"
     "      --bedgraph <FILE>    Write the per-base depth of the source rows as a bedGraph (seqid, start, end, depth; depth > 0)\n"
     "      --stats-json <FILE>  Write the run's stage timers and counts as one JSON object\n";
+
+const char *kClosestUsage =
+    "Usage: gffx closest [OPTIONS] --input <FILE> <--region <REGION>|--bed <BED>>\n\nOptions:\n"
+    "  -i, --input <FILE>       Input GFF file path\n"
+    "  -o, --output <FILE>      Output file (stdout if not provided)\n"
+    "  -r, --region <REGION>    Single region in format \"chr:start-end\"\n"
+    "  -b, --bed <BED>          BED file containing regions (plain or bgzipped, as for intersect)\n"
+    "      --ignore-overlaps    Do not report features that overlap the region: the nearest ones beside it\n"
+    "      --side <SIDE>        Which features count beside the overlapping ones: both, left (ending at or before the\n"
+    "                           region's start) or right (starting at or after its end) [default: both]\n"
+    "  -t, --threads <NUM>      Number of threads for parallel processing [default: 12]\n"
+    "  -v, --verbose            Enable verbose output\n"
+    "      --device <N>         HIP device to run on [default: 0]\n"
+    "      --stats-json <FILE>  Write the run's stage timers and counts as one JSON object\n\n"
+    "Output: a header line, then one line per nearest root feature, in the order of the regions:\n"
+    "  chr, start, end (as parsed), id, feature_start, feature_end (0-based, half-open), distance (0: overlap;\n"
+    "  negative: the feature lies left of the region; adjacent intervals are 1 apart).  All features at the smallest\n"
+    "  distance are reported; a region with none prints one line with '.' in the last four columns.\n";
 
 const char *kIndexUsage =
     "Usage: gffx index [OPTIONS] --input <INPUT>\n\nOptions:\n"
@@ -362,6 +381,43 @@ int run_coverage_cli(int argc, char **argv) {
     return 0;
 }
 
+int run_closest_cli(int argc, char **argv) {
+    static const std::vector<OptSpec> specs = {{'i', "input", true},   {'o', "output", true},          {'r', "region", true}, {'b', "bed", true},
+                                               {0, "ignore-overlaps", false}, {0, "side", true},       {'t', "threads", true}, {'v', "verbose", false},
+                                               {0, "device", true},    {0, "stats-json", true},        {'h', "help", false}};
+    const auto o = parse_opts(argc, argv, 2, specs);
+    if (o.count("help")) {
+        std::fputs(kClosestUsage, stdout);
+        return 0;
+    }
+    commands::closest::ClosestArgs a;
+    if (!o.count("input")) throw UsageError("the following required arguments were not provided:\n  --input <FILE>");
+    a.common.input = o.at("input")[0];
+    if (o.count("output")) a.common.output = o.at("output")[0];
+    if (o.count("threads")) a.common.threads = parse_size(o.at("threads")[0], "--threads <NUM>");
+    a.common.verbose = o.count("verbose") > 0;
+    if (o.count("region")) a.region = o.at("region")[0];
+    if (o.count("bed")) a.bed = o.at("bed")[0];
+    if (a.region && a.bed) throw UsageError("the argument '--region <REGION>' cannot be used with '--bed <BED>'");
+    if (!a.region && !a.bed) throw UsageError("the following required arguments were not provided:\n  <--region <REGION>|--bed <BED>>");
+    a.ignore_overlaps = o.count("ignore-overlaps") > 0;
+    if (o.count("side")) {
+        const std::string &v = o.at("side")[0];
+        if (v == "both")
+            a.side = commands::closest::Side::Both;
+        else if (v == "left")
+            a.side = commands::closest::Side::Left;
+        else if (v == "right")
+            a.side = commands::closest::Side::Right;
+        else
+            throw UsageError("invalid value '" + v + "' for '--side <SIDE>'\n  [possible values: both, left, right]");
+    }
+    if (o.count("device")) a.device = static_cast<int>(parse_size(o.at("device")[0], "--device <N>"));
+    if (o.count("stats-json")) g_run_stats.path = o.at("stats-json")[0];
+    commands::closest::run(a);
+    return 0;
+}
+
 int run_index_cli(int argc, char **argv) {
     static const std::vector<OptSpec> specs = {{'i', "input", true},
                                                {'a', "attribute", true},
@@ -457,7 +513,11 @@ int cli_main(int argc, char **argv) {
             usage = kCoverageUsage;
             return run_coverage_cli(argc, argv);
         }
-        throw UsageError("unrecognized subcommand '" + cmd + "' (this build carries the intersect, extract, search, depth and coverage paths only)");
+        if (cmd == "closest") {
+            usage = kClosestUsage;
+            return run_closest_cli(argc, argv);
+        }
+        throw UsageError("unrecognized subcommand '" + cmd + "' (this build carries the intersect, extract, search, depth, coverage and closest paths only)");
     } catch (const UsageError &e) {
         std::fprintf(stderr, "error: %s\n\n%s\nFor more information, try '--help'.\n", e.what(), usage);
         return 2;

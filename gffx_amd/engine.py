@@ -671,6 +671,105 @@ class Pileup:
                 "scan_ms": st[2].value, "segments_ms": st[3].value}
 
 
+CLOSEST_IGNORE_OVERLAPS, CLOSEST_LEFT_ONLY, CLOSEST_RIGHT_ONLY = 1, 2, 4  # enum gffx_closest_flags
+_CLOSEST_SIDES = {"both": 0, "left": CLOSEST_LEFT_ONLY, "right": CLOSEST_RIGHT_ONLY}
+
+
+def closest_flags(ignore_overlaps: bool = False, side: str = "both") -> int:
+    if side not in _CLOSEST_SIDES:
+        raise ValueError("side must be 'both', 'left' or 'right', not %r" % (side,))
+    return (CLOSEST_IGNORE_OVERLAPS if ignore_overlaps else 0) | _CLOSEST_SIDES[side]
+
+
+def closest_distances(regions, counts, triples, gaps) -> np.ndarray:
+    """Signed distance of every answered root as int64, in pair order: -gap for a root left of its region (end <= region
+    start), +gap for one to the right (start >= region end), 0 for an overlap.  It follows from the triple and the region."""
+    r = _u32(regions).reshape(-1, 3).astype(np.int64)
+    t = np.asarray(triples).reshape(-1, 3).astype(np.int64)
+    c = np.asarray(counts).astype(np.int64)
+    qs, qe, g = np.repeat(r[:, 1], c), np.repeat(r[:, 2], c), np.repeat(np.asarray(gaps).astype(np.int64), c)
+    over = (t[:, 1] < qe) & (t[:, 2] > qs)
+    return np.where(over, 0, np.where(t[:, 2] <= qs, -g, g)).astype(np.int64)
+
+
+class Closest:
+    """gffx_hip_closest_*: the roots nearest to every region, and how far away (`gffx closest`).  One handle per index, on the
+    index's device; it builds the end table (the roots' ends sorted by (seqid, end)) on the device when it is created."""
+
+    def __init__(self, index: TreeIndexData, max_queries: int = 1 << 20):
+        self.index = index
+        self._h = C.c_void_p()
+        check(lib().gffx_hip_closest_create(index._h, int(max_queries), C.byref(self._h)))
+        index._batches += 1  # (the handle reads the native index, like a batch)
+        self.max_queries = int(max_queries)
+        self._nq = 0
+        self._keep = None
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().gffx_hip_closest_destroy(self._h)
+            self._h = None
+            self.index._batch_closed()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _results(self, nq: int):
+        check(lib().gffx_hip_closest_wait(self._h))
+        self._keep = None
+        total = C.c_uint64()
+        check(lib().gffx_hip_closest_total_pairs(self._h, C.byref(total)))
+        counts, gaps = np.empty(nq, dtype=np.uint32), np.empty(nq, dtype=np.uint32)
+        offsets = np.empty(nq + 1, dtype=np.uint64)
+        triples = np.empty((total.value, 3), dtype=np.uint32)
+        check(lib().gffx_hip_closest_copy_counts(self._h, _p(counts)))
+        check(lib().gffx_hip_closest_copy_offsets(self._h, offsets.ctypes.data_as(u64p)))
+        check(lib().gffx_hip_closest_copy_triples(self._h, _p(triples)))
+        check(lib().gffx_hip_closest_copy_gaps(self._h, _p(gaps)))
+        return counts, offsets, triples, gaps
+
+    def run(self, regions, ignore_overlaps: bool = False, side: str = "both", flags: Optional[int] = None):
+        """regions: (nq, 3) u32 rows (chr, start, end).  Returns counts[nq], offsets[nq + 1] (u64, the exclusive prefix in input
+        order), triples[pairs, 3] (root_fid, start, end; ascending index position inside a region) and gaps[nq] (undefined
+        where the count is 0).  `flags`, when given, is passed as it is (enum gffx_closest_flags)."""
+        r = _u32(regions).reshape(-1, 3)
+        f = closest_flags(ignore_overlaps, side) if flags is None else int(flags)
+        check(lib().gffx_hip_closest_run_host(self._h, _p(r), r.shape[0], f))
+        return self._results(r.shape[0])
+
+    def run_store(self, store: "RegionStore", k: int, first: int, n_rows: int, ignore_overlaps: bool = False, side: str = "both"):
+        """The same over rows [first, first + n_rows) of the store's last append from staging buffer k, read in place."""
+        self._keep = store
+        check(lib().gffx_hip_closest_run_store(self._h, store.handle, int(k), int(first), int(n_rows), closest_flags(ignore_overlaps, side)))
+        return self._results(int(n_rows))
+
+    def end_table(self):
+        """(e_end, e_pos): the ends of the roots sorted stably by (seqid, end), and the index position each came from."""
+        n = self.index.n_roots
+        e_end, e_pos = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
+        check(lib().gffx_hip_closest_copy_end_table(self._h, _p(e_end), _p(e_pos)))
+        return e_end, e_pos
+
+    def last_kernel_ms(self) -> float:
+        ms = C.c_double()
+        check(lib().gffx_hip_closest_last_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def last_grid(self) -> Tuple[int, int]:
+        """(blocks, regions per block) of the last run's launches."""
+        blocks, chunk = C.c_uint32(), C.c_uint64()
+        check(lib().gffx_hip_closest_last_grid(self._h, C.byref(blocks), C.byref(chunk)))
+        return blocks.value, chunk.value
+
+    def stats(self) -> Dict[str, float]:
+        ms, grows = C.c_double(), C.c_uint64()
+        check(lib().gffx_hip_closest_stats(self._h, C.byref(ms), C.byref(grows)))
+        return {"build_ms": ms.value, "grows": grows.value}
+
+
 class DepthProfile:
     """gffx_hip_profile_*: the per-base depth of the rows added so far as canonical points per seqid (`gffx coverage
     --thresholds / --bedgraph`): (pos_i, d_i) with d_i the depth on [pos_i, pos_{i+1}), d_i != d_{i-1}, the last depth 0.

@@ -21,6 +21,7 @@
  *     (commands/coverage.rs:92-124, :339-364)
  *   (no reference item: the reference reports no per-base depth)  gffx_hip_pileup_* (`gffx coverage --mean-depth`)
  *   (no reference item)                                           gffx_hip_profile_* (`gffx coverage --thresholds / --bedgraph`)
+ *   (no reference item)                                           gffx_hip_closest_* (`gffx closest`)
  *   bam::Reader records -> (chr, start, end) rows        gffx_hip_bgzf_inflate, gffx_hip_bam_* (BAM sources)
  *     (commands/depth.rs:297-372, coverage.rs:125-168)
  *   the same reader on a .sam file                       gffx_hip_sam_* (SAM sources, plain or BGZF-compressed)
@@ -189,6 +190,7 @@ typedef struct gffx_hip_bed gffx_hip_bed;
 typedef struct gffx_hip_union gffx_hip_union;
 typedef struct gffx_hip_pileup gffx_hip_pileup;
 typedef struct gffx_hip_profile gffx_hip_profile;
+typedef struct gffx_hip_closest gffx_hip_closest;
 
 int gffx_hip_abi_version(void);
 /* number of visible HIP devices (0 when none / no driver); never fails */
@@ -556,6 +558,54 @@ int gffx_hip_profile_stage_ms(const gffx_hip_profile *, double *events, double *
 uint64_t gffx_hip_profile_fold_rows(void);
 uint32_t gffx_hip_profile_scan_tile(void);
 void gffx_hip_profile_destroy(gffx_hip_profile *);
+
+/* ---- closest: the roots nearest to every region, and how far away (`gffx closest`; an addition, the reference has no such
+ * command) --
+ * Coordinates are 0-based and half-open.  The roots of the region's seqid are taken in index position order (start ascending,
+ * stable); a root [fs, fe) has fe >= fs.  For a region (c, qs, qe) with qs < qe every root of seqid c is in exactly one class:
+ *     OVER   fs < qe && fe > qs     gap 0
+ *     LEFT   fe <= qs               gap qs - fe + 1
+ *     RIGHT  fs >= qe               gap fs - qe + 1        (adjacent intervals: gap 1, as in bedtools; a gap fits 32 bits)
+ * GFFX_CLOSEST_IGNORE_OVERLAPS removes the OVER class from the candidates, GFFX_CLOSEST_LEFT_ONLY the RIGHT class,
+ * GFFX_CLOSEST_RIGHT_ONLY the LEFT class (OVER counts for every side).  The ANSWER of a region is every candidate of minimal gap,
+ * in ascending index position; a region without candidates, and a row with qs >= qe, has an empty answer (no error).  The
+ * signed distance of an answered root is -gap for LEFT, +gap for RIGHT, 0 for OVER: it follows from the triple and the region,
+ * so one gap per region is stored.  Both _ONLY bits together, or an unknown bit: GFFX_E_INVALID.
+ *   _create       on the index's device, with a stream of its own, for runs of at most max_queries regions.  Builds the END TABLE
+ *                 on the device (device/closest.hip): the roots' ends sorted stably by (seqid, end) with the position each came
+ *                 from -- equal ends keep ascending position.  The index must outlive the handle.
+ *   _run_host     regions as AoS triples (chr, start, end) in host memory (free again when the call returns)
+ *   _run_store    rows [first, first + n_rows) of the chunk last appended to a region store from staging buffer k, read in place
+ *                 (untouched until _wait).  Both run the count pass, wait for it, size the pair buffer from its total and
+ *                 enqueue the emit pass.  A row with chr >= n_chr: GFFX_E_CHR_RANGE from the _run call (nothing is read for
+ *                 that row; the run is void, the handle stays usable).
+ *   _wait         the emit pass has finished; the results below are GFFX_E_STATE before it
+ *   _total_pairs  answered roots over all regions
+ *   _copy_counts  counts[nq]; _copy_offsets  offsets[nq + 1], the exclusive prefix of the counts in INPUT order (a deterministic
+ *                 CSR); _copy_triples  (root_fid, fs, fe) per answered root, 3 * pairs words; _copy_gaps  gaps[nq], undefined
+ *                 where the count is 0
+ *   _copy_end_table   e_end[n_roots], e_pos[n_roots] (either may be NULL); seqid c's slice is that of its roots' positions
+ *   _last_kernel_ms   HIP-event milliseconds of the last run's two kernels
+ *   _last_grid    the last run's launch: blocks, and regions per block
+ *   _stats        HIP-event milliseconds of the end table's build; how often a run had to grow the pair buffer
+ * After a failed HIP call the object only reports that error again; a refused ARGUMENT (bad flags, too many regions, NULL
+ * regions, a store on another device, rows beyond the last append) and GFFX_E_CHR_RANGE leave it usable.  Without a device
+ * _create returns GFFX_E_NO_DEVICE. */
+enum gffx_closest_flags { GFFX_CLOSEST_IGNORE_OVERLAPS = 1, GFFX_CLOSEST_LEFT_ONLY = 2, GFFX_CLOSEST_RIGHT_ONLY = 4 };
+int gffx_hip_closest_create(const gffx_hip_index *, uint64_t max_queries, gffx_hip_closest **out);
+int gffx_hip_closest_run_host(gffx_hip_closest *, const uint32_t *regions /* 3 per region */, uint64_t nq, uint32_t flags);
+int gffx_hip_closest_run_store(gffx_hip_closest *, const gffx_hip_regions *, int k, uint64_t first, uint64_t n_rows, uint32_t flags);
+int gffx_hip_closest_wait(gffx_hip_closest *);
+int gffx_hip_closest_total_pairs(gffx_hip_closest *, uint64_t *pairs);
+int gffx_hip_closest_copy_counts(gffx_hip_closest *, uint32_t *counts /* nq */);
+int gffx_hip_closest_copy_offsets(gffx_hip_closest *, uint64_t *offsets /* nq + 1 */);
+int gffx_hip_closest_copy_triples(gffx_hip_closest *, uint32_t *triples /* 3 * pairs */);
+int gffx_hip_closest_copy_gaps(gffx_hip_closest *, uint32_t *gaps /* nq */);
+int gffx_hip_closest_copy_end_table(gffx_hip_closest *, uint32_t *e_end, uint32_t *e_pos);
+int gffx_hip_closest_last_kernel_ms(gffx_hip_closest *, double *ms);
+int gffx_hip_closest_last_grid(const gffx_hip_closest *, uint32_t *blocks, uint64_t *chunk);
+int gffx_hip_closest_stats(const gffx_hip_closest *, double *build_ms, uint64_t *grows);
+void gffx_hip_closest_destroy(gffx_hip_closest *);
 
 /* ---- BAM sources of `gffx depth` / `gffx coverage` (commands/depth.rs:297-427, commands/coverage.rs:125-204) --
  * BGZF members are inflated on the device (one wave per member, device/bgzf.hip; the decoder, device/bgzf_core.hpp, is
