@@ -129,6 +129,22 @@ SIGNATURES = {
     "gffx_hip_closest_last_grid": (C.c_int, [vp, u32p, u64p]),
     "gffx_hip_closest_stats": (C.c_int, [vp, C.POINTER(C.c_double), u64p]),
     "gffx_hip_closest_destroy": (None, [vp]),
+    "gffx_hip_classmap_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
+    "gffx_hip_classmap_add_rows_host": (C.c_int, [vp, u32p, C.c_uint64]),
+    "gffx_hip_classmap_finish": (C.c_int, [vp]),
+    "gffx_hip_classmap_n_points": (C.c_uint64, [vp]),
+    "gffx_hip_classmap_copy_points": (C.c_int, [vp, u64p, u32p, C.POINTER(C.c_uint8)]),
+    "gffx_hip_classmap_copy_bases": (C.c_int, [vp, u64p]),
+    "gffx_hip_classmap_run_host": (C.c_int, [vp, u32p, C.c_uint64]),
+    "gffx_hip_classmap_run_store": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64]),
+    "gffx_hip_classmap_wait": (C.c_int, [vp]),
+    "gffx_hip_classmap_copy_counts": (C.c_int, [vp, u32p]),
+    "gffx_hip_classmap_copy_class": (C.c_int, [vp, C.POINTER(C.c_uint8)]),
+    "gffx_hip_classmap_last_kernel_ms": (C.c_int, [vp, C.POINTER(C.c_double)]),
+    "gffx_hip_classmap_stage_ms": (C.c_int, [vp, C.POINTER(C.c_double)]),
+    "gffx_hip_classmap_scan_tile": (C.c_uint32, []),
+    "gffx_hip_classmap_block_size": (C.c_uint32, []),
+    "gffx_hip_classmap_destroy": (None, [vp]),
     "gffx_hip_profile_create": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(vp)]),
     "gffx_hip_profile_add_host": (C.c_int, [vp, u32p, C.c_uint64]),
     "gffx_hip_profile_add_store": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64]),

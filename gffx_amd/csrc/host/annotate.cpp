@@ -1,0 +1,220 @@
+// annotate.cpp -- `gffx annotate` above the C-ABI (an addition: the reference has no such command): for every
+// region how many of its bases are of each feature class.  -T names the layers in priority order; the class of a base is the
+// first layer with a line that covers it (device/classmap_core.hpp).  The lines come from the all-line table `<gff>.lall`
+// (or from the text when there is none), the class map is built on the device once (gffx_hip_classmap_*), and a BED file
+// streams chunk by chunk through a region store like `gffx closest`: the output -- one line per region in input order --
+// depends neither on the chunk size nor on -t.
+#include <cstdio>
+#include <cstring>
+
+#include "intersect_internal.hpp"
+#include "table_output.hpp"
+
+namespace gffx::commands::annotate {
+
+namespace {
+
+using ClassMapHandle = Handle<gffx_hip_classmap, gffx_hip_classmap_destroy>;
+using intersect::SeqidTable;
+
+// The layers' rows (layer, seqid number, start - 1, end) from the all-line table's columns.  A line counts when its type is
+// one of the names, its split succeeded and 1 <= start <= end; a line on a seqid the index does not know is skipped.
+template <typename Names>
+void collect_rows(uint64_t n_lines, const uint32_t *start, const uint32_t *end, const uint32_t *seq, const uint32_t *type, const uint8_t *flags,
+                  const Names &seq_names, const Names &type_names, const std::vector<std::string> &layers,
+                  const std::unordered_map<std::string, uint32_t> &seqid_to_num, std::vector<uint32_t> &rows, std::vector<uint64_t> &per_layer, uint64_t &skipped) {
+    std::vector<uint32_t> layer_of(type_names.size(), UINT32_MAX), seq_of(seq_names.size(), UINT32_MAX);
+    for (size_t i = 0; i < type_names.size(); ++i)
+        for (size_t k = 0; k < layers.size(); ++k)
+            if (std::string_view(type_names[i]) == layers[k]) layer_of[i] = static_cast<uint32_t>(k);
+    for (size_t i = 0; i < seq_names.size(); ++i) {
+        const auto it = seqid_to_num.find(std::string(seq_names[i]));
+        if (it != seqid_to_num.end()) seq_of[i] = it->second;
+    }
+    for (uint64_t i = 0; i < n_lines; ++i) {
+        // (0xFFFFFFFF marks a type that gff_type_allowed rejects whatever the filter: it is no index into the names)
+        if (type[i] >= layer_of.size() || layer_of[type[i]] == UINT32_MAX || !(flags[i] & 1u)) continue;
+        if (start[i] < 1 || start[i] > end[i]) continue;
+        if (seq[i] >= seq_of.size() || seq_of[seq[i]] == UINT32_MAX) {
+            ++skipped;
+            continue;
+        }
+        const uint32_t k = layer_of[type[i]];
+        rows.insert(rows.end(), {k, seq_of[seq[i]], start[i] - 1, end[i]});
+        per_layer[k]++;
+    }
+}
+
+}  // namespace
+
+void run(const AnnotateArgs &args) {
+    const bool verbose = args.common.verbose;
+    StageTimer timer{verbose};
+    const size_t threads = args.common.effective_threads();
+    const std::vector<std::string> &layers = args.layers;
+    const uint32_t T = static_cast<uint32_t>(layers.size());
+    DeviceWarmup warm(args.device);
+    TreeIndexData index_data = TreeIndexData::load_tree_index(args.common.input);
+    const uint32_t n_seq = static_cast<uint32_t>(index_data.num_to_seqid.size());
+    timer.lap("Loading tree index");
+    // the layers' rows
+    std::vector<uint32_t> rows;
+    std::vector<uint64_t> per_layer(T, 0);
+    uint64_t skipped = 0;
+    {
+        const std::string &gff_path = args.common.input;
+        const MappedFile gff = map_file_or(gff_path, "Cannot open GFF file: \"" + gff_path + "\"");
+        const char *lt = std::getenv("GFFX_LINE_TABLE");
+        std::string why = "disabled";
+        intersect::AllLinesView all;
+        bool use_all = false;
+        if (!(lt && std::string(lt) == "parse")) {
+            const index_loader::GofMap gof = index_loader::load_gof(gff_path);
+            use_all = all.open(append_suffix(gff_path, ".lall"), gff.size(), index_loader::line_table_key(gff_path, gof), why);
+        }
+        if (use_all) {
+            collect_rows(all.n_lines, all.start, all.end, all.seq, all.type, all.flags, all.seq_names, all.type_names, layers, index_data.seqid_to_num, rows,
+                         per_layer, skipped);
+        } else {
+            const intersect::AllLines A = intersect::build_all_lines(gff.view(), threads);
+            collect_rows(A.ls.size(), A.start.data(), A.end.data(), A.seq.data(), A.type.data(), A.flags.data(), A.seq_names, A.type_names, layers,
+                         index_data.seqid_to_num, rows, per_layer, skipped);
+        }
+        if (verbose && use_all) std::fprintf(stderr, "[INFO] all-line table from %s.lall (%llu lines)\n", gff_path.c_str(), (unsigned long long)all.n_lines);
+        if (verbose && !use_all) std::fprintf(stderr, "[INFO] all-line table not used (%s): parsing the text\n", why.c_str());
+    }
+    for (uint32_t k = 0; k < T; ++k) {
+        if (!per_layer[k]) std::fprintf(stderr, "[WARN] no line of %s has type '%s': its column is zero\n", args.common.input.c_str(), layers[k].c_str());
+        if (verbose) std::fprintf(stderr, "[DEBUG] annotate: layer %u '%s': %llu lines\n", k, layers[k].c_str(), (unsigned long long)per_layer[k]);
+    }
+    if (verbose) std::fprintf(stderr, "[DEBUG] annotate: %llu lines skipped (a seqid the index does not know)\n", (unsigned long long)skipped);
+    timer.lap("Layer rows from the line table");
+    std::vector<uint32_t> all_rows;
+    std::optional<MappedFile> bed_file;
+    bool device_rows = false;
+    size_t chunk_rows = 1;
+    const size_t chunk_bytes = intersect::stream_chunk_bytes();
+    if (args.region) {
+        const auto [chr, s, e] = intersect::parse_region(*args.region, index_data.seqid_to_num, args.common);
+        all_rows = {chr, s, e};
+    } else {
+        device_rows = bed::route(*args.bed) == bed::Route::Device;
+        bed_file.emplace(*args.bed);
+    }
+    warm.wait();
+    if (args.bed && device_rows) {
+        all_rows = bed::read_rows(*args.bed, index_data.seqid_to_num, bed::kIntersect, args.device, verbose);
+        timer.lap("BED rows read on the device");
+    }
+    if (args.bed)
+        chunk_rows = (device_rows ? std::min(chunk_bytes / intersect::kMinBedRowBytes, std::max<size_t>(all_rows.size() / 3, 1))
+                                  : std::min(chunk_bytes, std::max<size_t>(bed_file->size(), 1)) / intersect::kMinBedRowBytes) + 16;
+    ClassMapHandle h;
+    if (gffx_hip_classmap_create(args.device, n_seq, T, OutPtr(h)) != GFFX_OK) hip_fail("gffx_hip_classmap_create");
+    if (gffx_hip_classmap_add_rows_host(h.get(), rows.data(), rows.size() / 4) != GFFX_OK) hip_fail("gffx_hip_classmap_add_rows_host");
+    if (gffx_hip_classmap_finish(h.get()) != GFFX_OK) hip_fail("gffx_hip_classmap_finish");
+    std::vector<uint32_t>().swap(rows);
+    RegionsHandle store;
+    if (gffx_hip_regions_create(args.device, 0, chunk_rows, 0, OutPtr(store)) != GFFX_OK) hip_fail("gffx_hip_regions_create");
+    timer.lap("Class map + buffers");
+    Output out(args.common.output);
+    {
+        std::string head = "#chr\tstart\tend\tclass";
+        for (const std::string &name : layers) head.append("\t").append(name);
+        out.write(head + "\tnone\n");
+    }
+    std::vector<uint64_t> sum_regions(T + 1, 0), sum_bases(T + 1, 0);
+    std::vector<uint32_t> counts;
+    std::vector<uint8_t> cls;
+    std::string text;
+    uint64_t regions = 0;
+    double kernel_ms = 0;
+    size_t chunk = 0;
+    // n rows sit in staging buffer k: to the store, through the device, to the output
+    auto serve = [&](int k, uint64_t n) {
+        const uint32_t *stage = gffx_hip_regions_staging(store.get(), k);
+        if (gffx_hip_regions_append(store.get(), k, n) != GFFX_OK) hip_fail("gffx_hip_regions_append");
+        if (gffx_hip_classmap_run_store(h.get(), store.get(), k, 0, n) != GFFX_OK) hip_fail("gffx_hip_classmap_run_store");
+        if (gffx_hip_classmap_wait(h.get()) != GFFX_OK) hip_fail("gffx_hip_classmap_wait");
+        counts.resize(n * (T + 1)), cls.resize(n);
+        if (gffx_hip_classmap_copy_counts(h.get(), counts.data()) != GFFX_OK || gffx_hip_classmap_copy_class(h.get(), cls.data()) != GFFX_OK)
+            hip_fail("gffx_hip_classmap_copy");
+        double ms = 0;
+        if (gffx_hip_classmap_last_kernel_ms(h.get(), &ms) == GFFX_OK) kernel_ms += ms;
+        text.clear();
+        append_rows_parallel(text, n, threads, [&](size_t i, std::string &s) {  // (the staging buffer still holds the rows)
+            char buf[64];
+            s.append(index_data.num_to_seqid[stage[3 * i]]);
+            s.append(buf, std::snprintf(buf, sizeof buf, "\t%u\t%u\t", stage[3 * i + 1], stage[3 * i + 2]));
+            if (cls[i] < T)
+                s.append(layers[cls[i]]);
+            else
+                s.push_back('.');
+            for (uint32_t c = 0; c <= T; ++c) s.append(buf, std::snprintf(buf, sizeof buf, "\t%u", counts[i * (T + 1) + c]));
+            s.push_back('\n');
+        });
+        out.write(text);
+        for (uint64_t i = 0; i < n; ++i) {
+            sum_regions[std::min<uint32_t>(cls[i], T)]++;
+            for (uint32_t c = 0; c <= T; ++c) sum_bases[c] += counts[i * (T + 1) + c];
+        }
+        regions += n;
+        ++chunk;
+    };
+    auto staging = [&](int k) {
+        if (gffx_hip_regions_wait_staging(store.get(), k) != GFFX_OK) hip_fail("gffx_hip_regions_wait_staging");
+        return gffx_hip_regions_staging(store.get(), k);
+    };
+    if (args.region || device_rows) {
+        const size_t n_all = all_rows.size() / 3, step = chunk_rows > 16 ? chunk_rows - 16 : 1;
+        for (size_t at = 0; at < n_all; at += step) {
+            const size_t n = std::min(step, n_all - at);
+            const int k = static_cast<int>(chunk & 1);
+            std::memcpy(staging(k), all_rows.data() + 3 * at, n * 12);
+            serve(k, n);
+        }
+    } else {
+        const std::string_view bed_text = bed_file->view();
+        const SeqidTable seqids(index_data.seqid_to_num);
+        std::vector<std::vector<uint32_t>> piece;
+        intersect::for_each_line_chunk(bed_text, chunk_bytes, [&](size_t pos, size_t z, bool last) {
+            intersect::parse_bed_pieces(bed_text, pos, z, last, seqids, threads, piece);
+            const int k = static_cast<int>(chunk & 1);
+            uint32_t *dst = staging(k);
+            uint64_t n = 0;
+            for (const auto &p : piece) {
+                std::memcpy(dst + 3 * n, p.data(), p.size() * 4);
+                n += p.size() / 3;
+            }
+            if (n) serve(k, n);
+            return true;
+        });
+    }
+    out.close();
+    if (args.summary) {
+        Output sum(args.summary);
+        std::string s;
+        for (uint32_t c = 0; c <= T; ++c) {
+            char buf[64];
+            s.append(c < T ? layers[c] : std::string("none"));
+            s.append(buf, std::snprintf(buf, sizeof buf, "\t%llu\t%llu\n", (unsigned long long)sum_regions[c], (unsigned long long)sum_bases[c]));
+        }
+        sum.write(s);
+        sum.close();
+    }
+    timer.lap("Regions through the device + writing");
+    if (verbose) std::fprintf(stderr, "[DEBUG] annotate: %llu regions in %zu chunks\n", (unsigned long long)regions, chunk);
+    const double total_ms = timer.total();
+    double stage[6] = {0, 0, 0, 0, 0, 0};
+    (void)gffx_hip_classmap_stage_ms(h.get(), stage);
+    g_run_stats.count("regions", (double)regions);
+    g_run_stats.count("layers", (double)T);
+    g_run_stats.count("points", (double)gffx_hip_classmap_n_points(h.get()));
+    g_run_stats.count("chunks", (double)chunk);
+    g_run_stats.count("kernel_ms", kernel_ms);
+    g_run_stats.count("class_map_build_ms", stage[0] + stage[1] + stage[2] + stage[3] + stage[4] + stage[5]);
+    g_run_stats.count("threads", (double)threads);
+    g_run_stats.write("annotate", total_ms);
+}
+
+}  // namespace gffx::commands::annotate

@@ -8,6 +8,7 @@
 
 #include "../device/closest_core.hpp"
 #include "intersect_internal.hpp"
+#include "table_output.hpp"
 
 namespace gffx::commands::closest {
 
@@ -29,29 +30,6 @@ std::vector<std::string_view> fts_lines(std::string_view data) {
     }
     return ids;
 }
-
-struct Output {
-    FILE *f = stdout;
-    std::string path;
-    explicit Output(const std::optional<std::string> &p) {
-        if (!p) return;
-        path = *p;
-        f = std::fopen(path.c_str(), "wb");
-        if (!f) throw Error("Cannot create output file: \"" + path + "\"");
-    }
-    void write(const std::string &s) {
-        if (!s.empty() && std::fwrite(s.data(), 1, s.size(), f) != s.size()) throw Error("Cannot write " + (path.empty() ? std::string("stdout") : path));
-    }
-    void close() {
-        const bool own = f != stdout;
-        const int rc = own ? std::fclose(f) : std::fflush(f);
-        f = stdout;
-        if (rc != 0) throw Error("Cannot write " + (path.empty() ? std::string("stdout") : path));
-    }
-    ~Output() {
-        if (f != stdout) std::fclose(f);
-    }
-};
 
 struct Runner {
     const TreeIndexData &index;

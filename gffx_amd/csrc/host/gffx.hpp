@@ -14,6 +14,7 @@
 //   gffx::commands::extract::{ExtractArgs, run_extract}                          commands/extract.rs (extract.cpp)
 //   gffx::commands::search::{SearchArgs, run_search}                             commands/search.rs (search.cpp, regex_dfa.cpp)
 //   gffx::commands::closest::{ClosestArgs, run}                                  (no reference item; closest.cpp)
+//   gffx::commands::annotate::{AnnotateArgs, run}                                (no reference item; annotate.cpp)
 // Compute (Join A, Join B) goes through include/gffx_hip.h only; there is no CPU join here.
 #pragma once
 #include <algorithm>
@@ -483,6 +484,24 @@ struct ClosestArgs {
 void run(const ClosestArgs &args);
 
 }  // namespace closest
+
+namespace annotate {
+
+struct AnnotateArgs {
+    CommonArgs common;                  // -i, -o, -t, -v
+    std::optional<std::string> region;  // -r/--region chr:start-end
+    std::optional<std::string> bed;     // -b/--bed (what `closest -b` accepts)
+    std::vector<std::string> layers;    // -T/--types: 1 .. 32 type names in priority order, no name twice
+    std::optional<std::string> summary; // --summary FILE
+    int device = 0;                     // --device
+};
+
+// For every region the bases of each feature class (device/classmap_core.hpp has the definition): a header line
+// `#chr start end class <t1> ... <tT> none`, then one line per region in input order.  --summary adds T + 1 lines
+// `name regions bases`.  A BED file streams chunk by chunk; results never depend on the chunk size or on -t.
+void run(const AnnotateArgs &args);
+
+}  // namespace annotate
 }  // namespace commands
 
 // ---- BAM sources of depth / coverage (bam.cpp; commands/depth.rs:297-372, coverage.rs:125-168) ------------------------

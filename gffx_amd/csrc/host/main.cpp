@@ -1,5 +1,5 @@
 // main.cpp -- `gffx` command line for the intersect path: `gffx index` (prerequisite),
-// `gffx intersect`, `gffx extract`, `gffx search`, `gffx depth` (BED source) and `gffx closest` (an addition) (reference: main.rs:11-39, commands/depth.rs:34-72, commands/extract.rs:16-35, commands/search.rs:18-51, commands/index.rs:11-23, commands/intersect.rs:32-70,
+// `gffx intersect`, `gffx extract`, `gffx search`, `gffx depth` (BED source), `gffx closest` and `gffx annotate` (additions) (reference: main.rs:11-39, commands/depth.rs:34-72, commands/extract.rs:16-35, commands/search.rs:18-51, commands/index.rs:11-23, commands/intersect.rs:32-70,
 // utils/common.rs:17-52).  Flag names, short flags, defaults and groups follow the reference's
 // clap derive; usage errors exit 2 like clap, run-time errors print `Error: <msg>` and exit 1.
 #include <unistd.h>
@@ -95,6 +95,7 @@ const char *kTopUsage =
     "  depth      Compute coverage depth across genomic features from a BED, BAM or SAM file (MI355X engine)\n"
     "  coverage   Compute coverage breadth across genomic features from a BED, BAM or SAM file (MI355X engine)\n"
     "  closest    Report the nearest root features of a region or of the regions of a BED file (MI355X engine)\n"
+    "  annotate   Count the bases of a region or of the regions of a BED file by feature class (MI355X engine)\n"
     "  help       Print this message\n";
 
 const char *kIntersectUsage =
@@ -186,6 +187,23 @@ const char *kClosestUsage =
     "  chr, start, end (as parsed), id, feature_start, feature_end (0-based, half-open), distance (0: overlap;\n"
     "  negative: the feature lies left of the region; adjacent intervals are 1 apart).  All features at the smallest\n"
     "  distance are reported; a region with none prints one line with '.' in the last four columns.\n";
+
+const char *kAnnotateUsage =
+    "Usage: gffx annotate [OPTIONS] --input <FILE> --types <T1,T2,...> <--region <REGION>|--bed <BED>>\n\nOptions:\n"
+    "  -i, --input <FILE>       Input GFF file path\n"
+    "  -o, --output <FILE>      Output file (stdout if not provided)\n"
+    "  -r, --region <REGION>    Single region in format \"chr:start-end\"\n"
+    "  -b, --bed <BED>          BED file containing regions (plain or bgzipped, as for closest)\n"
+    "  -T, --types <T1,T2,...>  One to 32 feature types (column 3) in priority order, no name twice: a base belongs to the\n"
+    "                           first type with a line that covers it, e.g. CDS,five_prime_UTR,three_prime_UTR,exon,gene\n"
+    "      --summary <FILE>     Write one line per type and one for 'none': name, regions of that class, bases over all regions\n"
+    "  -t, --threads <NUM>      Number of threads for parallel processing [default: 12]\n"
+    "  -v, --verbose            Enable verbose output\n"
+    "      --device <N>         HIP device to run on [default: 0]\n"
+    "      --stats-json <FILE>  Write the run's stage timers and counts as one JSON object\n\n"
+    "Output: a header line '#chr start end class <T1> ... none', then one line per region, in the order of the regions:\n"
+    "  chr, start, end (as parsed), the first type with at least one base in the region ('.' for none), and the region's\n"
+    "  bases per type and outside all of them; the counts add up to end - start.  Strand is ignored.\n";
 
 const char *kIndexUsage =
     "Usage: gffx index [OPTIONS] --input <INPUT>\n\nOptions:\n"
@@ -418,6 +436,47 @@ int run_closest_cli(int argc, char **argv) {
     return 0;
 }
 
+int run_annotate_cli(int argc, char **argv) {
+    static const std::vector<OptSpec> specs = {{'i', "input", true},   {'o', "output", true},  {'r', "region", true}, {'b', "bed", true},
+                                               {'T', "types", true},   {0, "summary", true},   {'t', "threads", true}, {'v', "verbose", false},
+                                               {0, "device", true},    {0, "stats-json", true}, {'h', "help", false}};
+    const auto o = parse_opts(argc, argv, 2, specs);
+    if (o.count("help")) {
+        std::fputs(kAnnotateUsage, stdout);
+        return 0;
+    }
+    commands::annotate::AnnotateArgs a;
+    if (!o.count("input")) throw UsageError("the following required arguments were not provided:\n  --input <FILE>");
+    a.common.input = o.at("input")[0];
+    if (o.count("output")) a.common.output = o.at("output")[0];
+    if (o.count("threads")) a.common.threads = parse_size(o.at("threads")[0], "--threads <NUM>");
+    a.common.verbose = o.count("verbose") > 0;
+    if (o.count("region")) a.region = o.at("region")[0];
+    if (o.count("bed")) a.bed = o.at("bed")[0];
+    if (a.region && a.bed) throw UsageError("the argument '--region <REGION>' cannot be used with '--bed <BED>'");
+    if (!a.region && !a.bed) throw UsageError("the following required arguments were not provided:\n  <--region <REGION>|--bed <BED>>");
+    if (!o.count("types")) throw UsageError("the following required arguments were not provided:\n  --types <T1,T2,...>");
+    {
+        const std::string &v = o.at("types")[0];
+        for (size_t at = 0;;) {
+            const size_t c = v.find(',', at);
+            const std::string name = v.substr(at, c == std::string::npos ? std::string::npos : c - at);
+            if (name.empty()) throw UsageError("invalid value '" + v + "' for '--types <T1,T2,...>': an empty type name");
+            if (std::find(a.layers.begin(), a.layers.end(), name) != a.layers.end())
+                throw UsageError("invalid value '" + v + "' for '--types <T1,T2,...>': '" + name + "' is given twice");
+            a.layers.push_back(name);
+            if (c == std::string::npos) break;
+            at = c + 1;
+        }
+        if (a.layers.size() > 32) throw UsageError("invalid value '" + v + "' for '--types <T1,T2,...>': more than 32 types");
+    }
+    if (o.count("summary")) a.summary = o.at("summary")[0];
+    if (o.count("device")) a.device = static_cast<int>(parse_size(o.at("device")[0], "--device <N>"));
+    if (o.count("stats-json")) g_run_stats.path = o.at("stats-json")[0];
+    commands::annotate::run(a);
+    return 0;
+}
+
 int run_index_cli(int argc, char **argv) {
     static const std::vector<OptSpec> specs = {{'i', "input", true},
                                                {'a', "attribute", true},
@@ -517,7 +576,11 @@ int cli_main(int argc, char **argv) {
             usage = kClosestUsage;
             return run_closest_cli(argc, argv);
         }
-        throw UsageError("unrecognized subcommand '" + cmd + "' (this build carries the intersect, extract, search, depth, coverage and closest paths only)");
+        if (cmd == "annotate") {
+            usage = kAnnotateUsage;
+            return run_annotate_cli(argc, argv);
+        }
+        throw UsageError("unrecognized subcommand '" + cmd + "' (this build carries the intersect, extract, search, depth, coverage, closest and annotate paths only)");
     } catch (const UsageError &e) {
         std::fprintf(stderr, "error: %s\n\n%s\nFor more information, try '--help'.\n", e.what(), usage);
         return 2;

@@ -845,6 +845,94 @@ class DepthProfile:
                 "scan_ms": st[2].value, "points_ms": st[3].value}
 
 
+def _classmap_constants() -> Tuple[int, int]:
+    """(events per scan tile, regions per block of the regions kernel) of the class map."""
+    return int(lib().gffx_hip_classmap_scan_tile()), int(lib().gffx_hip_classmap_block_size())
+
+
+class ClassMap:
+    """gffx_hip_classmap_*: per region the bases of every feature class (`gffx annotate`).  ``n_layers`` layers of intervals in
+    priority order; the class of a base is the first layer that covers it, or ``n_layers`` for none.  The class map is a
+    function of the multiset of rows: any grouping into ``add_rows`` calls, any order and duplicates give the same points."""
+
+    def __init__(self, n_seq: int, n_layers: int, device: int = 0):
+        self.n_seq, self.n_layers = int(n_seq), int(n_layers)
+        self._h = C.c_void_p()
+        self._keep = None
+        check(lib().gffx_hip_classmap_create(int(device), self.n_seq, self.n_layers, C.byref(self._h)))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().gffx_hip_classmap_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add_rows(self, rows) -> None:
+        """rows: (n, 4) u32 (layer, seqid, start, end)."""
+        r = _u32(rows).reshape(-1, 4)
+        check(lib().gffx_hip_classmap_add_rows_host(self._h, _p(r), r.shape[0]))
+
+    def finish(self) -> None:
+        check(lib().gffx_hip_classmap_finish(self._h))
+
+    @property
+    def n_points(self) -> int:
+        return int(lib().gffx_hip_classmap_n_points(self._h))
+
+    def points(self):
+        """(p_off, pos, cls) after ``finish``."""
+        o = np.zeros(self.n_seq + 1, dtype=np.uint64)
+        check(lib().gffx_hip_classmap_copy_points(self._h, o.ctypes.data_as(u64p), None, None))  # (GFFX_E_STATE before finish)
+        n = int(o[-1])
+        a, b = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint8)
+        check(lib().gffx_hip_classmap_copy_points(self._h, None, _p(a), b.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return o, a[:n], b[:n]
+
+    def bases(self) -> np.ndarray:
+        """cb[k, i]: the bases of class k on all points before point i, (n_layers, n_points) u64."""
+        n = self.n_points
+        cb = np.zeros((self.n_layers, max(n, 1)), dtype=np.uint64)
+        check(lib().gffx_hip_classmap_copy_bases(self._h, cb.ctypes.data_as(u64p)) if n else lib().gffx_hip_classmap_copy_bases(self._h, None))
+        return cb[:, :n]
+
+    def _results(self, nq: int):
+        check(lib().gffx_hip_classmap_wait(self._h))
+        self._keep = None
+        counts = np.zeros((max(nq, 1), self.n_layers + 1), dtype=np.uint32)
+        cls = np.zeros(max(nq, 1), dtype=np.uint8)
+        check(lib().gffx_hip_classmap_copy_counts(self._h, _p(counts)))
+        check(lib().gffx_hip_classmap_copy_class(self._h, cls.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return counts[:nq], cls[:nq]
+
+    def run(self, regions):
+        """regions: (nq, 3) u32 rows (chr, start, end).  Returns counts[nq, n_layers + 1] and the class byte per region
+        (n_layers for none)."""
+        r = _u32(regions).reshape(-1, 3)
+        check(lib().gffx_hip_classmap_run_host(self._h, _p(r), r.shape[0]))
+        return self._results(r.shape[0])
+
+    def run_store(self, store: "RegionStore", k: int, first: int, n_rows: int):
+        """The same over rows [first, first + n_rows) of the store's last append from staging buffer k, read in place."""
+        self._keep = store
+        check(lib().gffx_hip_classmap_run_store(self._h, store.handle, int(k), int(first), int(n_rows)))
+        return self._results(int(n_rows))
+
+    def last_kernel_ms(self) -> float:
+        ms = C.c_double()
+        check(lib().gffx_hip_classmap_last_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def stage_ms(self) -> Dict[str, float]:
+        ms = (C.c_double * 6)()
+        check(lib().gffx_hip_classmap_stage_ms(self._h, ms))
+        return dict(zip(("union_ms", "toggles_ms", "sort_ms", "scan_ms", "points_ms", "bases_ms"), [float(x) for x in ms]))
+
+
 def run_batches(batches: Sequence["QueryBatch"], mode: int = OverlapMode.Overlap, invert: bool = False, out_flags: int = OUT_FIDS,
                 strategy: int = STRATEGY_AUTO, n_passes: Optional[int] = None) -> None:
     """gffx_hip_batches_run_n: pass i over batches[i % len(batches)], enqueued by ONE call.  Distinct batches of one index that

@@ -607,6 +607,45 @@ int gffx_hip_closest_last_grid(const gffx_hip_closest *, uint32_t *blocks, uint6
 int gffx_hip_closest_stats(const gffx_hip_closest *, double *build_ms, uint64_t *grows);
 void gffx_hip_closest_destroy(gffx_hip_closest *);
 
+/* ---- class map: per region the bases of every feature class (`gffx annotate`; an addition, the reference has no such
+ * command) --
+ * T layers of intervals [start, end) per seqid in priority order, 1 <= T <= 32.  class(x) = the smallest k such that an
+ * interval of layer k covers base x, or T ("none").  The CLASS MAP of a seqid is the canonical list of points (pos_i, class_i):
+ * pos strictly ascending, class_i the class on [pos_i, pos_{i+1}), class_i != class_{i-1}, the first class not T, the last
+ * class T; a seqid without intervals has no points.  It is a function of the multiset of rows: any grouping into calls, any
+ * order and duplicates give the same points bit for bit.  For a region (c, qs, qe) with qs < qe, bases_k = the bases of
+ * [qs, qe) with class k, k = 0 .. T (they add up to qe - qs), and the region's class is the smallest k < T with bases_k > 0,
+ * or T; qs >= qe gives zeros and T (device/classmap.hip, device/classmap_core.hpp).
+ *   _create        n_seq * n_layers must fit 32 bits and n_layers be 1 .. 32, else GFFX_E_INVALID
+ *   _add_rows_host rows (layer, seqid, start, end), any number of calls.  layer >= n_layers or seqid >= n_seq:
+ *                  GFFX_E_CHR_RANGE (looked at first); start >= end: GFFX_E_INVALID -- the union builder's codes.  A refused
+ *                  row is an error of the object: it only reports it again
+ *   _finish        builds the points, p_off and the running sums on the device; rows added later need another _finish
+ *   _n_points, _copy_points   p_off[n_seq + 1], pos[n_points], cls[n_points] (any may be NULL); _copy_bases  cb[k * n_points + i]
+ *                  = the bases of class k < T on all points before point i (over all seqids)
+ *   _run_host, _run_store     as for closest; GFFX_E_STATE before _finish.  A row with chr >= n_seq: GFFX_E_CHR_RANGE from the
+ *                  _run call (nothing is read for that row; the run is void, the object stays usable)
+ *   _wait, _copy_counts  counts[nq * (T + 1)], _copy_class  one byte per region (T for none), _last_kernel_ms
+ *   _stage_ms      HIP-event milliseconds of the build: union, toggles, sort, scan, points, bases
+ *   _scan_tile, _block_size   events per scan tile; regions per block of the regions kernel */
+typedef struct gffx_hip_classmap gffx_hip_classmap;
+int gffx_hip_classmap_create(int device, uint32_t n_seq, uint32_t n_layers, gffx_hip_classmap **out);
+int gffx_hip_classmap_add_rows_host(gffx_hip_classmap *, const uint32_t *rows /* 4 per row: layer, seqid, start, end */, uint64_t n_rows);
+int gffx_hip_classmap_finish(gffx_hip_classmap *);
+uint64_t gffx_hip_classmap_n_points(const gffx_hip_classmap *);
+int gffx_hip_classmap_copy_points(gffx_hip_classmap *, uint64_t *p_off, uint32_t *pos, uint8_t *cls);
+int gffx_hip_classmap_copy_bases(gffx_hip_classmap *, uint64_t *cb /* T x n_points */);
+int gffx_hip_classmap_run_host(gffx_hip_classmap *, const uint32_t *regions /* 3 per region */, uint64_t nq);
+int gffx_hip_classmap_run_store(gffx_hip_classmap *, const gffx_hip_regions *, int k, uint64_t first, uint64_t n_rows);
+int gffx_hip_classmap_wait(gffx_hip_classmap *);
+int gffx_hip_classmap_copy_counts(gffx_hip_classmap *, uint32_t *counts /* nq x (T + 1) */);
+int gffx_hip_classmap_copy_class(gffx_hip_classmap *, uint8_t *cls /* nq */);
+int gffx_hip_classmap_last_kernel_ms(gffx_hip_classmap *, double *ms);
+int gffx_hip_classmap_stage_ms(const gffx_hip_classmap *, double *ms /* 6: union, toggles, sort, scan, points, bases */);
+uint32_t gffx_hip_classmap_scan_tile(void);
+uint32_t gffx_hip_classmap_block_size(void);
+void gffx_hip_classmap_destroy(gffx_hip_classmap *);
+
 /* ---- BAM sources of `gffx depth` / `gffx coverage` (commands/depth.rs:297-427, commands/coverage.rs:125-204) --
  * BGZF members are inflated on the device (one wave per member, device/bgzf.hip; the decoder, device/bgzf_core.hpp, is
  * shared with the host).  A bad member fails the call with a message naming its file offset: a header that is not BGZF,
