@@ -145,6 +145,13 @@ SIGNATURES = {
     "gffx_hip_classmap_scan_tile": (C.c_uint32, []),
     "gffx_hip_classmap_block_size": (C.c_uint32, []),
     "gffx_hip_classmap_destroy": (None, [vp]),
+    "gffx_hip_classmap_perm_begin": (C.c_int, [vp, u32p, C.c_uint32, C.c_uint64]),
+    "gffx_hip_classmap_perm_run_host": (C.c_int, [vp, u32p, C.c_uint64, C.c_uint64]),
+    "gffx_hip_classmap_perm_run_store": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64]),
+    "gffx_hip_classmap_perm_wait": (C.c_int, [vp]),
+    "gffx_hip_classmap_perm_copy_totals": (C.c_int, [vp, u64p, u64p, u64p]),
+    "gffx_hip_classmap_perm_last_kernel_ms": (C.c_int, [vp, C.POINTER(C.c_double)]),
+    "gffx_hip_classmap_perm_group": (C.c_uint32, []),
     "gffx_hip_profile_create": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(vp)]),
     "gffx_hip_profile_add_host": (C.c_int, [vp, u32p, C.c_uint64]),
     "gffx_hip_profile_add_store": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64]),

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "classmap_core.hpp"
+#include "classmap_private.hpp"
 #include "gffx_device.hpp"
 #include "radix_sort.hpp"
 #include "regions_store.hpp"
@@ -32,9 +33,7 @@
 
 namespace gffx {
 
-constexpr int kClassThreads = 256;
 constexpr uint32_t kClassScanTile = 4 * kClassThreads;  // 4 consecutive records per thread
-constexpr uint32_t kClassErrRange = 1u;                 // a region with chr >= n_seq
 
 enum { kOpSum = 0, kOpMax = 1, kOpXor = 2 };
 template <int OP>
@@ -277,14 +276,6 @@ __global__ __launch_bounds__(kClassThreads) void k_classmap_bases(const uint32_t
     }
 }
 
-struct ClassMapView {
-    const u64 *p_off;  // n_seq + 1
-    const uint32_t *p_pos;
-    const uint8_t *p_cls;
-    const u64 *cb;
-    uint32_t n_seq, T;
-};
-
 // region i = rows[3 i ..] -> counts[i * (T + 1) ..], cls[i].  A region with chr >= n_seq sets the error word and writes nothing
 __global__ __launch_bounds__(kClassThreads) void k_classmap_regions(ClassMapView M, const uint32_t *rows, u64 nq, uint32_t *counts, uint8_t *cls, uint32_t *err) {
     const u64 i = (u64)blockIdx.x * kClassThreads + threadIdx.x;
@@ -302,57 +293,7 @@ __global__ __launch_bounds__(kClassThreads) void k_classmap_regions(ClassMapView
 
 using namespace gffx;
 
-struct gffx_hip_classmap {
-    int device = 0;
-    uint32_t n_seq = 0, T = 0;
-    int status = GFFX_OK;  // the first error: the object only reports it again
-    std::string message;
-    hipStream_t stream = nullptr;
-    // _finish: 0 .. 1 toggles, 1 .. 2 sort, 2 .. 3 scan, 3 .. 4 count, 5 .. 6 emit + offsets, 6 .. 7 bases; a run: 8 .. 9
-    hipEvent_t ev[10] = {};
-    gffx_hip_union *U = nullptr;  // one union per (layer, seqid) under pseudo-seqids
-    std::vector<uint32_t> pseudo;  // _add_rows_host: the rows as the union takes them
-    bool finished = false;
-    uint64_t n_points = 0;
-    uint32_t *p_seq = nullptr, *p_pos = nullptr;
-    uint8_t *p_cls = nullptr;
-    u64 *cb = nullptr, *p_off = nullptr;
-    uint32_t *ctl = nullptr;  // device words {err, 3 x pad, count (64 bits), 2 x pad}
-    DevArr<uint32_t> d_regions, d_counts;
-    DevArr<uint8_t> d_class;
-    uint64_t nq = 0;
-    bool ran = false, waited = false;
-    double kernel_ms = 0;
-    double stage_ms[6] = {0, 0, 0, 0, 0, 0};  // union, toggles, sort, scan, points, bases
-};
-
 namespace {
-
-int classmap_fail(gffx_hip_classmap *H, int rc) {  // rc came from fail(): keep it and its message
-    if (H->status == GFFX_OK) H->status = rc, H->message = g_last_error;
-    return rc;
-}
-#define GFFX_CLASSMAP_TRY(expr)                \
-    do {                                       \
-        const int _rc = (expr);                \
-        if (_rc) return classmap_fail(H, _rc); \
-    } while (0)
-// a HIP call of an entry point that works on the handle: its failure is kept (argument errors of a run are not)
-#define GFFX_CLASSMAP_HIP(expr) GFFX_CLASSMAP_TRY([&]() -> int { GFFX_HIP_TRY(expr); return GFFX_OK; }())
-
-int classmap_enter(const gffx_hip_classmap *H, const char *who) {
-    if (!H) return fail(GFFX_E_INVALID, "%s: classmap is NULL", who);
-    if (H->status != GFFX_OK) return fail(H->status, "%s: the object failed earlier: %s", who, H->message.c_str());
-    GFFX_HIP_TRY(hipSetDevice(H->device));
-    return GFFX_OK;
-}
-
-template <typename X>
-int classmap_alloc(X **p, uint64_t n) {
-    *p = nullptr;
-    GFFX_HIP_TRY(hipMalloc((void **)p, std::max<uint64_t>(n, 4) * sizeof(X)));
-    return GFFX_OK;
-}
 
 void classmap_drop_points(gffx_hip_classmap *H) {
     for (void *p : {(void *)H->p_seq, (void *)H->p_pos, (void *)H->p_cls, (void *)H->cb})
@@ -360,15 +301,7 @@ void classmap_drop_points(gffx_hip_classmap *H) {
     H->p_seq = H->p_pos = nullptr, H->p_cls = nullptr, H->cb = nullptr;
     H->n_points = 0;
     H->finished = false;
-}
-
-uint32_t classmap_grid(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
-
-template <typename X>
-int classmap_ensure(DevArr<X> &a, uint64_t n, const char *what) {
-    const hipError_t e = a.ensure((size_t)std::max<uint64_t>(n, 4));
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? GFFX_E_OOM : GFFX_E_HIP, "gffx_hip_classmap: no room for %s: %s", what, hipGetErrorString(e));
-    return GFFX_OK;
+    classmap_perm_drop(H);  // (permutation totals are totals over this map)
 }
 
 // the spans of the union -> points, p_off and cb.  The work buffers live for this call only
@@ -486,13 +419,6 @@ int classmap_run(gffx_hip_classmap *H, const uint32_t *rows, uint64_t nq, const 
     return GFFX_OK;
 }
 
-int classmap_ready(gffx_hip_classmap *H, const char *who) {
-    const int rc = classmap_enter(H, who);
-    if (rc) return rc;
-    if (!H->finished) return fail(GFFX_E_STATE, "%s: call gffx_hip_classmap_finish first", who);
-    return GFFX_OK;
-}
-
 int classmap_results(gffx_hip_classmap *H, const char *who) {
     const int rc = classmap_enter(H, who);
     if (rc) return rc;
@@ -515,6 +441,7 @@ extern "C" void gffx_hip_classmap_destroy(gffx_hip_classmap *H) {
     if (H->U) gffx_hip_union_destroy(H->U);
     for (hipEvent_t e : H->ev)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : H->perm_ev_free) (void)hipEventDestroy(e);  // (classmap_perm_drop has put them all here)
     if (H->stream) (void)hipStreamDestroy(H->stream);
     delete H;
 }

@@ -87,26 +87,33 @@ GFFX_HD inline u64 bases_before(const uint32_t *pos, const uint8_t *cls, const u
     return cb[j * T + k] + (cls[j] == k ? (u64)(x - pos[j]) : 0ull);
 }
 
-// THE REGION RULE over the points [lo, hi) of the region's seqid: out[0 .. T] = bases_k, returns the region's class (the
-// smallest k < T with bases_k > 0, or T).  qs >= qe gives zeros and T.  Two searches whatever T is.
-GFFX_HD inline uint32_t region_bases(const uint32_t *pos, const uint8_t *cls, const u64 *cb, uint32_t T, u64 lo, u64 hi, uint32_t qs, uint32_t qe,
-                                     uint32_t *out) {
+// THE REGION RULE over the points [lo, hi) of the region's seqid: each(k, bases_k) for every k = 0 .. T of a region with
+// qs < qe (zeros included; k ascending), returns the region's class (the smallest k < T with bases_k > 0, or T).  qs >= qe calls
+// nothing and returns T.  Two searches whatever T is.
+template <typename Each>
+GFFX_HD inline uint32_t region_bases_each(const uint32_t *pos, const uint8_t *cls, const u64 *cb, uint32_t T, u64 lo, u64 hi, uint32_t qs, uint32_t qe,
+                                          Each &&each) {
     uint32_t best = T;
-    if (qs >= qe) {
-        for (uint32_t k = 0; k <= T; ++k) out[k] = 0u;
-        return best;
-    }
+    if (qs >= qe) return best;
     u64 a, b;
     first_after_pair(pos, lo, hi, qs, qe, &a, &b);
     uint32_t rest = qe - qs;
     for (uint32_t k = 0; k < T; ++k) {
         const uint32_t n = (uint32_t)(bases_before(pos, cls, cb, T, lo, hi, b, qe, k) - bases_before(pos, cls, cb, T, lo, hi, a, qs, k));
-        out[k] = n;
+        each(k, n);
         rest -= n;
         if (n && best == T) best = k;
     }
-    out[T] = rest;
+    each(T, rest);
     return best;
+}
+
+// ... with the counts in memory: out[0 .. T] = bases_k (qs >= qe gives zeros and T)
+GFFX_HD inline uint32_t region_bases(const uint32_t *pos, const uint8_t *cls, const u64 *cb, uint32_t T, u64 lo, u64 hi, uint32_t qs, uint32_t qe,
+                                     uint32_t *out) {
+    if (qs >= qe)
+        for (uint32_t k = 0; k <= T; ++k) out[k] = 0u;
+    return region_bases_each(pos, cls, cb, T, lo, hi, qs, qe, [out](uint32_t k, uint32_t n) { out[k] = n; });
 }
 
 }  // namespace classmap

@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "intersect_internal.hpp"
+#include "layer_rows.hpp"
 #include "table_output.hpp"
 
 namespace gffx::commands::annotate {
@@ -16,34 +17,6 @@ namespace {
 
 using ClassMapHandle = Handle<gffx_hip_classmap, gffx_hip_classmap_destroy>;
 using intersect::SeqidTable;
-
-// The layers' rows (layer, seqid number, start - 1, end) from the all-line table's columns.  A line counts when its type is
-// one of the names, its split succeeded and 1 <= start <= end; a line on a seqid the index does not know is skipped.
-template <typename Names>
-void collect_rows(uint64_t n_lines, const uint32_t *start, const uint32_t *end, const uint32_t *seq, const uint32_t *type, const uint8_t *flags,
-                  const Names &seq_names, const Names &type_names, const std::vector<std::string> &layers,
-                  const std::unordered_map<std::string, uint32_t> &seqid_to_num, std::vector<uint32_t> &rows, std::vector<uint64_t> &per_layer, uint64_t &skipped) {
-    std::vector<uint32_t> layer_of(type_names.size(), UINT32_MAX), seq_of(seq_names.size(), UINT32_MAX);
-    for (size_t i = 0; i < type_names.size(); ++i)
-        for (size_t k = 0; k < layers.size(); ++k)
-            if (std::string_view(type_names[i]) == layers[k]) layer_of[i] = static_cast<uint32_t>(k);
-    for (size_t i = 0; i < seq_names.size(); ++i) {
-        const auto it = seqid_to_num.find(std::string(seq_names[i]));
-        if (it != seqid_to_num.end()) seq_of[i] = it->second;
-    }
-    for (uint64_t i = 0; i < n_lines; ++i) {
-        // (0xFFFFFFFF marks a type that gff_type_allowed rejects whatever the filter: it is no index into the names)
-        if (type[i] >= layer_of.size() || layer_of[type[i]] == UINT32_MAX || !(flags[i] & 1u)) continue;
-        if (start[i] < 1 || start[i] > end[i]) continue;
-        if (seq[i] >= seq_of.size() || seq_of[seq[i]] == UINT32_MAX) {
-            ++skipped;
-            continue;
-        }
-        const uint32_t k = layer_of[type[i]];
-        rows.insert(rows.end(), {k, seq_of[seq[i]], start[i] - 1, end[i]});
-        per_layer[k]++;
-    }
-}
 
 }  // namespace
 
@@ -61,28 +34,7 @@ void run(const AnnotateArgs &args) {
     std::vector<uint32_t> rows;
     std::vector<uint64_t> per_layer(T, 0);
     uint64_t skipped = 0;
-    {
-        const std::string &gff_path = args.common.input;
-        const MappedFile gff = map_file_or(gff_path, "Cannot open GFF file: \"" + gff_path + "\"");
-        const char *lt = std::getenv("GFFX_LINE_TABLE");
-        std::string why = "disabled";
-        intersect::AllLinesView all;
-        bool use_all = false;
-        if (!(lt && std::string(lt) == "parse")) {
-            const index_loader::GofMap gof = index_loader::load_gof(gff_path);
-            use_all = all.open(append_suffix(gff_path, ".lall"), gff.size(), index_loader::line_table_key(gff_path, gof), why);
-        }
-        if (use_all) {
-            collect_rows(all.n_lines, all.start, all.end, all.seq, all.type, all.flags, all.seq_names, all.type_names, layers, index_data.seqid_to_num, rows,
-                         per_layer, skipped);
-        } else {
-            const intersect::AllLines A = intersect::build_all_lines(gff.view(), threads);
-            collect_rows(A.ls.size(), A.start.data(), A.end.data(), A.seq.data(), A.type.data(), A.flags.data(), A.seq_names, A.type_names, layers,
-                         index_data.seqid_to_num, rows, per_layer, skipped);
-        }
-        if (verbose && use_all) std::fprintf(stderr, "[INFO] all-line table from %s.lall (%llu lines)\n", gff_path.c_str(), (unsigned long long)all.n_lines);
-        if (verbose && !use_all) std::fprintf(stderr, "[INFO] all-line table not used (%s): parsing the text\n", why.c_str());
-    }
+    layer_rows::collect(args.common.input, layers, index_data.seqid_to_num, threads, verbose, rows, per_layer, skipped, nullptr);
     for (uint32_t k = 0; k < T; ++k) {
         if (!per_layer[k]) std::fprintf(stderr, "[WARN] no line of %s has type '%s': its column is zero\n", args.common.input.c_str(), layers[k].c_str());
         if (verbose) std::fprintf(stderr, "[DEBUG] annotate: layer %u '%s': %llu lines\n", k, layers[k].c_str(), (unsigned long long)per_layer[k]);

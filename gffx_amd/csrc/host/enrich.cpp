@@ -1,0 +1,240 @@
+// enrich.cpp -- `gffx enrich` above the C-ABI (an addition: the reference has no such command): a permutation test
+// of the regions of a BED file against the feature classes of `gffx annotate`.  Every region is moved to a random place on its
+// own seqid -n times (device/enrich_core.hpp has the random numbers and the placement rule); per class the observed bases and
+// region counts are compared with the permutations'.  The class map is built as `annotate` builds it (layer_rows.hpp), the BED
+// file streams chunk by chunk through a region store, and the device keeps only two (N + 1) x (T + 1) matrices of integer
+// sums (gffx_hip_classmap_perm_*): the output depends neither on the chunk size nor on -t.
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+
+#include "intersect_internal.hpp"
+#include "layer_rows.hpp"
+#include "table_output.hpp"
+
+namespace gffx::commands::enrich {
+
+namespace {
+
+using ClassMapHandle = Handle<gffx_hip_classmap, gffx_hip_classmap_destroy>;
+using intersect::SeqidTable;
+
+// -g: `name<TAB>length` per line, further columns ignored (a .fai works); empty lines and lines that begin with '#' are
+// skipped, so are names the index does not know; of a name given twice the last line counts.  Every seqid of the index
+// must be there.
+std::vector<uint32_t> read_genome(const std::string &path, const std::vector<std::string> &num_to_seqid, const std::unordered_map<std::string, uint32_t> &seqid_to_num) {
+    const MappedFile file = map_file_or(path, "Cannot open genome file: \"" + path + "\"");
+    const std::string_view text = file.view();
+    std::vector<uint32_t> len(num_to_seqid.size(), 0);
+    std::vector<bool> seen(num_to_seqid.size(), false);
+    size_t line_no = 0;
+    for (size_t at = 0; at < text.size();) {
+        size_t nl = text.find('\n', at);
+        if (nl == std::string_view::npos) nl = text.size();
+        std::string_view line = text.substr(at, nl - at);
+        at = nl + 1;
+        ++line_no;
+        if (!line.empty() && line.back() == '\r') line.remove_suffix(1);
+        if (line.empty() || line[0] == '#') continue;
+        const size_t tab = line.find('\t');
+        const auto bad = [&](const char *what) { return Error("genome file " + path + ", line " + std::to_string(line_no) + ": " + what); };
+        if (tab == std::string_view::npos || tab == 0) throw bad("expected name<TAB>length");
+        size_t num_end = tab + 1;
+        while (num_end < line.size() && line[num_end] != '\t') ++num_end;
+        const std::string_view num = line.substr(tab + 1, num_end - tab - 1);
+        if (num.empty() || num.size() > 10) throw bad("the length is not a number below 2^32");
+        uint64_t v = 0;
+        for (const char ch : num) {
+            if (ch < '0' || ch > '9') throw bad("the length is not a number below 2^32");
+            v = v * 10 + static_cast<uint64_t>(ch - '0');
+        }
+        if (v > 0xFFFFFFFFull) throw bad("the length is not a number below 2^32");
+        const auto it = seqid_to_num.find(std::string(line.substr(0, tab)));
+        if (it == seqid_to_num.end() || it->second >= len.size()) continue;
+        len[it->second] = static_cast<uint32_t>(v), seen[it->second] = true;
+    }
+    for (size_t c = 0; c < len.size(); ++c)
+        if (!seen[c]) throw Error("genome file " + path + " has no length for seqid '" + num_to_seqid[c] + "'");
+    return len;
+}
+
+void append_float(std::string &s, double v) {
+    char buf[48];
+    if (std::isnan(v))
+        s.append("\tnan");  // (never "-nan")
+    else
+        s.append(buf, std::snprintf(buf, sizeof buf, "\t%.6g", v));
+}
+
+// one output line: X[0] observed, X[1 .. N] the permutations
+void append_stats(std::string &s, const std::string &name, const char *quantity, const std::vector<uint64_t> &X) {
+    const size_t N = X.size() - 1;
+    const double nan = std::nan(""), obs = static_cast<double>(X[0]);
+    double sum = 0, ss = 0;
+    uint64_t n_ge = 0, n_le = 0;
+    for (size_t p = 1; p <= N; ++p) sum += static_cast<double>(X[p]), n_ge += X[p] >= X[0], n_le += X[p] <= X[0];
+    // (permutations that all give one value: mean is that value and sd is 0 exactly, whatever N x value rounds to in a double)
+    bool all_equal = true;
+    for (size_t p = 2; p <= N; ++p) all_equal &= X[p] == X[1];
+    const double mean = all_equal ? static_cast<double>(X[1]) : sum / static_cast<double>(N);
+    for (size_t p = 1; p <= N && !all_equal; ++p) ss += (static_cast<double>(X[p]) - mean) * (static_cast<double>(X[p]) - mean);
+    const double sd = N > 1 ? std::sqrt(ss / static_cast<double>(N - 1)) : nan;
+    const double z = (N > 1 && sd != 0) ? (obs - mean) / sd : nan, fold = mean != 0 ? obs / mean : nan;
+    char buf[96];
+    s.append(name).append("\t").append(quantity);
+    s.append(buf, std::snprintf(buf, sizeof buf, "\t%llu", (unsigned long long)X[0]));
+    append_float(s, mean), append_float(s, sd), append_float(s, z), append_float(s, fold);
+    s.append(buf, std::snprintf(buf, sizeof buf, "\t%llu\t%llu", (unsigned long long)n_ge, (unsigned long long)n_le));
+    append_float(s, static_cast<double>(n_ge + 1) / static_cast<double>(N + 1));
+    append_float(s, static_cast<double>(n_le + 1) / static_cast<double>(N + 1));
+    s.push_back('\n');
+}
+
+}  // namespace
+
+void run(const EnrichArgs &args) {
+    const bool verbose = args.common.verbose;
+    StageTimer timer{verbose};
+    const size_t threads = args.common.effective_threads();
+    const std::vector<std::string> &layers = args.layers;
+    const uint32_t T = static_cast<uint32_t>(layers.size()), N = args.n_perm;
+    // (what needs no device comes first: a bad -g file ends the run before the device is touched)
+    TreeIndexData index_data = TreeIndexData::load_tree_index(args.common.input);
+    const uint32_t n_seq = static_cast<uint32_t>(index_data.num_to_seqid.size());
+    timer.lap("Loading tree index");
+    std::vector<uint32_t> seq_len(n_seq, 0);
+    if (args.genome) seq_len = read_genome(*args.genome, index_data.num_to_seqid, index_data.seqid_to_num);
+    DeviceWarmup warm(args.device);
+    std::vector<uint32_t> rows, seq_end(n_seq, 0);
+    std::vector<uint64_t> per_layer(T, 0);
+    uint64_t skipped = 0;
+    layer_rows::collect(args.common.input, layers, index_data.seqid_to_num, threads, verbose, rows, per_layer, skipped, &seq_end);
+    if (!args.genome) {
+        seq_len = seq_end;
+        if (verbose) std::fprintf(stderr, "[INFO] enrich: no -g: a seqid's length is the largest end of its lines, which understates the chromosome\n");
+    }
+    for (uint32_t k = 0; k < T; ++k) {
+        if (!per_layer[k]) std::fprintf(stderr, "[WARN] no line of %s has type '%s': its class is empty\n", args.common.input.c_str(), layers[k].c_str());
+        if (verbose) std::fprintf(stderr, "[DEBUG] enrich: layer %u '%s': %llu lines\n", k, layers[k].c_str(), (unsigned long long)per_layer[k]);
+    }
+    if (verbose) std::fprintf(stderr, "[DEBUG] enrich: %llu lines skipped (a seqid the index does not know)\n", (unsigned long long)skipped);
+    timer.lap("Layer rows from the line table");
+    const bool device_rows = bed::route(args.bed) == bed::Route::Device;
+    std::optional<MappedFile> bed_file;
+    bed_file.emplace(args.bed);
+    const size_t chunk_bytes = intersect::stream_chunk_bytes();
+    warm.wait();
+    std::vector<uint32_t> all_rows;
+    if (device_rows) {
+        all_rows = bed::read_rows(args.bed, index_data.seqid_to_num, bed::kIntersect, args.device, verbose);
+        timer.lap("BED rows read on the device");
+    }
+    const size_t chunk_rows = (device_rows ? std::min(chunk_bytes / intersect::kMinBedRowBytes, std::max<size_t>(all_rows.size() / 3, 1))
+                                           : std::min(chunk_bytes, std::max<size_t>(bed_file->size(), 1)) / intersect::kMinBedRowBytes) + 16;
+    ClassMapHandle h;
+    if (gffx_hip_classmap_create(args.device, n_seq, T, OutPtr(h)) != GFFX_OK) hip_fail("gffx_hip_classmap_create");
+    if (gffx_hip_classmap_add_rows_host(h.get(), rows.data(), rows.size() / 4) != GFFX_OK) hip_fail("gffx_hip_classmap_add_rows_host");
+    if (gffx_hip_classmap_finish(h.get()) != GFFX_OK) hip_fail("gffx_hip_classmap_finish");
+    std::vector<uint32_t>().swap(rows);
+    if (gffx_hip_classmap_perm_begin(h.get(), seq_len.data(), N, args.seed) != GFFX_OK) hip_fail("gffx_hip_classmap_perm_begin");
+    RegionsHandle store;
+    if (gffx_hip_regions_create(args.device, 0, chunk_rows, 0, OutPtr(store)) != GFFX_OK) hip_fail("gffx_hip_regions_create");
+    timer.lap("Class map + buffers");
+    uint64_t regions = 0;
+    double kernel_ms = 0;
+    size_t chunk = 0;
+    // n rows sit in staging buffer k: to the store and into the totals; `regions` is the global row of the first of them
+    auto serve = [&](int k, uint64_t n) {
+        if (gffx_hip_regions_append(store.get(), k, n) != GFFX_OK) hip_fail("gffx_hip_regions_append");
+        if (gffx_hip_classmap_perm_run_store(h.get(), store.get(), k, 0, n, regions) != GFFX_OK) hip_fail("gffx_hip_classmap_perm_run_store");
+        if (gffx_hip_classmap_perm_wait(h.get()) != GFFX_OK) hip_fail("gffx_hip_classmap_perm_wait");
+        double ms = 0;
+        if (gffx_hip_classmap_perm_last_kernel_ms(h.get(), &ms) == GFFX_OK) kernel_ms += ms;
+        regions += n;
+        ++chunk;
+    };
+    auto staging = [&](int k) {
+        if (gffx_hip_regions_wait_staging(store.get(), k) != GFFX_OK) hip_fail("gffx_hip_regions_wait_staging");
+        return gffx_hip_regions_staging(store.get(), k);
+    };
+    if (device_rows) {
+        const size_t n_all = all_rows.size() / 3, step = chunk_rows > 16 ? chunk_rows - 16 : 1;
+        for (size_t at = 0; at < n_all; at += step) {
+            const size_t n = std::min(step, n_all - at);
+            const int k = static_cast<int>(chunk & 1);
+            std::memcpy(staging(k), all_rows.data() + 3 * at, n * 12);
+            serve(k, n);
+        }
+    } else {
+        const std::string_view bed_text = bed_file->view();
+        const SeqidTable seqids(index_data.seqid_to_num);
+        std::vector<std::vector<uint32_t>> piece;
+        intersect::for_each_line_chunk(bed_text, chunk_bytes, [&](size_t pos, size_t z, bool last) {
+            intersect::parse_bed_pieces(bed_text, pos, z, last, seqids, threads, piece);
+            const int k = static_cast<int>(chunk & 1);
+            uint32_t *dst = staging(k);
+            uint64_t n = 0;
+            for (const auto &p : piece) {
+                std::memcpy(dst + 3 * n, p.data(), p.size() * 4);
+                n += p.size() / 3;
+            }
+            if (n) serve(k, n);
+            return true;
+        });
+    }
+    const size_t cells = (static_cast<size_t>(N) + 1) * (T + 1);
+    std::vector<uint64_t> B(cells, 0), R(cells, 0);
+    uint64_t unplaced = 0;
+    if (gffx_hip_classmap_perm_wait(h.get()) != GFFX_OK) hip_fail("gffx_hip_classmap_perm_wait");
+    if (gffx_hip_classmap_perm_copy_totals(h.get(), B.data(), R.data(), &unplaced) != GFFX_OK) hip_fail("gffx_hip_classmap_perm_copy_totals");
+    timer.lap("Regions through the device");
+    Output out(args.common.output);
+    {
+        std::string s;
+        s.append("#class\tquantity\tobserved\tmean\tsd\tz\tfold\tn_ge\tn_le\tp_ge\tp_le\n");
+        std::vector<uint64_t> X(static_cast<size_t>(N) + 1);
+        for (uint32_t k = 0; k <= T; ++k) {
+            const std::string name = k < T ? layers[k] : std::string("none");
+            for (size_t p = 0; p <= N; ++p) X[p] = B[p * (T + 1) + k];
+            append_stats(s, name, "bases", X);
+            for (size_t p = 0; p <= N; ++p) X[p] = R[p * (T + 1) + k];
+            append_stats(s, name, "regions", X);
+        }
+        out.write(s);
+    }
+    out.close();
+    if (args.perms) {
+        Output pf(args.perms);
+        std::string s;
+        char buf[32];
+        for (size_t p = 0; p <= N; ++p) {
+            s.append(buf, std::snprintf(buf, sizeof buf, "%zu", p));
+            for (const std::vector<uint64_t> *M : {&B, &R})
+                for (uint32_t k = 0; k <= T; ++k) s.append(buf, std::snprintf(buf, sizeof buf, "\t%llu", (unsigned long long)(*M)[p * (T + 1) + k]));
+            s.push_back('\n');
+            if (s.size() > (1u << 20)) pf.write(s), s.clear();
+        }
+        pf.write(s);
+        pf.close();
+    }
+    timer.lap("Statistics + writing");
+    if (unplaced)
+        std::fprintf(stderr, "[WARN] %llu regions are wider than their seqid's length%s and stayed where they are in every permutation\n", (unsigned long long)unplaced,
+                     args.genome ? "" : " (no -g: the length is the largest end of the seqid's lines)");
+    if (verbose) std::fprintf(stderr, "[DEBUG] enrich: %llu regions in %zu chunks\n", (unsigned long long)regions, chunk);
+    const double total_ms = timer.total();
+    double stage[6] = {0, 0, 0, 0, 0, 0};
+    (void)gffx_hip_classmap_stage_ms(h.get(), stage);
+    g_run_stats.count("regions", (double)regions);
+    g_run_stats.count("layers", (double)T);
+    g_run_stats.count("permutations", (double)N);
+    g_run_stats.count("unplaced", (double)unplaced);
+    g_run_stats.count("points", (double)gffx_hip_classmap_n_points(h.get()));
+    g_run_stats.count("chunks", (double)chunk);
+    g_run_stats.count("kernel_ms", kernel_ms);
+    g_run_stats.count("class_map_build_ms", stage[0] + stage[1] + stage[2] + stage[3] + stage[4] + stage[5]);
+    g_run_stats.count("threads", (double)threads);
+    g_run_stats.write("enrich", total_ms);
+}
+
+}  // namespace gffx::commands::enrich

@@ -15,6 +15,7 @@
 //   gffx::commands::search::{SearchArgs, run_search}                             commands/search.rs (search.cpp, regex_dfa.cpp)
 //   gffx::commands::closest::{ClosestArgs, run}                                  (no reference item; closest.cpp)
 //   gffx::commands::annotate::{AnnotateArgs, run}                                (no reference item; annotate.cpp)
+//   gffx::commands::enrich::{EnrichArgs, run}                                    (no reference item; enrich.cpp)
 // Compute (Join A, Join B) goes through include/gffx_hip.h only; there is no CPU join here.
 #pragma once
 #include <algorithm>
@@ -502,6 +503,27 @@ struct AnnotateArgs {
 void run(const AnnotateArgs &args);
 
 }  // namespace annotate
+
+namespace enrich {
+
+struct EnrichArgs {
+    CommonArgs common;                  // -i, -o, -t, -v
+    std::string bed;                    // -b/--bed (what `annotate -b` accepts)
+    std::vector<std::string> layers;    // -T/--types, as for annotate
+    uint32_t n_perm = 0;                // -n/--permutations: 1 .. 2^20
+    uint64_t seed = 0;                  // --seed
+    std::optional<std::string> genome;  // -g/--genome: name<TAB>length per line (a .fai works)
+    std::optional<std::string> perms;   // --perms FILE: the raw matrices
+    int device = 0;                     // --device
+};
+
+// A permutation test of the BED regions against the classes of `annotate` (device/enrich_core.hpp has the definition): a
+// header line, then per class (`t1 .. tT`, `none`) and quantity (`bases`, `regions`) one line
+// `class quantity observed mean sd z fold n_ge n_le p_ge p_le`.  --perms writes one line per row p = 0 .. N of the totals:
+// p, the T + 1 bases, the T + 1 region counts.  Results never depend on the chunk size or on -t.
+void run(const EnrichArgs &args);
+
+}  // namespace enrich
 }  // namespace commands
 
 // ---- BAM sources of depth / coverage (bam.cpp; commands/depth.rs:297-372, coverage.rs:125-168) ------------------------

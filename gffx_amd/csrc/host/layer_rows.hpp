@@ -1,0 +1,71 @@
+// layer_rows.hpp -- the rows of the class map's layers from a GFF file, shared by `gffx annotate` and `gffx enrich`: -T names
+// the layers in priority order, the lines come from the all-line table `<gff>.lall` (or from the text when there is none:
+// GFFX_LINE_TABLE=parse, a stale or missing image).
+#pragma once
+#include <cstdio>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "intersect_internal.hpp"
+
+namespace gffx::commands::layer_rows {
+
+// The layers' rows (layer, seqid number, start - 1, end) from the all-line table's columns.  A line counts when its type is
+// one of the names, its split succeeded and 1 <= start <= end; a line on a seqid the index does not know is skipped.
+// seq_end (unless NULL, sized by the caller to the index's seqids): the largest end of ANY such valid line per seqid, whatever
+// its type.
+template <typename Names>
+void collect_rows(uint64_t n_lines, const uint32_t *start, const uint32_t *end, const uint32_t *seq, const uint32_t *type, const uint8_t *flags,
+                  const Names &seq_names, const Names &type_names, const std::vector<std::string> &layers,
+                  const std::unordered_map<std::string, uint32_t> &seqid_to_num, std::vector<uint32_t> &rows, std::vector<uint64_t> &per_layer, uint64_t &skipped,
+                  std::vector<uint32_t> *seq_end) {
+    std::vector<uint32_t> layer_of(type_names.size(), UINT32_MAX), seq_of(seq_names.size(), UINT32_MAX);
+    for (size_t i = 0; i < type_names.size(); ++i)
+        for (size_t k = 0; k < layers.size(); ++k)
+            if (std::string_view(type_names[i]) == layers[k]) layer_of[i] = static_cast<uint32_t>(k);
+    for (size_t i = 0; i < seq_names.size(); ++i) {
+        const auto it = seqid_to_num.find(std::string(seq_names[i]));
+        if (it != seqid_to_num.end()) seq_of[i] = it->second;
+    }
+    for (uint64_t i = 0; i < n_lines; ++i) {
+        if (seq_end && (flags[i] & 1u) && start[i] >= 1 && start[i] <= end[i] && seq[i] < seq_of.size() && seq_of[seq[i]] < seq_end->size())
+            (*seq_end)[seq_of[seq[i]]] = std::max((*seq_end)[seq_of[seq[i]]], end[i]);
+        // (0xFFFFFFFF marks a type that gff_type_allowed rejects whatever the filter: it is no index into the names)
+        if (type[i] >= layer_of.size() || layer_of[type[i]] == UINT32_MAX || !(flags[i] & 1u)) continue;
+        if (start[i] < 1 || start[i] > end[i]) continue;
+        if (seq[i] >= seq_of.size() || seq_of[seq[i]] == UINT32_MAX) {
+            ++skipped;
+            continue;
+        }
+        const uint32_t k = layer_of[type[i]];
+        rows.insert(rows.end(), {k, seq_of[seq[i]], start[i] - 1, end[i]});
+        per_layer[k]++;
+    }
+}
+
+// ... from the file: its line table when it is usable, else its text
+inline void collect(const std::string &gff_path, const std::vector<std::string> &layers, const std::unordered_map<std::string, uint32_t> &seqid_to_num, size_t threads,
+                    bool verbose, std::vector<uint32_t> &rows, std::vector<uint64_t> &per_layer, uint64_t &skipped, std::vector<uint32_t> *seq_end) {
+    const MappedFile gff = map_file_or(gff_path, "Cannot open GFF file: \"" + gff_path + "\"");
+    const char *lt = std::getenv("GFFX_LINE_TABLE");
+    std::string why = "disabled";
+    intersect::AllLinesView all;
+    bool use_all = false;
+    if (!(lt && std::string(lt) == "parse")) {
+        const index_loader::GofMap gof = index_loader::load_gof(gff_path);
+        use_all = all.open(append_suffix(gff_path, ".lall"), gff.size(), index_loader::line_table_key(gff_path, gof), why);
+    }
+    if (use_all) {
+        collect_rows(all.n_lines, all.start, all.end, all.seq, all.type, all.flags, all.seq_names, all.type_names, layers, seqid_to_num, rows, per_layer, skipped,
+                     seq_end);
+    } else {
+        const intersect::AllLines A = intersect::build_all_lines(gff.view(), threads);
+        collect_rows(A.ls.size(), A.start.data(), A.end.data(), A.seq.data(), A.type.data(), A.flags.data(), A.seq_names, A.type_names, layers, seqid_to_num, rows,
+                     per_layer, skipped, seq_end);
+    }
+    if (verbose && use_all) std::fprintf(stderr, "[INFO] all-line table from %s.lall (%llu lines)\n", gff_path.c_str(), (unsigned long long)all.n_lines);
+    if (verbose && !use_all) std::fprintf(stderr, "[INFO] all-line table not used (%s): parsing the text\n", why.c_str());
+}
+
+}  // namespace gffx::commands::layer_rows

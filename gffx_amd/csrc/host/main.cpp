@@ -1,8 +1,9 @@
 // main.cpp -- `gffx` command line for the intersect path: `gffx index` (prerequisite),
-// `gffx intersect`, `gffx extract`, `gffx search`, `gffx depth` (BED source), `gffx closest` and `gffx annotate` (additions) (reference: main.rs:11-39, commands/depth.rs:34-72, commands/extract.rs:16-35, commands/search.rs:18-51, commands/index.rs:11-23, commands/intersect.rs:32-70,
+// `gffx intersect`, `gffx extract`, `gffx search`, `gffx depth` (BED source), `gffx closest`, `gffx annotate` and `gffx enrich` (additions) (reference: main.rs:11-39, commands/depth.rs:34-72, commands/extract.rs:16-35, commands/search.rs:18-51, commands/index.rs:11-23, commands/intersect.rs:32-70,
 // utils/common.rs:17-52).  Flag names, short flags, defaults and groups follow the reference's
 // clap derive; usage errors exit 2 like clap, run-time errors print `Error: <msg>` and exit 1.
 #include <unistd.h>
+#include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -96,6 +97,7 @@ const char *kTopUsage =
     "  coverage   Compute coverage breadth across genomic features from a BED, BAM or SAM file (MI355X engine)\n"
     "  closest    Report the nearest root features of a region or of the regions of a BED file (MI355X engine)\n"
     "  annotate   Count the bases of a region or of the regions of a BED file by feature class (MI355X engine)\n"
+    "  enrich     Test the regions of a BED file against feature classes by permutation (MI355X engine)\n"
     "  help       Print this message\n";
 
 const char *kIntersectUsage =
@@ -204,6 +206,29 @@ const char *kAnnotateUsage =
     "Output: a header line '#chr start end class <T1> ... none', then one line per region, in the order of the regions:\n"
     "  chr, start, end (as parsed), the first type with at least one base in the region ('.' for none), and the region's\n"
     "  bases per type and outside all of them; the counts add up to end - start.  Strand is ignored.\n";
+
+const char *kEnrichUsage =
+    "Usage: gffx enrich [OPTIONS] --input <FILE> --bed <BED> --types <T1,T2,...> --permutations <N>\n\nOptions:\n"
+    "  -i, --input <FILE>       Input GFF file path\n"
+    "  -o, --output <FILE>      Output file (stdout if not provided)\n"
+    "  -b, --bed <BED>          BED file containing regions (plain or bgzipped, as for annotate)\n"
+    "  -T, --types <T1,T2,...>  One to 32 feature types in priority order, as for annotate\n"
+    "  -n, --permutations <N>   Number of permutations, 1 to 1048576: every region is moved to a random place on its own\n"
+    "                           seqid N times\n"
+    "      --seed <S>           Seed of the random numbers, 64 bits [default: 0]; the same seed gives the same output\n"
+    "  -g, --genome <FILE>      Lengths of the seqids, 'name<TAB>length' per line (a .fai works: further columns are ignored).\n"
+    "                           Without it a seqid's length is the largest end of its lines in the GFF file, which understates\n"
+    "                           the real chromosome: -g is the right choice\n"
+    "      --perms <FILE>       Write the raw totals, one line per row (0: observed, 1 .. N: the permutations): the row, the\n"
+    "                           bases per type and outside all, the regions per class\n"
+    "  -t, --threads <NUM>      Number of threads for parallel processing [default: 12]\n"
+    "  -v, --verbose            Enable verbose output\n"
+    "      --device <N>         HIP device to run on [default: 0]\n"
+    "      --stats-json <FILE>  Write the run's stage timers and counts as one JSON object\n\n"
+    "Output: a header line, then per type and for 'none' one line for 'bases' and one for 'regions':\n"
+    "  class, quantity, observed, mean, sd, z, fold (observed / mean), n_ge and n_le (permutations with a value >= / <= the\n"
+    "  observed one), p_ge = (n_ge + 1) / (N + 1) and p_le.  A region wider than its seqid stays where it is (a warning says\n"
+    "  how many).  Regions may overlap each other after placement.\n";
 
 const char *kIndexUsage =
     "Usage: gffx index [OPTIONS] --input <INPUT>\n\nOptions:\n"
@@ -436,6 +461,23 @@ int run_closest_cli(int argc, char **argv) {
     return 0;
 }
 
+// -T: one to 32 names, none empty, none twice
+std::vector<std::string> parse_layers(const std::string &v) {
+    std::vector<std::string> layers;
+    for (size_t at = 0;;) {
+        const size_t c = v.find(',', at);
+        const std::string name = v.substr(at, c == std::string::npos ? std::string::npos : c - at);
+        if (name.empty()) throw UsageError("invalid value '" + v + "' for '--types <T1,T2,...>': an empty type name");
+        if (std::find(layers.begin(), layers.end(), name) != layers.end())
+            throw UsageError("invalid value '" + v + "' for '--types <T1,T2,...>': '" + name + "' is given twice");
+        layers.push_back(name);
+        if (c == std::string::npos) break;
+        at = c + 1;
+    }
+    if (layers.size() > 32) throw UsageError("invalid value '" + v + "' for '--types <T1,T2,...>': more than 32 types");
+    return layers;
+}
+
 int run_annotate_cli(int argc, char **argv) {
     static const std::vector<OptSpec> specs = {{'i', "input", true},   {'o', "output", true},  {'r', "region", true}, {'b', "bed", true},
                                                {'T', "types", true},   {0, "summary", true},   {'t', "threads", true}, {'v', "verbose", false},
@@ -456,24 +498,55 @@ int run_annotate_cli(int argc, char **argv) {
     if (a.region && a.bed) throw UsageError("the argument '--region <REGION>' cannot be used with '--bed <BED>'");
     if (!a.region && !a.bed) throw UsageError("the following required arguments were not provided:\n  <--region <REGION>|--bed <BED>>");
     if (!o.count("types")) throw UsageError("the following required arguments were not provided:\n  --types <T1,T2,...>");
-    {
-        const std::string &v = o.at("types")[0];
-        for (size_t at = 0;;) {
-            const size_t c = v.find(',', at);
-            const std::string name = v.substr(at, c == std::string::npos ? std::string::npos : c - at);
-            if (name.empty()) throw UsageError("invalid value '" + v + "' for '--types <T1,T2,...>': an empty type name");
-            if (std::find(a.layers.begin(), a.layers.end(), name) != a.layers.end())
-                throw UsageError("invalid value '" + v + "' for '--types <T1,T2,...>': '" + name + "' is given twice");
-            a.layers.push_back(name);
-            if (c == std::string::npos) break;
-            at = c + 1;
-        }
-        if (a.layers.size() > 32) throw UsageError("invalid value '" + v + "' for '--types <T1,T2,...>': more than 32 types");
-    }
+    a.layers = parse_layers(o.at("types")[0]);
     if (o.count("summary")) a.summary = o.at("summary")[0];
     if (o.count("device")) a.device = static_cast<int>(parse_size(o.at("device")[0], "--device <N>"));
     if (o.count("stats-json")) g_run_stats.path = o.at("stats-json")[0];
     commands::annotate::run(a);
+    return 0;
+}
+
+int run_enrich_cli(int argc, char **argv) {
+    static const std::vector<OptSpec> specs = {{'i', "input", true},   {'o', "output", true},       {'b', "bed", true},     {'T', "types", true},
+                                               {'n', "permutations", true}, {0, "seed", true},      {'g', "genome", true},  {0, "perms", true},
+                                               {'t', "threads", true}, {'v', "verbose", false},     {0, "device", true},    {0, "stats-json", true},
+                                               {'h', "help", false}};
+    const auto o = parse_opts(argc, argv, 2, specs);
+    if (o.count("help")) {
+        std::fputs(kEnrichUsage, stdout);
+        return 0;
+    }
+    commands::enrich::EnrichArgs a;
+    std::string missing;
+    for (const char *name : {"input", "bed", "types", "permutations"})
+        if (!o.count(name))
+            missing += std::string("\n  --") + name + (std::string(name) == "input" ? " <FILE>" : std::string(name) == "bed" ? " <BED>" : std::string(name) == "types" ? " <T1,T2,...>" : " <N>");
+    if (!missing.empty()) throw UsageError("the following required arguments were not provided:" + missing);
+    a.common.input = o.at("input")[0];
+    if (o.count("output")) a.common.output = o.at("output")[0];
+    if (o.count("threads")) a.common.threads = parse_size(o.at("threads")[0], "--threads <NUM>");
+    a.common.verbose = o.count("verbose") > 0;
+    a.bed = o.at("bed")[0];
+    a.layers = parse_layers(o.at("types")[0]);
+    {
+        const std::string &v = o.at("permutations")[0];
+        const size_t n = parse_size(v, "--permutations <N>");
+        if (n < 1 || n > (1u << 20)) throw UsageError("invalid value '" + v + "' for '--permutations <N>': 1 to 1048576 are possible");
+        a.n_perm = static_cast<uint32_t>(n);
+    }
+    if (o.count("seed")) {
+        const std::string &v = o.at("seed")[0];
+        char *end = nullptr;
+        errno = 0;
+        const unsigned long long s = std::strtoull(v.c_str(), &end, 10);
+        if (v.empty() || v[0] < '0' || v[0] > '9' || *end || errno == ERANGE) throw UsageError("invalid value '" + v + "' for '--seed <S>': a number below 2^64 is expected");
+        a.seed = s;
+    }
+    if (o.count("genome")) a.genome = o.at("genome")[0];
+    if (o.count("perms")) a.perms = o.at("perms")[0];
+    if (o.count("device")) a.device = static_cast<int>(parse_size(o.at("device")[0], "--device <N>"));
+    if (o.count("stats-json")) g_run_stats.path = o.at("stats-json")[0];
+    commands::enrich::run(a);
     return 0;
 }
 
@@ -580,7 +653,11 @@ int cli_main(int argc, char **argv) {
             usage = kAnnotateUsage;
             return run_annotate_cli(argc, argv);
         }
-        throw UsageError("unrecognized subcommand '" + cmd + "' (this build carries the intersect, extract, search, depth, coverage, closest and annotate paths only)");
+        if (cmd == "enrich") {
+            usage = kEnrichUsage;
+            return run_enrich_cli(argc, argv);
+        }
+        throw UsageError("unrecognized subcommand '" + cmd + "' (this build carries the intersect, extract, search, depth, coverage, closest, annotate and enrich paths only)");
     } catch (const UsageError &e) {
         std::fprintf(stderr, "error: %s\n\n%s\nFor more information, try '--help'.\n", e.what(), usage);
         return 2;

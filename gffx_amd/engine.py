@@ -932,6 +932,45 @@ class ClassMap:
         check(lib().gffx_hip_classmap_stage_ms(self._h, ms))
         return dict(zip(("union_ms", "toggles_ms", "sort_ms", "scan_ms", "points_ms", "bases_ms"), [float(x) for x in ms]))
 
+    # ---- permutation totals (`gffx enrich`) ----
+    def perm_begin(self, seq_len, n_perm: int, seed: int = 0) -> None:
+        """Start (or start over) the totals of ``n_perm`` permutations: ``seq_len[c]`` is the length of seqid c."""
+        L = _u32(seq_len).reshape(-1)
+        if len(L) != self.n_seq:
+            raise ValueError("seq_len must have n_seq entries")
+        check(lib().gffx_hip_classmap_perm_begin(self._h, _p(L), int(n_perm), int(seed) & 0xFFFFFFFFFFFFFFFF))
+        self._n_perm = int(n_perm)  # (a refused call leaves the earlier totals and their shape)
+
+    def perm_run(self, regions, first_row: int = 0) -> None:
+        """Add regions ((nq, 3) u32 rows; region j is global row ``first_row + j``) to the totals.  Asynchronous."""
+        r = _u32(regions).reshape(-1, 3)
+        check(lib().gffx_hip_classmap_perm_run_host(self._h, _p(r), r.shape[0], int(first_row)))
+
+    def perm_run_store(self, store: "RegionStore", k: int, first: int, n_rows: int, first_row: int = 0) -> None:
+        """The same over rows [first, first + n_rows) of the store's last append from staging buffer k, read in place."""
+        self._keep = store
+        check(lib().gffx_hip_classmap_perm_run_store(self._h, store.handle, int(k), int(first), int(n_rows), int(first_row)))
+
+    def perm_totals(self):
+        """Waits for the runs.  -> (bases, regions) as (n_perm + 1, n_layers + 1) u64 -- row 0 the observed data -- and
+        the number of unplaceable regions."""
+        check(lib().gffx_hip_classmap_perm_wait(self._h))
+        self._keep = None
+        shape = (getattr(self, "_n_perm", 0) + 1, self.n_layers + 1)
+        b, r, u = np.zeros(shape, np.uint64), np.zeros(shape, np.uint64), np.zeros(1, np.uint64)
+        check(lib().gffx_hip_classmap_perm_copy_totals(self._h, b.ctypes.data_as(u64p), r.ctypes.data_as(u64p), u.ctypes.data_as(u64p)))
+        return b, r, int(u[0])
+
+    def perm_last_kernel_ms(self) -> float:
+        ms = C.c_double()
+        check(lib().gffx_hip_classmap_perm_last_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
+
+def _enrich_constants() -> Tuple[int, int]:
+    """(rows of the totals per block, regions per block) of k_classmap_permute."""
+    return int(lib().gffx_hip_classmap_perm_group()), int(lib().gffx_hip_classmap_block_size())
+
 
 def run_batches(batches: Sequence["QueryBatch"], mode: int = OverlapMode.Overlap, invert: bool = False, out_flags: int = OUT_FIDS,
                 strategy: int = STRATEGY_AUTO, n_passes: Optional[int] = None) -> None:

@@ -646,6 +646,31 @@ uint32_t gffx_hip_classmap_scan_tile(void);
 uint32_t gffx_hip_classmap_block_size(void);
 void gffx_hip_classmap_destroy(gffx_hip_classmap *);
 
+/* ---- permutation totals on a finished class map (`gffx enrich`; device/enrich.hip, device/enrich_core.hpp) --
+ * Regions (c, qs, qe) with a global row i (their place in the input), a length L[c] per seqid, n_perm permutations and a seed.
+ * Row 0 of the totals is the observed data; in row p = 1 .. n_perm a region of width w = qe - qs <= L[c] lies at
+ * [s', s' + w), s' = (r(p, i) * (L[c] - w + 1)) >> 64, r(p, i) = mix64(mix64(seed + GOLD * p) + GOLD * (i + 1)) with the
+ * splitmix64 finalizer mix64 and GOLD = 0x9E3779B97F4A7C15 (a bias of at most 2^-32, not corrected).  A region with
+ * qs >= qe is empty (class T, no bases); one with w > L[c] is unplaceable: it stays where it is and is counted in `unplaced`.
+ * bases[p * (T + 1) + k] = the sum of bases_k over the regions, regions[p * (T + 1) + k] = the regions of class k.  Integer
+ * sums: any split of the regions into runs gives the same totals.
+ *   _perm_begin    allocates and zeroes the totals (a second call starts over; so does _finish of new rows, which drops them).
+ *                  GFFX_E_STATE before _finish, GFFX_E_INVALID for n_perm > 2^20
+ *   _perm_run_host, _perm_run_store   add regions to the totals, asynchronous on the object's stream; first_row = the global
+ *                  row of the first region.  GFFX_E_STATE before _perm_begin.  _run_store reads the slot in place: _perm_wait
+ *                  before the staging buffer is appended again.  A run with a row chr >= n_seq is void (it adds nothing):
+ *   _perm_wait     waits for the runs; GFFX_E_CHR_RANGE once if a run since the last wait was void (the object stays usable)
+ *   _perm_copy_totals   bases, regions: (n_perm + 1) x (T + 1) each, unplaced: one word (any may be NULL); after _perm_wait
+ *   _perm_last_kernel_ms   HIP-event milliseconds of the runs the last _perm_wait waited for
+ *   _perm_group    rows of the totals per block of k_classmap_permute (regions per block: _block_size) */
+int gffx_hip_classmap_perm_begin(gffx_hip_classmap *, const uint32_t *seq_len /* n_seq */, uint32_t n_perm, uint64_t seed);
+int gffx_hip_classmap_perm_run_host(gffx_hip_classmap *, const uint32_t *regions /* 3 per region */, uint64_t nq, uint64_t first_row);
+int gffx_hip_classmap_perm_run_store(gffx_hip_classmap *, const gffx_hip_regions *, int k, uint64_t first, uint64_t n_rows, uint64_t first_row);
+int gffx_hip_classmap_perm_wait(gffx_hip_classmap *);
+int gffx_hip_classmap_perm_copy_totals(gffx_hip_classmap *, uint64_t *bases, uint64_t *regions, uint64_t *unplaced);
+int gffx_hip_classmap_perm_last_kernel_ms(gffx_hip_classmap *, double *ms);
+uint32_t gffx_hip_classmap_perm_group(void);
+
 /* ---- BAM sources of `gffx depth` / `gffx coverage` (commands/depth.rs:297-427, commands/coverage.rs:125-204) --
  * BGZF members are inflated on the device (one wave per member, device/bgzf.hip; the decoder, device/bgzf_core.hpp, is
  * shared with the host).  A bad member fails the call with a message naming its file offset: a header that is not BGZF,
