@@ -115,6 +115,12 @@ SIGNATURES = {
     "gffx_hip_pileup_fold_rows": (C.c_uint64, []),
     "gffx_hip_pileup_scan_tile": (C.c_uint32, []),
     "gffx_hip_pileup_destroy": (None, [vp]),
+    "gffx_hip_pileup_meta_set": (C.c_int, [vp, C.c_uint64, u32p, u32p, u32p, u8p, u32p, vp, C.c_int]),
+    "gffx_hip_pileup_meta_copy": (C.c_int, [vp, u64p, u64p, u64p, u64p]),
+    "gffx_hip_pileup_meta_ms": (C.c_int, [vp, C.POINTER(C.c_double)]),
+    "gffx_hip_pileup_meta_columns": (C.c_uint64, [vp]),
+    "gffx_hip_pileup_meta_max_columns": (C.c_uint32, []),
+    "gffx_hip_pileup_meta_tile": (C.c_uint32, []),
     "gffx_hip_closest_create": (C.c_int, [vp, C.c_uint64, C.POINTER(vp)]),
     "gffx_hip_closest_run_host": (C.c_int, [vp, u32p, C.c_uint64, C.c_uint32]),
     "gffx_hip_closest_run_store": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32]),

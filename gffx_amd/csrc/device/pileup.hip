@@ -13,6 +13,13 @@
 //   k_pileup_segments   one thread per segment (resident since _create, in the order given: neighbours search neighbouring
 //                       keys): four lower bounds inside [off[c], off[c + 1]), acc[i] += B(b) - B(a) as a plain 64-bit store.
 //                       The thread owns its segment and folds are serialised on the stream: no atomics.
+//   k_pileup_meta       (only after _meta_set: `gffx meta`) one wave per feature, kMetaTile features per block: the
+//                       B + 1 column boundaries of meta_core.hpp, 64 at a time, one per lane; B(x) once per boundary, a column
+//                       as the difference of two neighbouring lanes.  The feature's searches are confined first: four searches
+//                       by the whole wave (64 probes a step) find where the window's two ends fall among the starts and the
+//                       ends, and a lane's own two searches run inside that.  Column sums: LDS, then one 64-bit atomic add per
+//                       column and block (integers: any order gives the same bits); the matrix, if kept: plain stores, the
+//                       wave owns its feature's row.
 // Roofline bound: the sorts HBM (8 W bytes per record and pass), the segment kernel latency (dependent gathers, like Join A).
 #include <algorithm>
 #include <cstring>
@@ -20,6 +27,7 @@
 #include <vector>
 
 #include "gffx_device.hpp"
+#include "meta_core.hpp"
 #include "pileup_core.hpp"
 #include "radix_sort.hpp"
 #include "regions_store.hpp"
@@ -31,6 +39,9 @@ constexpr uint32_t kPileupScanTile = 4 * kPileupThreads;  // 4 consecutive recor
 constexpr uint64_t kPileupFold = 4ull << 20;              // rows per fold (the default batch of `gffx coverage`)
 constexpr uint32_t kPileupErrRange = 2u;                  // err word: a row with seqid >= n_seq (the sort's own bit for it)
 constexpr uint32_t kPileupErrInverted = 8u;               // ... with start >= end (4 is the sort's time-out)
+constexpr uint32_t kMetaMaxColumns = 4096;                // k_pileup_meta's column sums in LDS: 32 KB of u64
+constexpr uint32_t kMetaTile = 64;                        // features per block of k_pileup_meta: 16 per wave
+constexpr uint32_t kMetaGeometrySlice = 1024;             // features per block of k_pileup_meta_geometry
 
 // rows [i0, i0 + 4) -> their key records.  wide: `rows` is 16-byte aligned (a region-store slot that starts at a row that is
 // no multiple of four is not)
@@ -188,6 +199,95 @@ __global__ __launch_bounds__(kPileupThreads) void k_pileup_segments(pileup::Keys
     if (add) acc[i] += add;
 }
 
+// the features of `gffx meta`, resident since _meta_set, in the order given
+struct MetaFeatures {
+    const uint32_t *seq, *start, *end;
+    const uint8_t *minus;
+    const uint32_t *seq_len;  // n_seq lengths, or NULL: every seqid is 2^32 - 1 long
+    u64 n;
+};
+
+// The first position p of [lo, hi) with keys[p] >= x (hi if none), found by the whole wave: 64 probes a step cut the range to a
+// 65th, the last step looks at up to 64 neighbours.  lo, hi and x are the same in every lane and all 64 lanes are here.  Every
+// probe lies inside [lo, hi).
+__device__ __forceinline__ u64 meta_wave_lower_bound(const uint32_t *keys, u64 lo, u64 hi, uint32_t x, int lane) {
+    while (hi - lo > 64) {
+        const u64 n = hi - lo;  // (below 2^28: 65 n fits)
+        const u64 below = __ballot(keys[lo + ((u64)(lane + 1) * n) / 65] < x);  // probes ascend with the lane: a prefix of the lanes
+        const int c = __popcll(below);
+        const u64 new_lo = c ? lo + ((u64)c * n) / 65 + 1 : lo;
+        const u64 new_hi = c < 64 ? lo + ((u64)(c + 1) * n) / 65 : hi;
+        lo = new_lo, hi = new_hi;  // (at most n / 65 + 1 wide: the loop ends)
+    }
+    const u64 p = lo + (u64)lane;
+    return lo + (u64)__popcll(__ballot(p < hi && keys[p] < x));
+}
+
+// col_bases[j] += the bases this fold's rows lay on column j of every feature; matrix (or NULL): n x B, the same per feature.
+// B <= kMetaMaxColumns words of dynamic LDS.
+__global__ __launch_bounds__(kPileupThreads) void k_pileup_meta(pileup::Keys K, const u64 *off, uint32_t n_seq, MetaFeatures F, meta::Layout lay, uint32_t B,
+                                                                u64 *col_bases, u64 *matrix) {
+    extern __shared__ u64 s_col[];
+    for (uint32_t j = threadIdx.x; j < B; j += kPileupThreads) s_col[j] = 0ull;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (uint32_t t = wave; t < kMetaTile; t += kPileupThreads / 64) {  // (everything up to the column loop is the same in all lanes)
+        const u64 i = (u64)blockIdx.x * kMetaTile + t;
+        if (i >= F.n) break;
+        const uint32_t c = F.seq[i];
+        if (c >= n_seq) continue;  // (refused at _meta_set)
+        const u64 lo = off[c], hi = off[c + 1];
+        if (lo >= hi) continue;  // no row on the seqid in this fold
+        const uint32_t s = F.start[i], e = F.end[i], len = F.seq_len ? F.seq_len[c] : 0xFFFFFFFFu;
+        const bool minus = F.minus[i] != 0;
+        const uint32_t x_first = meta::boundary(lay, s, e, minus, len, 0), x_last = meta::boundary(lay, s, e, minus, len, B);
+        const uint32_t x_min = minus ? x_last : x_first, x_max = minus ? x_first : x_last;
+        // every boundary x has x_min <= x <= x_max: its searches end inside [s_lo, s_hi] and [e_lo, e_hi]
+        const u64 s_lo = meta_wave_lower_bound(K.starts, lo, hi, x_min, lane);
+        const u64 s_hi = meta_wave_lower_bound(K.starts, s_lo, hi, x_max, lane);
+        if (s_hi == lo) continue;  // no row starts below the window's end: B(x) = 0 all over it
+        const u64 e_lo = meta_wave_lower_bound(K.ends, lo, hi, x_min, lane);
+        if (e_lo == hi) continue;  // every row ends below the window: B(x) is the same all over it
+        const u64 e_hi = meta_wave_lower_bound(K.ends, e_lo, hi, x_max, lane);
+        const u64 base_s = K.pre_s[lo], base_e = K.pre_e[lo];
+        for (uint32_t k0 = 0; k0 < B; k0 += 63) {  // boundaries k0 .. k0 + 63, columns k0 .. k0 + 62
+            const uint32_t k = min(k0 + (uint32_t)lane, B);
+            const uint32_t x = meta::boundary(lay, s, e, minus, len, k);
+            const u64 ps = pileup::lower_bound(K.starts, s_lo, s_hi, x), pe = pileup::lower_bound(K.ends, e_lo, e_hi, x);
+            const u64 below = pileup::bases_below(x, ps - lo, K.pre_s[ps] - base_s, pe - lo, K.pre_e[pe] - base_e);
+            const u64 next = __shfl_down(below, 1, 64);
+            if (lane < 63 && k0 + (uint32_t)lane < B) {
+                const u64 add = minus ? below - next : next - below;
+                if (add) {
+                    atomicAdd(&s_col[k], add);
+                    if (matrix) matrix[i * B + k] += add;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < B; j += kPileupThreads)
+        if (s_col[j]) atomicAdd(&col_bases[j], s_col[j]);
+}
+
+// what does not depend on the rows, once at _meta_set: col_len[j] = the clamped lengths of column j over the features,
+// col_features[j] = the features whose column j is not empty.  blockIdx.x: a slice of kMetaGeometrySlice features, blockIdx.y: 256 columns
+__global__ __launch_bounds__(kPileupThreads) void k_pileup_meta_geometry(uint32_t n_seq, MetaFeatures F, meta::Layout lay, uint32_t B, u64 *col_len,
+                                                                         u64 *col_features) {
+    const uint32_t j = blockIdx.y * kPileupThreads + threadIdx.x;
+    if (j >= B) return;
+    const u64 i0 = (u64)blockIdx.x * kMetaGeometrySlice, i1 = i0 + kMetaGeometrySlice < F.n ? i0 + kMetaGeometrySlice : F.n;
+    u64 total = 0, features = 0;
+    for (u64 i = i0; i < i1; ++i) {
+        const uint32_t c = F.seq[i];
+        if (c >= n_seq) continue;
+        uint32_t a, b;
+        meta::column(lay, F.start[i], F.end[i], F.minus[i] != 0, F.seq_len ? F.seq_len[c] : 0xFFFFFFFFu, j, &a, &b);
+        total += b - a, features += b > a;
+    }
+    if (total) atomicAdd(&col_len[j], total), atomicAdd(&col_features[j], features);
+}
+
 }  // namespace gffx
 
 using namespace gffx;
@@ -200,8 +300,8 @@ struct gffx_hip_pileup {
     std::string message;
     hipStream_t stream = nullptr;
     // two folds in flight, each: 0 start, 1 keys done, 2 sorts start (the host looked at the error word in between), 3 sorts done,
-    // 4 scan done, 5 segments done, 6 the error word is on the host
-    hipEvent_t ev[2][7] = {};
+    // 4 scan done, 5 segments done, 6 the error word is on the host, 7 the meta kernel done (recorded between 5 and 6)
+    hipEvent_t ev[2][8] = {};
     hipEvent_t read = nullptr;  // the fold's rows have been read
     bool pending[2] = {false, false};  // ev[j] and h_ctl[j] wait to be looked at
     int next_set = 0;
@@ -222,6 +322,16 @@ struct gffx_hip_pileup {
     SortPlan plan{};
     double stage_ms[4] = {0, 0, 0, 0};  // keys, the two sorts, scan (+ offsets), segments
     uint64_t rows_added = 0, folds = 0;
+    // the second consumer (`gffx meta`): nothing of it exists before _meta_set
+    bool meta = false, meta_matrix = false;
+    uint64_t n_feat = 0;
+    uint32_t meta_cols = 0;
+    meta::Layout meta_layout{};
+    uint32_t *d_feat[3] = {nullptr, nullptr, nullptr}, *d_seq_len = nullptr;
+    uint8_t *d_feat_minus = nullptr;
+    u64 *d_col = nullptr;  // 3 x meta_cols: bases, length, features
+    u64 *d_matrix = nullptr;
+    double meta_ms = 0;
 };
 
 namespace {
@@ -263,6 +373,10 @@ int pileup_collect(gffx_hip_pileup *P, int j) {
     for (int s = 0; s < 4; ++s) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, P->ev[j][from[s]], P->ev[j][s == 0 ? 1 : from[s] + 1]) == hipSuccess) P->stage_ms[s] += ms;
+    }
+    if (P->meta) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, P->ev[j][5], P->ev[j][7]) == hipSuccess) P->meta_ms += ms;
     }
     if (P->h_ctl[8 * j] & 4u) return fail(GFFX_E_HIP, "gffx_hip_pileup: the device sort timed out waiting for an earlier tile");
     return GFFX_OK;
@@ -334,6 +448,16 @@ int pileup_fold(gffx_hip_pileup *P, const uint32_t *rows, uint64_t m) {
         GFFX_HIP_TRY(hipGetLastError());
     }
     GFFX_HIP_TRY(hipEventRecord(P->ev[j][5], P->stream));
+    if (P->meta) {
+        if (P->n_feat) {
+            const pileup::Keys K{P->co[0], P->co[1], P->pre[0], P->pre[1]};
+            const MetaFeatures F{P->d_feat[0], P->d_feat[1], P->d_feat[2], P->d_feat_minus, P->d_seq_len, (u64)P->n_feat};
+            hipLaunchKernelGGL(k_pileup_meta, dim3((uint32_t)((P->n_feat + kMetaTile - 1) / kMetaTile)), dim3(kPileupThreads), P->meta_cols * sizeof(u64),
+                               P->stream, K, P->off, P->n_seq, F, P->meta_layout, P->meta_cols, P->d_col, P->meta_matrix ? P->d_matrix : nullptr);
+            GFFX_HIP_TRY(hipGetLastError());
+        }
+        GFFX_HIP_TRY(hipEventRecord(P->ev[j][7], P->stream));
+    }
     GFFX_HIP_TRY(hipMemcpyAsync(P->h_ctl + 8 * j, P->ctl, 32, hipMemcpyDeviceToHost, P->stream));
     GFFX_HIP_TRY(hipEventRecord(P->ev[j][6], P->stream));
     P->pending[j] = true;
@@ -341,6 +465,18 @@ int pileup_fold(gffx_hip_pileup *P, const uint32_t *rows, uint64_t m) {
     P->rows_added += m;
     P->folds++;
     return GFFX_OK;
+}
+
+// the meta consumer's device memory (the stream is idle)
+void pileup_meta_free(gffx_hip_pileup *P) {
+    for (void *p : {(void *)P->d_feat[0], (void *)P->d_feat[1], (void *)P->d_feat[2], (void *)P->d_seq_len, (void *)P->d_feat_minus, (void *)P->d_col,
+                    (void *)P->d_matrix})
+        if (p) (void)hipFree(p);
+    P->d_feat[0] = P->d_feat[1] = P->d_feat[2] = P->d_seq_len = nullptr;
+    P->d_feat_minus = nullptr;
+    P->d_col = P->d_matrix = nullptr;
+    P->meta = P->meta_matrix = false;
+    P->n_feat = 0, P->meta_cols = 0;
 }
 
 // every fold enqueued so far is through and looked at
@@ -357,6 +493,13 @@ int pileup_drain(gffx_hip_pileup *P) {
 
 extern "C" uint64_t gffx_hip_pileup_fold_rows(void) { return kPileupFold; }
 extern "C" uint32_t gffx_hip_pileup_scan_tile(void) { return kPileupScanTile; }
+extern "C" uint32_t gffx_hip_pileup_meta_max_columns(void) { return kMetaMaxColumns; }
+extern "C" uint32_t gffx_hip_pileup_meta_tile(void) { return kMetaTile; }
+
+extern "C" uint64_t gffx_hip_pileup_meta_columns(const gffx_hip_meta_layout *layout) {
+    if (!layout) return 0;
+    return meta::columns(meta::Layout{layout->mode, layout->anchor, layout->up, layout->down, layout->bin, layout->body_bins});
+}
 
 extern "C" void gffx_hip_pileup_destroy(gffx_hip_pileup *P) {
     if (!P) return;
@@ -366,6 +509,7 @@ extern "C" void gffx_hip_pileup_destroy(gffx_hip_pileup *P) {
                     (void *)P->ke[0], (void *)P->ke[1], (void *)P->co[0], (void *)P->co[1], (void *)P->pre[0], (void *)P->pre[1], (void *)P->tile_sum,
                     (void *)P->off, (void *)P->work, (void *)P->ctl})
         if (p) (void)hipFree(p);
+    pileup_meta_free(P);
     if (P->h_stage) (void)hipHostFree(P->h_stage);
     if (P->h_ctl) (void)hipHostFree(P->h_ctl);
     for (auto &set : P->ev)
@@ -482,6 +626,79 @@ extern "C" int gffx_hip_pileup_reset(gffx_hip_pileup *P) {
     int rc = pileup_enter(P, "gffx_hip_pileup_reset");
     if (rc) return rc;
     GFFX_PILEUP_HIP(hipMemsetAsync(P->d_acc, 0, std::max<uint64_t>(P->n_seg, 4) * 8, P->stream));  // (behind the folds enqueued so far)
+    if (P->meta) {  // the column totals and the matrix; length and features are the features' own and stay
+        GFFX_PILEUP_HIP(hipMemsetAsync(P->d_col, 0, (size_t)P->meta_cols * 8, P->stream));
+        if (P->meta_matrix) GFFX_PILEUP_HIP(hipMemsetAsync(P->d_matrix, 0, std::max<uint64_t>(P->n_feat * P->meta_cols, 4) * 8, P->stream));
+    }
+    return GFFX_OK;
+}
+
+extern "C" int gffx_hip_pileup_meta_set(gffx_hip_pileup *P, uint64_t n_feat, const uint32_t *feat_seq, const uint32_t *feat_start, const uint32_t *feat_end,
+                                        const uint8_t *feat_minus, const uint32_t *seq_len, const gffx_hip_meta_layout *layout, int keep_matrix) {
+    int rc = pileup_enter(P, "gffx_hip_pileup_meta_set");
+    if (rc) return rc;
+    if (!layout) return fail(GFFX_E_INVALID, "gffx_hip_pileup_meta_set: layout is NULL");
+    if (n_feat && (!feat_seq || !feat_start || !feat_end || !feat_minus)) return fail(GFFX_E_INVALID, "gffx_hip_pileup_meta_set: NULL feature array");
+    if (n_feat >= (1ull << 32)) return fail(GFFX_E_INVALID, "gffx_hip_pileup_meta_set: %llu features exceed the limit of 2^32 - 1", (unsigned long long)n_feat);
+    const meta::Layout lay{layout->mode, layout->anchor, layout->up, layout->down, layout->bin, layout->body_bins};
+    const uint64_t B = meta::columns(lay);
+    if (!B)
+        return fail(GFFX_E_INVALID, "gffx_hip_pileup_meta_set: no such layout (mode %u, anchor %u, up %u, down %u, bin %u, body bins %u)", lay.mode, lay.anchor, lay.up,
+                    lay.down, lay.bin, lay.body_bins);
+    if (B > kMetaMaxColumns) return fail(GFFX_E_INVALID, "gffx_hip_pileup_meta_set: %llu columns exceed the limit of %u", (unsigned long long)B, kMetaMaxColumns);
+    for (uint64_t i = 0; i < n_feat; i++) {
+        if (feat_seq[i] >= P->n_seq)
+            return fail(GFFX_E_INVALID, "gffx_hip_pileup_meta_set: feature %llu has chr %u >= %u", (unsigned long long)i, feat_seq[i], P->n_seq);
+        if (feat_start[i] >= feat_end[i]) return fail(GFFX_E_INVALID, "gffx_hip_pileup_meta_set: feature %llu has start >= end", (unsigned long long)i);
+    }
+    GFFX_PILEUP_TRY(pileup_drain(P));  // (folds in flight read the features that are replaced here)
+    pileup_meta_free(P);
+    for (uint32_t *&p : P->d_feat) GFFX_PILEUP_TRY(pileup_alloc(&p, n_feat));
+    GFFX_PILEUP_TRY(pileup_alloc(&P->d_feat_minus, n_feat));
+    GFFX_PILEUP_TRY(pileup_alloc(&P->d_col, 3 * B));
+    if (seq_len) GFFX_PILEUP_TRY(pileup_alloc(&P->d_seq_len, (uint64_t)P->n_seq));
+    if (keep_matrix) GFFX_PILEUP_TRY(pileup_alloc(&P->d_matrix, n_feat * B));
+    if (n_feat) {
+        GFFX_PILEUP_HIP(hipMemcpyAsync(P->d_feat[0], feat_seq, n_feat * 4, hipMemcpyHostToDevice, P->stream));
+        GFFX_PILEUP_HIP(hipMemcpyAsync(P->d_feat[1], feat_start, n_feat * 4, hipMemcpyHostToDevice, P->stream));
+        GFFX_PILEUP_HIP(hipMemcpyAsync(P->d_feat[2], feat_end, n_feat * 4, hipMemcpyHostToDevice, P->stream));
+        GFFX_PILEUP_HIP(hipMemcpyAsync(P->d_feat_minus, feat_minus, n_feat, hipMemcpyHostToDevice, P->stream));
+    }
+    if (seq_len && P->n_seq) GFFX_PILEUP_HIP(hipMemcpyAsync(P->d_seq_len, seq_len, (size_t)P->n_seq * 4, hipMemcpyHostToDevice, P->stream));
+    GFFX_PILEUP_HIP(hipMemsetAsync(P->d_col, 0, std::max<uint64_t>(3 * B, 4) * 8, P->stream));
+    if (keep_matrix) GFFX_PILEUP_HIP(hipMemsetAsync(P->d_matrix, 0, std::max<uint64_t>(n_feat * B, 4) * 8, P->stream));
+    if (n_feat) {
+        const MetaFeatures F{P->d_feat[0], P->d_feat[1], P->d_feat[2], P->d_feat_minus, P->d_seq_len, (u64)n_feat};
+        hipLaunchKernelGGL(k_pileup_meta_geometry, dim3((uint32_t)((n_feat + kMetaGeometrySlice - 1) / kMetaGeometrySlice), (uint32_t)((B + kPileupThreads - 1) / kPileupThreads)),
+                           dim3(kPileupThreads), 0, P->stream, P->n_seq, F, lay, (uint32_t)B, P->d_col + B, P->d_col + 2 * B);
+        GFFX_PILEUP_HIP(hipGetLastError());
+    }
+    GFFX_PILEUP_HIP(hipStreamSynchronize(P->stream));  // (the caller's arrays are free again)
+    P->meta = true, P->meta_matrix = keep_matrix != 0;
+    P->n_feat = n_feat, P->meta_cols = (uint32_t)B, P->meta_layout = lay;
+    return GFFX_OK;
+}
+
+extern "C" int gffx_hip_pileup_meta_copy(gffx_hip_pileup *P, uint64_t *col_bases, uint64_t *col_len, uint64_t *col_features, uint64_t *matrix) {
+    int rc = pileup_enter(P, "gffx_hip_pileup_meta_copy");
+    if (rc) return rc;
+    if (!P->meta) return fail(GFFX_E_INVALID, "gffx_hip_pileup_meta_copy: the pileup has no features (gffx_hip_pileup_meta_set)");
+    if (matrix && !P->meta_matrix) return fail(GFFX_E_INVALID, "gffx_hip_pileup_meta_copy: the matrix was not kept");
+    GFFX_PILEUP_TRY(pileup_drain(P));
+    const size_t B = P->meta_cols;
+    if (col_bases) GFFX_PILEUP_HIP(hipMemcpy(col_bases, P->d_col, B * 8, hipMemcpyDeviceToHost));
+    if (col_len) GFFX_PILEUP_HIP(hipMemcpy(col_len, P->d_col + B, B * 8, hipMemcpyDeviceToHost));
+    if (col_features) GFFX_PILEUP_HIP(hipMemcpy(col_features, P->d_col + 2 * B, B * 8, hipMemcpyDeviceToHost));
+    if (matrix && P->n_feat) GFFX_PILEUP_HIP(hipMemcpy(matrix, P->d_matrix, P->n_feat * B * 8, hipMemcpyDeviceToHost));
+    return GFFX_OK;
+}
+
+// (const in the interface: like _stage_ms it waits for the folds in flight)
+extern "C" int gffx_hip_pileup_meta_ms(const gffx_hip_pileup *Pc, double *ms) {
+    if (!Pc) return fail(GFFX_E_INVALID, "gffx_hip_pileup_meta_ms: pileup is NULL");
+    const int rc = gffx_hip_pileup_stage_ms(Pc, nullptr, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    if (ms) *ms = Pc->meta_ms;
     return GFFX_OK;
 }
 

@@ -16,6 +16,7 @@
 //   gffx::commands::closest::{ClosestArgs, run}                                  (no reference item; closest.cpp)
 //   gffx::commands::annotate::{AnnotateArgs, run}                                (no reference item; annotate.cpp)
 //   gffx::commands::enrich::{EnrichArgs, run}                                    (no reference item; enrich.cpp)
+//   gffx::commands::meta::{MetaArgs, run}                                        (no reference item; meta.cpp)
 // Compute (Join A, Join B) goes through include/gffx_hip.h only; there is no CPU join here.
 #pragma once
 #include <algorithm>
@@ -524,6 +525,27 @@ struct EnrichArgs {
 void run(const EnrichArgs &args);
 
 }  // namespace enrich
+
+namespace meta {
+
+struct MetaArgs {
+    CommonArgs common;                   // -i, -o, -t, -v
+    std::string source;                  // -s/--source (what `coverage -s` accepts)
+    std::vector<std::string> types{"gene"};  // -T/--types: the features are the lines of these types
+    gffx_hip_meta_layout layout{0, 0, 2000, 2000, 10, 0};  // --anchor | --scale, -u, -d, -w (checked by the command line)
+    std::optional<std::string> genome;   // -g/--genome: the seqids' lengths (as for enrich); without it columns are cut at 0 only
+    std::optional<std::string> matrix;   // --matrix: one line per feature with its bases per column
+    int device = 0;                      // --device
+    int gpus = 1;                        // --gpus (the rows in batches over N devices, totals added)
+};
+
+// The stranded depth profile around the features (device/meta_core.hpp has the definition): a header line, then per column
+// `column part from to features bases length mean_depth`.  GFFX_META_BATCH_ROWS sets the rows per device batch (default 4 Mi
+// rows; a positive decimal number, capped at 1 << 28, anything else is ignored), as GFFX_COVERAGE_BATCH_ROWS does for
+// `coverage`.  Results never depend on it, on --gpus or on -t.
+void run(const MetaArgs &args);
+
+}  // namespace meta
 }  // namespace commands
 
 // ---- BAM sources of depth / coverage (bam.cpp; commands/depth.rs:297-372, coverage.rs:125-168) ------------------------

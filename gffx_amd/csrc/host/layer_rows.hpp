@@ -14,12 +14,13 @@ namespace gffx::commands::layer_rows {
 // The layers' rows (layer, seqid number, start - 1, end) from the all-line table's columns.  A line counts when its type is
 // one of the names, its split succeeded and 1 <= start <= end; a line on a seqid the index does not know is skipped.
 // seq_end (unless NULL, sized by the caller to the index's seqids): the largest end of ANY such valid line per seqid, whatever
-// its type.
+// its type.  line_start (unless NULL; ls: where every line begins in the text): per row where its line begins (`gffx meta`
+// reads the strand and the ID there: feature_rows.hpp).
 template <typename Names>
 void collect_rows(uint64_t n_lines, const uint32_t *start, const uint32_t *end, const uint32_t *seq, const uint32_t *type, const uint8_t *flags,
                   const Names &seq_names, const Names &type_names, const std::vector<std::string> &layers,
                   const std::unordered_map<std::string, uint32_t> &seqid_to_num, std::vector<uint32_t> &rows, std::vector<uint64_t> &per_layer, uint64_t &skipped,
-                  std::vector<uint32_t> *seq_end) {
+                  std::vector<uint32_t> *seq_end, const uint64_t *ls = nullptr, std::vector<uint64_t> *line_start = nullptr) {
     std::vector<uint32_t> layer_of(type_names.size(), UINT32_MAX), seq_of(seq_names.size(), UINT32_MAX);
     for (size_t i = 0; i < type_names.size(); ++i)
         for (size_t k = 0; k < layers.size(); ++k)
@@ -41,12 +42,14 @@ void collect_rows(uint64_t n_lines, const uint32_t *start, const uint32_t *end, 
         const uint32_t k = layer_of[type[i]];
         rows.insert(rows.end(), {k, seq_of[seq[i]], start[i] - 1, end[i]});
         per_layer[k]++;
+        if (line_start) line_start->push_back(ls[i]);
     }
 }
 
 // ... from the file: its line table when it is usable, else its text
 inline void collect(const std::string &gff_path, const std::vector<std::string> &layers, const std::unordered_map<std::string, uint32_t> &seqid_to_num, size_t threads,
-                    bool verbose, std::vector<uint32_t> &rows, std::vector<uint64_t> &per_layer, uint64_t &skipped, std::vector<uint32_t> *seq_end) {
+                    bool verbose, std::vector<uint32_t> &rows, std::vector<uint64_t> &per_layer, uint64_t &skipped, std::vector<uint32_t> *seq_end,
+                    std::vector<uint64_t> *line_start = nullptr) {
     const MappedFile gff = map_file_or(gff_path, "Cannot open GFF file: \"" + gff_path + "\"");
     const char *lt = std::getenv("GFFX_LINE_TABLE");
     std::string why = "disabled";
@@ -58,11 +61,11 @@ inline void collect(const std::string &gff_path, const std::vector<std::string> 
     }
     if (use_all) {
         collect_rows(all.n_lines, all.start, all.end, all.seq, all.type, all.flags, all.seq_names, all.type_names, layers, seqid_to_num, rows, per_layer, skipped,
-                     seq_end);
+                     seq_end, all.ls, line_start);
     } else {
         const intersect::AllLines A = intersect::build_all_lines(gff.view(), threads);
         collect_rows(A.ls.size(), A.start.data(), A.end.data(), A.seq.data(), A.type.data(), A.flags.data(), A.seq_names, A.type_names, layers, seqid_to_num, rows,
-                     per_layer, skipped, seq_end);
+                     per_layer, skipped, seq_end, A.ls.data(), line_start);
     }
     if (verbose && use_all) std::fprintf(stderr, "[INFO] all-line table from %s.lall (%llu lines)\n", gff_path.c_str(), (unsigned long long)all.n_lines);
     if (verbose && !use_all) std::fprintf(stderr, "[INFO] all-line table not used (%s): parsing the text\n", why.c_str());

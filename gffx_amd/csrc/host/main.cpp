@@ -1,5 +1,5 @@
 // main.cpp -- `gffx` command line for the intersect path: `gffx index` (prerequisite),
-// `gffx intersect`, `gffx extract`, `gffx search`, `gffx depth` (BED source), `gffx closest`, `gffx annotate` and `gffx enrich` (additions) (reference: main.rs:11-39, commands/depth.rs:34-72, commands/extract.rs:16-35, commands/search.rs:18-51, commands/index.rs:11-23, commands/intersect.rs:32-70,
+// `gffx intersect`, `gffx extract`, `gffx search`, `gffx depth` (BED source), `gffx closest`, `gffx annotate`, `gffx enrich` and `gffx meta` (additions) (reference: main.rs:11-39, commands/depth.rs:34-72, commands/extract.rs:16-35, commands/search.rs:18-51, commands/index.rs:11-23, commands/intersect.rs:32-70,
 // utils/common.rs:17-52).  Flag names, short flags, defaults and groups follow the reference's
 // clap derive; usage errors exit 2 like clap, run-time errors print `Error: <msg>` and exit 1.
 #include <unistd.h>
@@ -98,6 +98,7 @@ const char *kTopUsage =
     "  closest    Report the nearest root features of a region or of the regions of a BED file (MI355X engine)\n"
     "  annotate   Count the bases of a region or of the regions of a BED file by feature class (MI355X engine)\n"
     "  enrich     Test the regions of a BED file against feature classes by permutation (MI355X engine)\n"
+    "  meta       Sum the depth of a BED, BAM or SAM file around features, along their strand (MI355X engine)\n"
     "  help       Print this message\n";
 
 const char *kIntersectUsage =
@@ -229,6 +230,31 @@ const char *kEnrichUsage =
     "  class, quantity, observed, mean, sd, z, fold (observed / mean), n_ge and n_le (permutations with a value >= / <= the\n"
     "  observed one), p_ge = (n_ge + 1) / (N + 1) and p_le.  A region wider than its seqid stays where it is (a warning says\n"
     "  how many).  Regions may overlap each other after placement.\n";
+
+const char *kMetaUsage =
+    "Usage: gffx meta [OPTIONS] --input <FILE> --source <SOURCE>\n\nOptions:\n"
+    "  -i, --input <FILE>       Input GFF file path\n"
+    "  -s, --source <SOURCE>    Input source (BED, plain or bgzipped, BAM or SAM), as for coverage\n"
+    "  -o, --output <FILE>      Output file (stdout if not provided)\n"
+    "  -T, --types <T1,T2,...>  Feature types (column 3) whose lines are the features [default: gene]\n"
+    "      --anchor <ANCHOR>    Point mode: columns around the feature's tss (its 5' end), tes (its 3' end) or center\n"
+    "                           [default: tss]\n"
+    "      --scale <M>          Scaled mode instead: every feature's body becomes M columns, whatever its length\n"
+    "  -u, --upstream <UP>      Bases before the anchor or the body, a multiple of BIN [default: 2000]\n"
+    "  -d, --downstream <DOWN>  Bases behind the anchor or the body, a multiple of BIN [default: 2000]\n"
+    "  -w, --bin <BIN>          Bases per column outside the body [default: 10]\n"
+    "  -g, --genome <FILE>      Lengths of the seqids, 'name<TAB>length' per line (a .fai works), as for enrich: columns are\n"
+    "                           cut at a seqid's end.  Without it they are cut at 0 only\n"
+    "      --matrix <FILE>      Write one line per feature: chr, start, end, id, strand and its bases per column\n"
+    "  -t, --threads <NUM>      Number of threads for parallel processing [default: 12]\n"
+    "  -v, --verbose            Enable verbose output\n"
+    "      --device <N>         HIP device to run on [default: 0]\n"
+    "      --gpus <N>           Spread the source rows over N devices [default: 1]\n"
+    "      --stats-json <FILE>  Write the run's stage timers and counts as one JSON object\n\n"
+    "Output: a header line, then one line per column, in the direction of transcription (a feature on '-' is mirrored):\n"
+    "  column, part (point, up, body, down), from and to (offsets from the anchor, the 5' end or the 3' end; body columns\n"
+    "  count from 0 to M), features with bases in the column, bases (summed depth), length, mean_depth = bases / length.\n"
+    "  A strand other than '+' or '-' counts as '+' (a warning says how many).\n";
 
 const char *kIndexUsage =
     "Usage: gffx index [OPTIONS] --input <INPUT>\n\nOptions:\n"
@@ -550,6 +576,64 @@ int run_enrich_cli(int argc, char **argv) {
     return 0;
 }
 
+int run_meta_cli(int argc, char **argv) {
+    static const std::vector<OptSpec> specs = {{'i', "input", true},    {'s', "source", true},     {'o', "output", true},  {'T', "types", true},
+                                               {0, "anchor", true},     {0, "scale", true},        {'u', "upstream", true}, {'d', "downstream", true},
+                                               {'w', "bin", true},      {'g', "genome", true},     {0, "matrix", true},    {'t', "threads", true},
+                                               {'v', "verbose", false}, {0, "device", true},       {0, "gpus", true},      {0, "stats-json", true},
+                                               {'h', "help", false}};
+    const auto o = parse_opts(argc, argv, 2, specs);
+    if (o.count("help")) {
+        std::fputs(kMetaUsage, stdout);
+        return 0;
+    }
+    commands::meta::MetaArgs a;
+    if (!o.count("input") || !o.count("source"))
+        throw UsageError(std::string("the following required arguments were not provided:") + (o.count("input") ? "" : "\n  --input <FILE>") +
+                         (o.count("source") ? "" : "\n  --source <SOURCE>"));
+    a.common.input = o.at("input")[0];
+    a.source = o.at("source")[0];
+    if (o.count("output")) a.common.output = o.at("output")[0];
+    if (o.count("threads")) a.common.threads = parse_size(o.at("threads")[0], "--threads <NUM>");
+    a.common.verbose = o.count("verbose") > 0;
+    if (o.count("types")) a.types = parse_layers(o.at("types")[0]);
+    if (o.count("anchor") && o.count("scale")) throw UsageError("the argument '--anchor <ANCHOR>' cannot be used with '--scale <M>'");
+    gffx_hip_meta_layout &y = a.layout;
+    if (o.count("anchor")) {
+        const std::string &v = o.at("anchor")[0];
+        if (v == "tss")
+            y.anchor = 0;
+        else if (v == "tes")
+            y.anchor = 1;
+        else if (v == "center")
+            y.anchor = 2;
+        else
+            throw UsageError("invalid value '" + v + "' for '--anchor <ANCHOR>'\n  [possible values: tss, tes, center]");
+    }
+    if (o.count("upstream")) y.up = static_cast<uint32_t>(parse_size(o.at("upstream")[0], "--upstream <UP>"));
+    if (o.count("downstream")) y.down = static_cast<uint32_t>(parse_size(o.at("downstream")[0], "--downstream <DOWN>"));
+    if (o.count("bin")) y.bin = static_cast<uint32_t>(parse_size(o.at("bin")[0], "--bin <BIN>"));
+    if (o.count("scale")) {
+        y.mode = 1;
+        y.body_bins = static_cast<uint32_t>(parse_size(o.at("scale")[0], "--scale <M>"));
+        if (y.body_bins == 0) throw UsageError("invalid value '0' for '--scale <M>': at least one body column is needed");
+    }
+    if (y.bin == 0) throw UsageError("invalid value '0' for '--bin <BIN>': a column has at least one base");
+    if (y.up % y.bin) throw UsageError("invalid value '" + std::to_string(y.up) + "' for '--upstream <UP>': not a multiple of --bin " + std::to_string(y.bin));
+    if (y.down % y.bin) throw UsageError("invalid value '" + std::to_string(y.down) + "' for '--downstream <DOWN>': not a multiple of --bin " + std::to_string(y.bin));
+    if (y.mode == 0 && static_cast<uint64_t>(y.up) + y.down == 0) throw UsageError("--upstream and --downstream are both 0: there is no column");
+    if (gffx_hip_pileup_meta_columns(&y) > gffx_hip_pileup_meta_max_columns())
+        throw UsageError(std::to_string(gffx_hip_pileup_meta_columns(&y)) + " columns exceed the limit of " + std::to_string(gffx_hip_pileup_meta_max_columns()) +
+                         ": choose a larger --bin or a smaller --scale");
+    if (o.count("genome")) a.genome = o.at("genome")[0];
+    if (o.count("matrix")) a.matrix = o.at("matrix")[0];
+    if (o.count("device")) a.device = static_cast<int>(parse_size(o.at("device")[0], "--device <N>"));
+    if (o.count("gpus")) a.gpus = static_cast<int>(std::max<size_t>(1, std::min<size_t>(64, parse_size(o.at("gpus")[0], "--gpus <N>"))));
+    if (o.count("stats-json")) g_run_stats.path = o.at("stats-json")[0];
+    commands::meta::run(a);
+    return 0;
+}
+
 int run_index_cli(int argc, char **argv) {
     static const std::vector<OptSpec> specs = {{'i', "input", true},
                                                {'a', "attribute", true},
@@ -657,7 +741,11 @@ int cli_main(int argc, char **argv) {
             usage = kEnrichUsage;
             return run_enrich_cli(argc, argv);
         }
-        throw UsageError("unrecognized subcommand '" + cmd + "' (this build carries the intersect, extract, search, depth, coverage, closest, annotate and enrich paths only)");
+        if (cmd == "meta") {
+            usage = kMetaUsage;
+            return run_meta_cli(argc, argv);
+        }
+        throw UsageError("unrecognized subcommand '" + cmd + "' (this build carries the intersect, extract, search, depth, coverage, closest, annotate, enrich and meta paths only)");
     } catch (const UsageError &e) {
         std::fprintf(stderr, "error: %s\n\n%s\nFor more information, try '--help'.\n", e.what(), usage);
         return 2;

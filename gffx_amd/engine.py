@@ -630,6 +630,7 @@ class Pileup:
         if not (len(q) == len(s) == len(e)):
             raise ValueError("seg_seq, seg_start and seg_end must have the same length")
         self.n_seg = len(q)
+        self.n_feat, self.meta_columns, self.meta_matrix = 0, 0, False  # (set by meta_set)
         self._h = C.c_void_p()
         check(lib().gffx_hip_pileup_create(int(device), self.n_seq, self.n_seg, _p(q), _p(s), _p(e), C.byref(self._h)))
 
@@ -669,6 +670,65 @@ class Pileup:
         check(lib().gffx_hip_pileup_stage_ms(self._h, *[C.byref(x) for x in st]))
         return {"kernel_ms": ms.value, "rows": rows.value, "folds": folds.value, "keys_ms": st[0].value, "sorts_ms": st[1].value,
                 "scan_ms": st[2].value, "segments_ms": st[3].value}
+
+    # ---- the second consumer: the stranded depth profile around features (`gffx meta`, gffx_hip_pileup_meta_*) ----
+
+    def meta_set(self, feat_seq, feat_start, feat_end, feat_minus, layout: "MetaLayout", seq_len=None, keep_matrix: bool = False) -> int:
+        """The features and the layout (they replace earlier ones and zero the meta totals); returns the number of columns."""
+        q, s, e = _u32(feat_seq).ravel(), _u32(feat_start).ravel(), _u32(feat_end).ravel()
+        m = np.ascontiguousarray(feat_minus, dtype=np.uint8).ravel()
+        if not (len(q) == len(s) == len(e) == len(m)):
+            raise ValueError("feat_seq, feat_start, feat_end and feat_minus must have the same length")
+        ln = None
+        if seq_len is not None:
+            ln = _u32(seq_len).ravel()
+            if len(ln) != self.n_seq:
+                raise ValueError("seq_len must have one length per seqid")
+        check(lib().gffx_hip_pileup_meta_set(self._h, len(q), _p(q), _p(s), _p(e), m.ctypes.data_as(_ffi.u8p), _p(ln) if ln is not None else None,
+                                             C.byref(layout), int(bool(keep_matrix))))
+        self.n_feat, self.meta_columns, self.meta_matrix = len(q), layout.columns, bool(keep_matrix)
+        return self.meta_columns
+
+    def meta(self, matrix: bool = False):
+        """(col_bases, col_len, col_features), each u64[B]; with ``matrix`` also the n_feat x B matrix (waits for the folds)."""
+        B = self.meta_columns
+        cols = [np.zeros(max(B, 1), dtype=np.uint64) for _ in range(3)]
+        mat = np.zeros(max(self.n_feat * B, 1), dtype=np.uint64) if matrix else None
+        check(lib().gffx_hip_pileup_meta_copy(self._h, *[c.ctypes.data_as(u64p) for c in cols], mat.ctypes.data_as(u64p) if matrix else None))
+        out = tuple(c[:B] for c in cols)
+        return out + (mat[: self.n_feat * B].reshape(self.n_feat, B),) if matrix else out
+
+    def meta_ms(self) -> float:
+        ms = C.c_double(0)
+        check(lib().gffx_hip_pileup_meta_ms(self._h, C.byref(ms)))
+        return ms.value
+
+
+META_POINT, META_SCALED = 0, 1
+META_TSS, META_TES, META_CENTER = 0, 1, 2
+
+
+class MetaLayout(C.Structure):
+    """gffx_hip_meta_layout: point mode around an anchor, or scaled mode with ``body_bins`` columns over the feature."""
+    _fields_ = [("mode", C.c_uint32), ("anchor", C.c_uint32), ("up", C.c_uint32), ("down", C.c_uint32), ("bin", C.c_uint32), ("body_bins", C.c_uint32)]
+
+    @classmethod
+    def point(cls, up: int, down: int, bin: int, anchor: int = META_TSS) -> "MetaLayout":
+        return cls(META_POINT, anchor, up, down, bin, 0)
+
+    @classmethod
+    def scaled(cls, up: int, down: int, bin: int, body_bins: int) -> "MetaLayout":
+        return cls(META_SCALED, 0, up, down, bin, body_bins)
+
+    @property
+    def columns(self) -> int:
+        """B, 0 for a layout that is none (it may exceed meta_max_columns())."""
+        return int(lib().gffx_hip_pileup_meta_columns(C.byref(self)))
+
+
+def meta_constants() -> Tuple[int, int]:
+    """(the column limit, the features per block of k_pileup_meta) of the library as it was built."""
+    return int(lib().gffx_hip_pileup_meta_max_columns()), int(lib().gffx_hip_pileup_meta_tile())
 
 
 CLOSEST_IGNORE_OVERLAPS, CLOSEST_LEFT_ONLY, CLOSEST_RIGHT_ONLY = 1, 2, 4  # enum gffx_closest_flags

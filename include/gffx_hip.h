@@ -20,6 +20,7 @@
  *   merge_intervals + the two-pointer walk              gffx_hip_segments_covered, gffx_hip_union_* (`gffx coverage`)
  *     (commands/coverage.rs:92-124, :339-364)
  *   (no reference item: the reference reports no per-base depth)  gffx_hip_pileup_* (`gffx coverage --mean-depth`)
+ *   (no reference item)                                           gffx_hip_pileup_meta_* (`gffx meta`)
  *   (no reference item)                                           gffx_hip_profile_* (`gffx coverage --thresholds / --bedgraph`)
  *   (no reference item)                                           gffx_hip_closest_* (`gffx closest`)
  *   bam::Reader records -> (chr, start, end) rows        gffx_hip_bgzf_inflate, gffx_hip_bam_* (BAM sources)
@@ -507,6 +508,43 @@ int gffx_hip_pileup_stage_ms(const gffx_hip_pileup *, double *keys, double *sort
 uint64_t gffx_hip_pileup_fold_rows(void);
 uint32_t gffx_hip_pileup_scan_tile(void);
 void gffx_hip_pileup_destroy(gffx_hip_pileup *);
+
+/* ---- pileup, second consumer: the stranded depth profile around features (`gffx meta`; device/meta_core.hpp has the rule,
+ * DESIGN 23) --
+ * Features [feat_start[i], feat_end[i]) on seqid feat_seq[i], on the minus strand where feat_minus[i] != 0, and a layout: in
+ * point mode (0) B = (up + down) / bin columns of `bin` bases around the anchor (0 tss, 1 tes, 2 center), in scaled mode (1)
+ * up / bin columns before the feature, body_bins columns over it, whatever its length, and down / bin behind it.  Columns run in
+ * the direction of transcription: a minus feature is the mirror image of a plus one.  Every column boundary is clamped to
+ * [0, seq_len[seqid]] (seq_len NULL: 2^32 - 1).  Per feature i and column j, with [a, b) the clamped column,
+ *     matrix[i * B + j] = the pileup's bases(a, b) over the rows added so far,  len[i][j] = b - a
+ *     col_bases[j] = sum_i matrix[i][j],  col_len[j] = sum_i len[i][j],  col_features[j] = #{i : len[i][j] > 0}
+ * all unsigned 64-bit sums over rows: any grouping of the rows into _add calls, and rows spread over several pileups whose
+ * totals are added, give the same numbers.  The pileup keeps its segments: _copy gives what it gives without features.
+ *   _meta_set          the features are copied to the device and stay (a second call replaces them and zeroes the totals);
+ *                      col_len and col_features are computed here.  keep_matrix == 0: only the B column totals exist.
+ *                      GFFX_E_INVALID, the handle stays usable: a seqid >= n_seq, start >= end, a layout that is none (bin == 0,
+ *                      up or down no multiple of bin, no column), more than _meta_max_columns() columns.  n_feat == 0 is legal.
+ *   _meta_copy         waits for the folds; B words each (any may be NULL), and the n_feat x B matrix (NULL unless kept)
+ *   _meta_columns      B of a layout, 0 for one that is none (it may exceed the limit)
+ *   _meta_ms           HIP-event milliseconds of the meta kernel over all folds so far (not part of _stats)
+ *   _meta_max_columns / _meta_tile   constants of the build: the column limit, the features per block of the kernel
+ * _reset zeroes the column totals and the matrix too. */
+typedef struct {
+    uint32_t mode;      /* 0 point, 1 scaled */
+    uint32_t anchor;    /* point mode: 0 tss, 1 tes, 2 center */
+    uint32_t up, down;  /* bases before / behind, multiples of bin */
+    uint32_t bin;
+    uint32_t body_bins; /* scaled mode: M */
+} gffx_hip_meta_layout;
+int gffx_hip_pileup_meta_set(gffx_hip_pileup *, uint64_t n_feat, const uint32_t *feat_seq, const uint32_t *feat_start,
+                             const uint32_t *feat_end, const uint8_t *feat_minus, const uint32_t *seq_len /* n_seq or NULL */,
+                             const gffx_hip_meta_layout *, int keep_matrix);
+int gffx_hip_pileup_meta_copy(gffx_hip_pileup *, uint64_t *col_bases, uint64_t *col_len, uint64_t *col_features /* B each */,
+                              uint64_t *matrix /* n_feat x B, NULL unless keep_matrix */);
+int gffx_hip_pileup_meta_ms(const gffx_hip_pileup *, double *ms);
+uint64_t gffx_hip_pileup_meta_columns(const gffx_hip_meta_layout *);
+uint32_t gffx_hip_pileup_meta_max_columns(void);
+uint32_t gffx_hip_pileup_meta_tile(void);
 
 /* ---- depth profile: how deep every base is covered (`gffx coverage --thresholds / --bedgraph`; an addition, the reference has
  * no such figure) --

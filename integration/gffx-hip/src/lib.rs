@@ -53,6 +53,15 @@ pub struct gffx_hip_pileup {
 pub struct gffx_hip_profile {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct gffx_hip_meta_layout {
+    pub mode: u32,      // 0 point, 1 scaled
+    pub anchor: u32,    // point mode: 0 tss, 1 tes, 2 center
+    pub up: u32,        // bases before / behind, multiples of bin
+    pub down: u32,
+    pub bin: u32,
+    pub body_bins: u32, // scaled mode
+}
 
 pub const GFFX_MODE_CONTAINED: c_int = 0; // OverlapMode::Contained       intersect.rs:75
 pub const GFFX_MODE_CONTAINS_REGION: c_int = 1; // OverlapMode::ContainsRegion  intersect.rs:76
@@ -252,6 +261,14 @@ extern "C" {
     pub fn gffx_hip_pileup_fold_rows() -> u64;
     pub fn gffx_hip_pileup_scan_tile() -> u32;
     pub fn gffx_hip_pileup_destroy(p: *mut gffx_hip_pileup);
+    // its second consumer: the stranded depth profile around features (`gffx meta`): B column totals, the features x B matrix if kept
+    pub fn gffx_hip_pileup_meta_set(p: *mut gffx_hip_pileup, n_feat: u64, feat_seq: *const u32, feat_start: *const u32, feat_end: *const u32,
+                                    feat_minus: *const u8, seq_len: *const u32, layout: *const gffx_hip_meta_layout, keep_matrix: c_int) -> c_int;
+    pub fn gffx_hip_pileup_meta_copy(p: *mut gffx_hip_pileup, col_bases: *mut u64, col_len: *mut u64, col_features: *mut u64, matrix: *mut u64) -> c_int;
+    pub fn gffx_hip_pileup_meta_ms(p: *const gffx_hip_pileup, ms: *mut f64) -> c_int;
+    pub fn gffx_hip_pileup_meta_columns(layout: *const gffx_hip_meta_layout) -> u64;
+    pub fn gffx_hip_pileup_meta_max_columns() -> u32;
+    pub fn gffx_hip_pileup_meta_tile() -> u32;
     // the per-base depth as canonical points per seqid (`gffx coverage --thresholds / --bedgraph`): any grouping gives the same points
     pub fn gffx_hip_profile_create(device: c_int, n_seq: u32, out: *mut *mut gffx_hip_profile) -> c_int;
     pub fn gffx_hip_profile_add_host(p: *mut gffx_hip_profile, rows: *const u32, n_rows: u64) -> c_int;
