@@ -331,8 +331,8 @@ int classmap_build(gffx_hip_classmap *H) {
     };
     int rc = [&]() -> int {
         int r;
-        if ((r = classmap_alloc(&buf[0], 3 * n)) || (r = classmap_alloc(&buf[1], 3 * n)) || (r = classmap_alloc(&work, DeviceSort::work_words(n, plan.n_passes))) ||
-            (r = classmap_alloc(&tile[0], tiles)) || (r = classmap_alloc(&tile[1], tiles)) || (r = classmap_alloc(&tile[2], tiles)))
+        if ((r = dev_alloc_padded(&buf[0], 3 * n)) || (r = dev_alloc_padded(&buf[1], 3 * n)) || (r = dev_alloc_padded(&work, DeviceSort::work_words(n, plan.n_passes))) ||
+            (r = dev_alloc_padded(&tile[0], tiles)) || (r = dev_alloc_padded(&tile[1], tiles)) || (r = dev_alloc_padded(&tile[2], tiles)))
             return r;
         GFFX_HIP_TRY(hipMemsetAsync(H->ctl, 0, 32, H->stream));
         GFFX_HIP_TRY(hipEventRecord(H->ev[0], H->stream));
@@ -359,8 +359,8 @@ int classmap_build(gffx_hip_classmap *H) {
         const u64 np = (u64)h[4] | ((u64)h[5] << 32);
         if (np > n) return fail(GFFX_E_HIP, "gffx_hip_classmap_finish: more points than events");
         const uint32_t ptiles = classmap_grid(np, kClassScanTile);
-        if ((r = classmap_alloc(&H->p_seq, np)) || (r = classmap_alloc(&H->p_pos, np)) || (r = classmap_alloc(&H->p_cls, np)) ||
-            (r = classmap_alloc(&H->cb, np * T)) || (r = classmap_alloc(&tile_tot, (u64)ptiles * T)))
+        if ((r = dev_alloc_padded(&H->p_seq, np)) || (r = dev_alloc_padded(&H->p_pos, np)) || (r = dev_alloc_padded(&H->p_cls, np)) ||
+            (r = dev_alloc_padded(&H->cb, np * T)) || (r = dev_alloc_padded(&tile_tot, (u64)ptiles * T)))
             return r;
         GFFX_HIP_TRY(hipEventRecord(H->ev[5], H->stream));
         hipLaunchKernelGGL(k_classmap_emit, dim3(tiles), dim3(kClassThreads), 0, H->stream, (const uint32_t *)sorted, n, T, (const u64 *)tile[0], (const u64 *)tile[1],
@@ -402,25 +402,25 @@ int classmap_run(gffx_hip_classmap *H, const uint32_t *rows, uint64_t nq, const 
         H->ran = true;
         return GFFX_OK;
     }
-    GFFX_CLASSMAP_TRY(classmap_ensure(H->d_counts, nq * (H->T + 1), "the counts"));
-    GFFX_CLASSMAP_TRY(classmap_ensure(H->d_class, nq, "the class bytes"));
+    GFFX_KEEP_TRY(H, classmap_ensure(H->d_counts, nq * (H->T + 1), "the counts"));
+    GFFX_KEEP_TRY(H, classmap_ensure(H->d_class, nq, "the class bytes"));
     const ClassMapView M{H->p_off, H->p_pos, H->p_cls, H->cb, H->n_seq, H->T};
-    GFFX_CLASSMAP_HIP(hipMemsetAsync(H->ctl, 0, 4, H->stream));
-    GFFX_CLASSMAP_HIP(hipEventRecord(H->ev[8], H->stream));
+    GFFX_KEEP_HIP(H, hipMemsetAsync(H->ctl, 0, 4, H->stream));
+    GFFX_KEEP_HIP(H, hipEventRecord(H->ev[8], H->stream));
     hipLaunchKernelGGL(k_classmap_regions, dim3(classmap_grid(nq, kClassThreads)), dim3(kClassThreads), 0, H->stream, M, rows, (u64)nq, H->d_counts.p, H->d_class.p,
                        H->ctl);
-    GFFX_CLASSMAP_HIP(hipGetLastError());
-    GFFX_CLASSMAP_HIP(hipEventRecord(H->ev[9], H->stream));
+    GFFX_KEEP_HIP(H, hipGetLastError());
+    GFFX_KEEP_HIP(H, hipEventRecord(H->ev[9], H->stream));
     uint32_t err = 0;
-    GFFX_CLASSMAP_HIP(hipMemcpyAsync(&err, H->ctl, 4, hipMemcpyDeviceToHost, H->stream));
-    GFFX_CLASSMAP_HIP(hipStreamSynchronize(H->stream));
+    GFFX_KEEP_HIP(H, hipMemcpyAsync(&err, H->ctl, 4, hipMemcpyDeviceToHost, H->stream));
+    GFFX_KEEP_HIP(H, hipStreamSynchronize(H->stream));
     if (err & kClassErrRange) return fail(GFFX_E_CHR_RANGE, "%s: a region has chr >= %u", who, H->n_seq);  // (the run is void, the object stays usable)
     H->ran = true;
     return GFFX_OK;
 }
 
 int classmap_results(gffx_hip_classmap *H, const char *who) {
-    const int rc = classmap_enter(H, who);
+    const int rc = enter_handle(H, who);
     if (rc) return rc;
     if (!H->ran || !H->waited) return fail(GFFX_E_STATE, "%s: no run has been waited for", who);
     return GFFX_OK;
@@ -462,13 +462,13 @@ extern "C" int gffx_hip_classmap_create(int device, uint32_t n_seq, uint32_t n_l
     GFFX_HIP_TRY(hipSetDevice(device));
     GFFX_HIP_TRY(hipStreamCreateWithFlags(&H->stream, hipStreamNonBlocking));
     for (hipEvent_t &e : H->ev) GFFX_HIP_TRY(hipEventCreate(&e));
-    if ((rc = classmap_alloc(&H->ctl, 8)) || (rc = classmap_alloc(&H->p_off, (uint64_t)n_seq + 1))) return rc;
+    if ((rc = dev_alloc_padded(&H->ctl, 8)) || (rc = dev_alloc_padded(&H->p_off, (uint64_t)n_seq + 1))) return rc;
     *out = H.release();
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_classmap_add_rows_host(gffx_hip_classmap *H, const uint32_t *rows, uint64_t n_rows) {
-    int rc = classmap_enter(H, "gffx_hip_classmap_add_rows_host");
+    int rc = enter_handle(H, "gffx_hip_classmap_add_rows_host");
     if (rc) return rc;
     if (n_rows && !rows) return fail(GFFX_E_INVALID, "gffx_hip_classmap_add_rows_host: rows is NULL");
     if (!n_rows) return GFFX_OK;
@@ -481,21 +481,21 @@ extern "C" int gffx_hip_classmap_add_rows_host(gffx_hip_classmap *H, const uint3
         inverted |= s >= e;
         H->pseudo[3 * i] = c * H->T + k, H->pseudo[3 * i + 1] = s, H->pseudo[3 * i + 2] = e;  // (wraps only in a refused call)
     }
-    if (range) return classmap_fail(H, fail(GFFX_E_CHR_RANGE, "gffx_hip_classmap_add_rows_host: a row has layer >= %u or chr >= %u", H->T, H->n_seq));
-    if (inverted) return classmap_fail(H, fail(GFFX_E_INVALID, "gffx_hip_classmap_add_rows_host: a row has start >= end"));
+    if (range) return keep_failure(H, fail(GFFX_E_CHR_RANGE, "gffx_hip_classmap_add_rows_host: a row has layer >= %u or chr >= %u", H->T, H->n_seq));
+    if (inverted) return keep_failure(H, fail(GFFX_E_INVALID, "gffx_hip_classmap_add_rows_host: a row has start >= end"));
     H->finished = false;
-    GFFX_CLASSMAP_TRY(gffx_hip_union_add_host(H->U, H->pseudo.data(), n_rows));
+    GFFX_KEEP_TRY(H, gffx_hip_union_add_host(H->U, H->pseudo.data(), n_rows));
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_classmap_finish(gffx_hip_classmap *H) {
-    int rc = classmap_enter(H, "gffx_hip_classmap_finish");
+    int rc = enter_handle(H, "gffx_hip_classmap_finish");
     if (rc) return rc;
     if (H->finished) return GFFX_OK;
-    GFFX_CLASSMAP_HIP(hipStreamSynchronize(H->stream));  // (no run reads the points that go away next)
+    GFFX_KEEP_HIP(H, hipStreamSynchronize(H->stream));  // (no run reads the points that go away next)
     classmap_drop_points(H);
     H->ran = H->waited = false;
-    GFFX_CLASSMAP_TRY(classmap_build(H));
+    GFFX_KEEP_TRY(H, classmap_build(H));
     H->finished = true;
     return GFFX_OK;
 }
@@ -505,9 +505,9 @@ extern "C" uint64_t gffx_hip_classmap_n_points(const gffx_hip_classmap *H) { ret
 extern "C" int gffx_hip_classmap_copy_points(gffx_hip_classmap *H, uint64_t *p_off, uint32_t *pos, uint8_t *cls) {
     const int rc = classmap_ready(H, "gffx_hip_classmap_copy_points");
     if (rc) return rc;
-    if (p_off) GFFX_CLASSMAP_HIP(hipMemcpy(p_off, H->p_off, ((size_t)H->n_seq + 1) * 8, hipMemcpyDeviceToHost));
-    if (pos && H->n_points) GFFX_CLASSMAP_HIP(hipMemcpy(pos, H->p_pos, H->n_points * 4, hipMemcpyDeviceToHost));
-    if (cls && H->n_points) GFFX_CLASSMAP_HIP(hipMemcpy(cls, H->p_cls, H->n_points, hipMemcpyDeviceToHost));
+    if (p_off) GFFX_KEEP_HIP(H, hipMemcpy(p_off, H->p_off, ((size_t)H->n_seq + 1) * 8, hipMemcpyDeviceToHost));
+    if (pos && H->n_points) GFFX_KEEP_HIP(H, hipMemcpy(pos, H->p_pos, H->n_points * 4, hipMemcpyDeviceToHost));
+    if (cls && H->n_points) GFFX_KEEP_HIP(H, hipMemcpy(cls, H->p_cls, H->n_points, hipMemcpyDeviceToHost));
     return GFFX_OK;
 }
 
@@ -517,7 +517,7 @@ extern "C" int gffx_hip_classmap_copy_bases(gffx_hip_classmap *H, uint64_t *cb) 
     if (H->n_points && !cb) return fail(GFFX_E_INVALID, "gffx_hip_classmap_copy_bases: cb is NULL");
     if (!H->n_points) return GFFX_OK;
     std::vector<u64> v(H->n_points * H->T);
-    GFFX_CLASSMAP_HIP(hipMemcpy(v.data(), H->cb, v.size() * 8, hipMemcpyDeviceToHost));
+    GFFX_KEEP_HIP(H, hipMemcpy(v.data(), H->cb, v.size() * 8, hipMemcpyDeviceToHost));
     for (uint64_t i = 0; i < H->n_points; ++i)  // (the device keeps a point's T sums side by side; the caller gets cb[k][i])
         for (uint32_t k = 0; k < H->T; ++k) cb[k * H->n_points + i] = v[i * H->T + k];
     return GFFX_OK;
@@ -528,8 +528,8 @@ extern "C" int gffx_hip_classmap_run_host(gffx_hip_classmap *H, const uint32_t *
     if (rc) return rc;
     if (nq && !regions) return fail(GFFX_E_INVALID, "gffx_hip_classmap_run_host: regions is NULL");
     if (nq) {
-        GFFX_CLASSMAP_TRY(classmap_ensure(H->d_regions, 3 * nq, "the regions"));
-        GFFX_CLASSMAP_HIP(hipMemcpyAsync(H->d_regions.p, regions, nq * 12, hipMemcpyHostToDevice, H->stream));
+        GFFX_KEEP_TRY(H, classmap_ensure(H->d_regions, 3 * nq, "the regions"));
+        GFFX_KEEP_HIP(H, hipMemcpyAsync(H->d_regions.p, regions, nq * 12, hipMemcpyHostToDevice, H->stream));
     }
     return classmap_run(H, H->d_regions.p, nq, "gffx_hip_classmap_run_host");  // (it waits for the kernel: the caller's array is free)
 }
@@ -537,19 +537,18 @@ extern "C" int gffx_hip_classmap_run_host(gffx_hip_classmap *H, const uint32_t *
 extern "C" int gffx_hip_classmap_run_store(gffx_hip_classmap *H, const gffx_hip_regions *R, int k, uint64_t first, uint64_t n_rows) {
     const int rc = classmap_ready(H, "gffx_hip_classmap_run_store");
     if (rc) return rc;
-    if (!R || (k != 0 && k != 1)) return fail(GFFX_E_INVALID, "gffx_hip_classmap_run_store: bad argument");
-    if (R->device != H->device) return fail(GFFX_E_INVALID, "gffx_hip_classmap_run_store: store and class map on different devices");
-    if (first + n_rows > R->last_n[k]) return fail(GFFX_E_INVALID, "gffx_hip_classmap_run_store: rows beyond the last append");
-    if (R->pending[k]) GFFX_CLASSMAP_HIP(hipStreamWaitEvent(H->stream, R->copied[k], 0));
-    return classmap_run(H, R->d + 3 * (R->last_first[k] + first), n_rows, "gffx_hip_classmap_run_store");  // (the slot is read in place)
+    const uint32_t *rows = nullptr;
+    if (const int bad = store_slot_rows(R, k, first, n_rows, H->device, "gffx_hip_classmap_run_store", "class map", &rows)) return bad;
+    if (R->pending[k]) GFFX_KEEP_HIP(H, hipStreamWaitEvent(H->stream, R->copied[k], 0));
+    return classmap_run(H, rows, n_rows, "gffx_hip_classmap_run_store");  // (the slot is read in place)
 }
 
 extern "C" int gffx_hip_classmap_wait(gffx_hip_classmap *H) {
-    const int rc = classmap_enter(H, "gffx_hip_classmap_wait");
+    const int rc = enter_handle(H, "gffx_hip_classmap_wait");
     if (rc) return rc;
     if (!H->ran) return fail(GFFX_E_STATE, "gffx_hip_classmap_wait: nothing has been run");
     if (H->waited) return GFFX_OK;
-    GFFX_CLASSMAP_HIP(hipStreamSynchronize(H->stream));
+    GFFX_KEEP_HIP(H, hipStreamSynchronize(H->stream));
     float ms = 0.f;
     if (H->nq && hipEventElapsedTime(&ms, H->ev[8], H->ev[9]) == hipSuccess) H->kernel_ms = ms;
     H->waited = true;
@@ -560,7 +559,7 @@ extern "C" int gffx_hip_classmap_copy_counts(gffx_hip_classmap *H, uint32_t *cou
     const int rc = classmap_results(H, "gffx_hip_classmap_copy_counts");
     if (rc) return rc;
     if (H->nq && !counts) return fail(GFFX_E_INVALID, "gffx_hip_classmap_copy_counts: counts is NULL");
-    if (H->nq) GFFX_CLASSMAP_HIP(hipMemcpy(counts, H->d_counts.p, H->nq * (H->T + 1) * 4, hipMemcpyDeviceToHost));
+    if (H->nq) GFFX_KEEP_HIP(H, hipMemcpy(counts, H->d_counts.p, H->nq * (H->T + 1) * 4, hipMemcpyDeviceToHost));
     return GFFX_OK;
 }
 
@@ -568,7 +567,7 @@ extern "C" int gffx_hip_classmap_copy_class(gffx_hip_classmap *H, uint8_t *cls) 
     const int rc = classmap_results(H, "gffx_hip_classmap_copy_class");
     if (rc) return rc;
     if (H->nq && !cls) return fail(GFFX_E_INVALID, "gffx_hip_classmap_copy_class: cls is NULL");
-    if (H->nq) GFFX_CLASSMAP_HIP(hipMemcpy(cls, H->d_class.p, H->nq, hipMemcpyDeviceToHost));
+    if (H->nq) GFFX_KEEP_HIP(H, hipMemcpy(cls, H->d_class.p, H->nq, hipMemcpyDeviceToHost));
     return GFFX_OK;
 }
 

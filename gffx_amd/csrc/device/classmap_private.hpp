@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "gffx_device.hpp"
+#include "handle_status.hpp"
 
 struct gffx_hip_union;  // (union_private.hpp)
 
@@ -25,11 +26,9 @@ struct ClassMapView {
 
 }  // namespace gffx
 
-struct gffx_hip_classmap {
-    int device = 0;
+struct gffx_hip_classmap : gffx::HandleStatus {
+    static constexpr const char *kName = "classmap", *kNoun = "object";
     uint32_t n_seq = 0, T = 0;
-    int status = GFFX_OK;  // the first error: the object only reports it again
-    std::string message;
     hipStream_t stream = nullptr;
     // _finish: 0 .. 1 toggles, 1 .. 2 sort, 2 .. 3 scan, 3 .. 4 count, 5 .. 6 emit + offsets, 6 .. 7 bases; a run: 8 .. 9
     hipEvent_t ev[10] = {};
@@ -65,36 +64,10 @@ struct gffx_hip_classmap {
 
 namespace gffx {
 
-inline int classmap_fail(gffx_hip_classmap *H, int rc) {  // rc came from fail(): keep it and its message
-    if (H->status == GFFX_OK) H->status = rc, H->message = g_last_error;
-    return rc;
-}
-#define GFFX_CLASSMAP_TRY(expr)                \
-    do {                                       \
-        const int _rc = (expr);                \
-        if (_rc) return classmap_fail(H, _rc); \
-    } while (0)
-// a HIP call of an entry point that works on the handle: its failure is kept (argument errors of a run are not)
-#define GFFX_CLASSMAP_HIP(expr) GFFX_CLASSMAP_TRY([&]() -> int { GFFX_HIP_TRY(expr); return GFFX_OK; }())
-
-inline int classmap_enter(const gffx_hip_classmap *H, const char *who) {
-    if (!H) return fail(GFFX_E_INVALID, "%s: classmap is NULL", who);
-    if (H->status != GFFX_OK) return fail(H->status, "%s: the object failed earlier: %s", who, H->message.c_str());
-    GFFX_HIP_TRY(hipSetDevice(H->device));
-    return GFFX_OK;
-}
-
 inline int classmap_ready(gffx_hip_classmap *H, const char *who) {
-    const int rc = classmap_enter(H, who);
+    const int rc = enter_handle(H, who);
     if (rc) return rc;
     if (!H->finished) return fail(GFFX_E_STATE, "%s: call gffx_hip_classmap_finish first", who);
-    return GFFX_OK;
-}
-
-template <typename X>
-int classmap_alloc(X **p, uint64_t n) {
-    *p = nullptr;
-    GFFX_HIP_TRY(hipMalloc((void **)p, std::max<uint64_t>(n, 4) * sizeof(X)));
     return GFFX_OK;
 }
 

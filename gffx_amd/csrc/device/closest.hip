@@ -21,6 +21,7 @@
 
 #include "engine_private.hpp"
 #include "closest_core.hpp"
+#include "handle_status.hpp"
 #include "join_a_kernels.hpp"
 #include "radix_sort.hpp"
 #include "regions_store.hpp"
@@ -198,11 +199,9 @@ __global__ __launch_bounds__(kJoinThreads) void k_closest_emit(IndexView ix, End
 
 }  // namespace gffx
 
-struct gffx_hip_closest {
+struct gffx_hip_closest : gffx::HandleStatus {
+    static constexpr const char *kName = "closest", *kNoun = "object";
     const gffx_hip_index *ix = nullptr;
-    int device = 0;
-    int status = GFFX_OK;  // the first error: the object only reports it again
-    std::string message;
     hipStream_t stream = nullptr;
     hipEvent_t ev[4] = {};  // count: 0 .. 1, emit: 2 .. 3
     hipEvent_t build[2] = {};
@@ -222,25 +221,6 @@ struct gffx_hip_closest {
 };
 
 namespace {
-
-int closest_fail(gffx_hip_closest *H, int rc) {  // rc came from fail(): keep it and its message
-    if (H->status == GFFX_OK) H->status = rc, H->message = g_last_error;
-    return rc;
-}
-#define GFFX_CLOSEST_TRY(expr)                \
-    do {                                      \
-        const int _rc = (expr);               \
-        if (_rc) return closest_fail(H, _rc); \
-    } while (0)
-// a HIP call of an entry point that works on the handle: its failure is kept (argument errors are not)
-#define GFFX_CLOSEST_HIP(expr) GFFX_CLOSEST_TRY([&]() -> int { GFFX_HIP_TRY(expr); return GFFX_OK; }())
-
-int closest_enter(const gffx_hip_closest *H, const char *who) {
-    if (!H) return fail(GFFX_E_INVALID, "%s: closest is NULL", who);
-    if (H->status != GFFX_OK) return fail(H->status, "%s: the object failed earlier: %s", who, H->message.c_str());
-    GFFX_HIP_TRY(hipSetDevice(H->device));
-    return GFFX_OK;
-}
 
 // the end table: sorted on the device, once
 int closest_build(gffx_hip_closest *H) {
@@ -302,7 +282,7 @@ int closest_run(gffx_hip_closest *H, const uint32_t *regions, uint64_t nq, uint3
     H->chunk = tiles_per_block * kJoinThreads;
     H->n_blocks = (uint32_t)((nq + H->chunk - 1) / H->chunk);
     if (!nq) {
-        GFFX_CLOSEST_HIP(hipMemsetAsync(H->d_offsets, 0, 8, H->stream));
+        GFFX_KEEP_HIP(H, hipMemsetAsync(H->d_offsets, 0, 8, H->stream));
         H->ran = true;
         return GFFX_OK;
     }
@@ -310,19 +290,19 @@ int closest_run(gffx_hip_closest *H, const uint32_t *regions, uint64_t nq, uint3
     const uint32_t lds = ml ? meta_bytes(ix) : 0u;
     const EndTable et{H->e_end, H->e_pos};
     ClosestOut out{H->d_counts, H->d_gaps, H->d_block_sums, H->d_offsets, H->triples.p, (u64)(H->triples.cap / 3), H->d_err};
-    GFFX_CLOSEST_HIP(hipMemsetAsync(H->d_err, 0, 4, H->stream));
-    GFFX_CLOSEST_HIP(hipEventRecord(H->ev[0], H->stream));
+    GFFX_KEEP_HIP(H, hipMemsetAsync(H->d_err, 0, 4, H->stream));
+    GFFX_KEEP_HIP(H, hipEventRecord(H->ev[0], H->stream));
     if (ml)
         hipLaunchKernelGGL(k_closest_count<true>, dim3(H->n_blocks), dim3(kJoinThreads), 32 + lds, H->stream, ix->view(), et, regions, (u64)nq, (u64)H->chunk,
                            flags, out);
     else
         hipLaunchKernelGGL(k_closest_count<false>, dim3(H->n_blocks), dim3(kJoinThreads), 32, H->stream, ix->view(), et, regions, (u64)nq, (u64)H->chunk,
                            flags, out);
-    GFFX_CLOSEST_HIP(hipGetLastError());
-    GFFX_CLOSEST_HIP(hipEventRecord(H->ev[1], H->stream));
-    GFFX_CLOSEST_HIP(hipMemcpyAsync(H->h_sums, H->d_block_sums, (size_t)H->n_blocks * 8, hipMemcpyDeviceToHost, H->stream));
-    GFFX_CLOSEST_HIP(hipMemcpyAsync(H->h_sums + kClosestMaxBlocks, H->d_err, 4, hipMemcpyDeviceToHost, H->stream));
-    GFFX_CLOSEST_HIP(hipStreamSynchronize(H->stream));
+    GFFX_KEEP_HIP(H, hipGetLastError());
+    GFFX_KEEP_HIP(H, hipEventRecord(H->ev[1], H->stream));
+    GFFX_KEEP_HIP(H, hipMemcpyAsync(H->h_sums, H->d_block_sums, (size_t)H->n_blocks * 8, hipMemcpyDeviceToHost, H->stream));
+    GFFX_KEEP_HIP(H, hipMemcpyAsync(H->h_sums + kClosestMaxBlocks, H->d_err, 4, hipMemcpyDeviceToHost, H->stream));
+    GFFX_KEEP_HIP(H, hipStreamSynchronize(H->stream));
     if (*reinterpret_cast<const uint32_t *>(H->h_sums + kClosestMaxBlocks) & 1u)
         return fail(GFFX_E_CHR_RANGE, "gffx_hip_closest: a region has chr >= %u", ix->n_chr);  // (the run is void, the object stays usable)
     uint64_t total = 0;
@@ -330,28 +310,28 @@ int closest_run(gffx_hip_closest *H, const uint32_t *regions, uint64_t nq, uint3
     if (3 * total > H->triples.cap) {
         const hipError_t e = H->triples.ensure((size_t)(3 * total));
         if (e != hipSuccess)
-            return closest_fail(H, fail(e == hipErrorOutOfMemory ? GFFX_E_OOM : GFFX_E_HIP, "gffx_hip_closest: no room for %llu pairs: %s",
+            return keep_failure(H, fail(e == hipErrorOutOfMemory ? GFFX_E_OOM : GFFX_E_HIP, "gffx_hip_closest: no room for %llu pairs: %s",
                                         (unsigned long long)total, hipGetErrorString(e)));
         H->grows++;
     }
     out.triples = H->triples.p;
     out.capacity = H->triples.cap / 3;
-    GFFX_CLOSEST_HIP(hipEventRecord(H->ev[2], H->stream));
+    GFFX_KEEP_HIP(H, hipEventRecord(H->ev[2], H->stream));
     if (ml)
         hipLaunchKernelGGL(k_closest_emit<true>, dim3(H->n_blocks), dim3(kJoinThreads), 48 + lds, H->stream, ix->view(), et, regions, (u64)nq, (u64)H->chunk,
                            flags, out);
     else
         hipLaunchKernelGGL(k_closest_emit<false>, dim3(H->n_blocks), dim3(kJoinThreads), 48, H->stream, ix->view(), et, regions, (u64)nq, (u64)H->chunk,
                            flags, out);
-    GFFX_CLOSEST_HIP(hipGetLastError());
-    GFFX_CLOSEST_HIP(hipEventRecord(H->ev[3], H->stream));
+    GFFX_KEEP_HIP(H, hipGetLastError());
+    GFFX_KEEP_HIP(H, hipEventRecord(H->ev[3], H->stream));
     H->total = total;
     H->ran = true;
     return GFFX_OK;
 }
 
 int closest_results(gffx_hip_closest *H, const char *who) {
-    const int rc = closest_enter(H, who);
+    const int rc = enter_handle(H, who);
     if (rc) return rc;
     if (!H->ran || !H->waited) return fail(GFFX_E_STATE, "%s: no run has been waited for", who);
     return GFFX_OK;
@@ -417,30 +397,29 @@ extern "C" int gffx_hip_closest_create(const gffx_hip_index *ix, uint64_t max_qu
 
 extern "C" int gffx_hip_closest_run_host(gffx_hip_closest *H, const uint32_t *regions, uint64_t nq, uint32_t flags) {
     int rc = closest_check_flags(flags, "gffx_hip_closest_run_host");
-    if (rc || (rc = closest_enter(H, "gffx_hip_closest_run_host")) || (rc = closest_check_nq(H, nq, "gffx_hip_closest_run_host"))) return rc;
+    if (rc || (rc = enter_handle(H, "gffx_hip_closest_run_host")) || (rc = closest_check_nq(H, nq, "gffx_hip_closest_run_host"))) return rc;
     if (nq && !regions) return fail(GFFX_E_INVALID, "gffx_hip_closest_run_host: regions is NULL");
     // (closest_run waits for the count pass, which runs behind this copy: the caller's array is free when the call returns)
-    if (nq) GFFX_CLOSEST_HIP(hipMemcpyAsync(H->d_regions, regions, nq * 12, hipMemcpyHostToDevice, H->stream));
+    if (nq) GFFX_KEEP_HIP(H, hipMemcpyAsync(H->d_regions, regions, nq * 12, hipMemcpyHostToDevice, H->stream));
     return closest_run(H, H->d_regions, nq, flags);
 }
 
 extern "C" int gffx_hip_closest_run_store(gffx_hip_closest *H, const gffx_hip_regions *R, int k, uint64_t first, uint64_t n_rows, uint32_t flags) {
     int rc = closest_check_flags(flags, "gffx_hip_closest_run_store");
-    if (rc || (rc = closest_enter(H, "gffx_hip_closest_run_store"))) return rc;
-    if (!R || (k != 0 && k != 1)) return fail(GFFX_E_INVALID, "gffx_hip_closest_run_store: bad argument");
+    if (rc || (rc = enter_handle(H, "gffx_hip_closest_run_store"))) return rc;
     if ((rc = closest_check_nq(H, n_rows, "gffx_hip_closest_run_store"))) return rc;
-    if (R->device != H->device) return fail(GFFX_E_INVALID, "gffx_hip_closest_run_store: store and index on different devices");
-    if (first + n_rows > R->last_n[k]) return fail(GFFX_E_INVALID, "gffx_hip_closest_run_store: rows beyond the last append");
-    if (R->pending[k]) GFFX_CLOSEST_HIP(hipStreamWaitEvent(H->stream, R->copied[k], 0));
-    return closest_run(H, R->d + 3 * (R->last_first[k] + first), n_rows, flags);  // (the slot is read in place: no copy)
+    const uint32_t *rows = nullptr;
+    if ((rc = store_slot_rows(R, k, first, n_rows, H->device, "gffx_hip_closest_run_store", "index", &rows))) return rc;
+    if (R->pending[k]) GFFX_KEEP_HIP(H, hipStreamWaitEvent(H->stream, R->copied[k], 0));
+    return closest_run(H, rows, n_rows, flags);  // (the slot is read in place: no copy)
 }
 
 extern "C" int gffx_hip_closest_wait(gffx_hip_closest *H) {
-    const int rc = closest_enter(H, "gffx_hip_closest_wait");
+    const int rc = enter_handle(H, "gffx_hip_closest_wait");
     if (rc) return rc;
     if (!H->ran) return fail(GFFX_E_STATE, "gffx_hip_closest_wait: nothing has been run");
     if (H->waited) return GFFX_OK;
-    GFFX_CLOSEST_HIP(hipStreamSynchronize(H->stream));
+    GFFX_KEEP_HIP(H, hipStreamSynchronize(H->stream));
     if (H->nq) {
         float a = 0.f, b = 0.f;
         if (hipEventElapsedTime(&a, H->ev[0], H->ev[1]) == hipSuccess && hipEventElapsedTime(&b, H->ev[2], H->ev[3]) == hipSuccess) H->kernel_ms = (double)a + b;
@@ -461,7 +440,7 @@ extern "C" int gffx_hip_closest_copy_counts(gffx_hip_closest *H, uint32_t *count
     const int rc = closest_results(H, "gffx_hip_closest_copy_counts");
     if (rc) return rc;
     if (H->nq && !counts) return fail(GFFX_E_INVALID, "gffx_hip_closest_copy_counts: counts is NULL");
-    if (H->nq) GFFX_CLOSEST_HIP(hipMemcpy(counts, H->d_counts, H->nq * 4, hipMemcpyDeviceToHost));
+    if (H->nq) GFFX_KEEP_HIP(H, hipMemcpy(counts, H->d_counts, H->nq * 4, hipMemcpyDeviceToHost));
     return GFFX_OK;
 }
 
@@ -469,7 +448,7 @@ extern "C" int gffx_hip_closest_copy_gaps(gffx_hip_closest *H, uint32_t *gaps) {
     const int rc = closest_results(H, "gffx_hip_closest_copy_gaps");
     if (rc) return rc;
     if (H->nq && !gaps) return fail(GFFX_E_INVALID, "gffx_hip_closest_copy_gaps: gaps is NULL");
-    if (H->nq) GFFX_CLOSEST_HIP(hipMemcpy(gaps, H->d_gaps, H->nq * 4, hipMemcpyDeviceToHost));
+    if (H->nq) GFFX_KEEP_HIP(H, hipMemcpy(gaps, H->d_gaps, H->nq * 4, hipMemcpyDeviceToHost));
     return GFFX_OK;
 }
 
@@ -477,7 +456,7 @@ extern "C" int gffx_hip_closest_copy_offsets(gffx_hip_closest *H, uint64_t *offs
     const int rc = closest_results(H, "gffx_hip_closest_copy_offsets");
     if (rc) return rc;
     if (!offsets) return fail(GFFX_E_INVALID, "gffx_hip_closest_copy_offsets: offsets is NULL");
-    GFFX_CLOSEST_HIP(hipMemcpy(offsets, H->d_offsets, (H->nq + 1) * 8, hipMemcpyDeviceToHost));
+    GFFX_KEEP_HIP(H, hipMemcpy(offsets, H->d_offsets, (H->nq + 1) * 8, hipMemcpyDeviceToHost));
     return GFFX_OK;
 }
 
@@ -485,16 +464,16 @@ extern "C" int gffx_hip_closest_copy_triples(gffx_hip_closest *H, uint32_t *trip
     const int rc = closest_results(H, "gffx_hip_closest_copy_triples");
     if (rc) return rc;
     if (H->total && !triples) return fail(GFFX_E_INVALID, "gffx_hip_closest_copy_triples: triples is NULL");
-    if (H->total) GFFX_CLOSEST_HIP(hipMemcpy(triples, H->triples.p, H->total * 12, hipMemcpyDeviceToHost));
+    if (H->total) GFFX_KEEP_HIP(H, hipMemcpy(triples, H->triples.p, H->total * 12, hipMemcpyDeviceToHost));
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_closest_copy_end_table(gffx_hip_closest *H, uint32_t *e_end, uint32_t *e_pos) {
-    const int rc = closest_enter(H, "gffx_hip_closest_copy_end_table");
+    const int rc = enter_handle(H, "gffx_hip_closest_copy_end_table");
     if (rc) return rc;
     const size_t n = H->ix->n_roots;
-    if (n && e_end) GFFX_CLOSEST_HIP(hipMemcpy(e_end, H->e_end, n * 4, hipMemcpyDeviceToHost));
-    if (n && e_pos) GFFX_CLOSEST_HIP(hipMemcpy(e_pos, H->e_pos, n * 4, hipMemcpyDeviceToHost));
+    if (n && e_end) GFFX_KEEP_HIP(H, hipMemcpy(e_end, H->e_end, n * 4, hipMemcpyDeviceToHost));
+    if (n && e_pos) GFFX_KEEP_HIP(H, hipMemcpy(e_pos, H->e_pos, n * 4, hipMemcpyDeviceToHost));
     return GFFX_OK;
 }
 

@@ -381,36 +381,12 @@ __global__ __launch_bounds__(kUnionThreads) void k_union_emit(const uint32_t *re
 
 namespace {
 
-int union_fail(gffx_hip_union *U, int rc) {  // rc came from fail(): keep it and its message
-    if (U->status == GFFX_OK) U->status = rc, U->message = g_last_error;
-    return rc;
-}
-#define GFFX_UNION_TRY(expr)                   \
-    do {                                       \
-        const int _rc = (expr);                \
-        if (_rc) return union_fail(U, _rc);    \
-    } while (0)
-
-int union_enter(gffx_hip_union *U, const char *who) {
-    if (!U) return fail(GFFX_E_INVALID, "%s: union is NULL", who);
-    if (U->status != GFFX_OK) return fail(U->status, "%s: the union failed earlier: %s", who, U->message.c_str());
-    GFFX_HIP_TRY(hipSetDevice(U->device));
-    return GFFX_OK;
-}
-
 void union_drop_tables(gffx_hip_union *U) {
     for (void *&p : U->tables) {
         if (p) (void)hipFree(p);
         p = nullptr;
     }
     U->finished = false;
-}
-
-template <typename T>
-int union_alloc(T **p, uint64_t n) {
-    *p = nullptr;
-    GFFX_HIP_TRY(hipMalloc((void **)p, std::max<uint64_t>(n, 4) * sizeof(T)));
-    return GFFX_OK;
 }
 
 // room for the spans so far + m new rows (the spans stay at the front of rec_a)
@@ -421,8 +397,8 @@ int union_reserve(gffx_hip_union *U, uint64_t m) {
     if (n > U->cap) {
         const uint64_t cap = n + n / 4 + 1024;
         uint32_t *a = nullptr, *b = nullptr;
-        if ((rc = union_alloc(&a, 3 * cap))) return rc;
-        if ((rc = union_alloc(&b, 3 * cap))) {
+        if ((rc = dev_alloc_padded(&a, 3 * cap))) return rc;
+        if ((rc = dev_alloc_padded(&b, 3 * cap))) {
             (void)hipFree(a);
             return rc;
         }
@@ -442,7 +418,7 @@ int union_reserve(gffx_hip_union *U, uint64_t m) {
     if (want_work > U->cap_work) {
         if (U->work) GFFX_HIP_TRY(hipFree(U->work));
         U->cap_work = 0;
-        if ((rc = union_alloc(&U->work, want_work))) return rc;
+        if ((rc = dev_alloc_padded(&U->work, want_work))) return rc;
         U->cap_work = want_work;
     }
     if (want_tiles > U->cap_tiles) {
@@ -450,7 +426,7 @@ int union_reserve(gffx_hip_union *U, uint64_t m) {
         if (U->tile_b) GFFX_HIP_TRY(hipFree(U->tile_b));
         U->tile_a = U->tile_b = nullptr;
         U->cap_tiles = 0;
-        if ((rc = union_alloc(&U->tile_a, want_tiles)) || (rc = union_alloc(&U->tile_b, want_tiles))) return rc;
+        if ((rc = dev_alloc_padded(&U->tile_a, want_tiles)) || (rc = dev_alloc_padded(&U->tile_b, want_tiles))) return rc;
         U->cap_tiles = want_tiles;
     }
     return GFFX_OK;
@@ -533,14 +509,14 @@ extern "C" int gffx_hip_union_create(int device, uint32_t n_seq, gffx_hip_union 
     GFFX_HIP_TRY(hipStreamCreateWithFlags(&U->stream, hipStreamNonBlocking));
     GFFX_HIP_TRY(hipEventCreate(&U->ev0));
     GFFX_HIP_TRY(hipEventCreate(&U->ev1));
-    int rc = union_alloc(&U->ctl, 8);
+    int rc = dev_alloc_padded(&U->ctl, 8);
     if (rc) return rc;
     *out = U.release();
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_union_add_host(gffx_hip_union *U, const uint32_t *rows, uint64_t n_rows) {
-    int rc = union_enter(U, "gffx_hip_union_add_host");
+    int rc = enter_handle(U, "gffx_hip_union_add_host");
     if (rc) return rc;
     if (n_rows && !rows) return fail(GFFX_E_INVALID, "gffx_hip_union_add_host: rows is NULL");
     const uint64_t want = std::min<uint64_t>(n_rows, kUnionFold);
@@ -553,33 +529,31 @@ extern "C" int gffx_hip_union_add_host(gffx_hip_union *U, const uint32_t *rows, 
     }
     for (uint64_t at = 0; at < n_rows; at += kUnionFold) {
         const uint64_t m = std::min<uint64_t>(kUnionFold, n_rows - at);
-        GFFX_UNION_TRY(union_reserve(U, m));
+        GFFX_KEEP_TRY(U, union_reserve(U, m));
         std::memcpy(U->h_stage, rows + 3 * at, m * 12);  // (the fold below ends with a synchronisation: the buffer is free again)
         GFFX_HIP_TRY(hipMemcpyAsync(U->rec_a + 3 * U->n_spans, U->h_stage, m * 12, hipMemcpyHostToDevice, U->stream));
-        GFFX_UNION_TRY(union_fold(U, m));
+        GFFX_KEEP_TRY(U, union_fold(U, m));
     }
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_union_add_store(gffx_hip_union *U, const gffx_hip_regions *R, int k, uint64_t first, uint64_t n_rows) {
-    int rc = union_enter(U, "gffx_hip_union_add_store");
+    int rc = enter_handle(U, "gffx_hip_union_add_store");
     if (rc) return rc;
-    if (!R || (k != 0 && k != 1)) return fail(GFFX_E_INVALID, "gffx_hip_union_add_store: bad argument");
-    if (R->device != U->device) return fail(GFFX_E_INVALID, "gffx_hip_union_add_store: store and union on different devices");
-    if (first + n_rows > R->last_n[k]) return fail(GFFX_E_INVALID, "gffx_hip_union_add_store: rows beyond the last append");
+    const uint32_t *src = nullptr;
+    if ((rc = store_slot_rows(R, k, first, n_rows, U->device, "gffx_hip_union_add_store", "union", &src))) return rc;
     if (R->pending[k]) GFFX_HIP_TRY(hipStreamWaitEvent(U->stream, R->copied[k], 0));
-    const uint32_t *src = R->d + 3 * (R->last_first[k] + first);
     for (uint64_t at = 0; at < n_rows; at += kUnionFold) {
         const uint64_t m = std::min<uint64_t>(kUnionFold, n_rows - at);
-        GFFX_UNION_TRY(union_reserve(U, m));
+        GFFX_KEEP_TRY(U, union_reserve(U, m));
         GFFX_HIP_TRY(hipMemcpyAsync(U->rec_a + 3 * U->n_spans, src + 3 * at, m * 12, hipMemcpyDeviceToDevice, U->stream));
-        GFFX_UNION_TRY(union_fold(U, m));
+        GFFX_KEEP_TRY(U, union_fold(U, m));
     }
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_union_add_spans(gffx_hip_union *U, const uint64_t *u_off, const uint32_t *us, const uint32_t *ue) {
-    int rc = union_enter(U, "gffx_hip_union_add_spans");
+    int rc = enter_handle(U, "gffx_hip_union_add_spans");
     if (rc) return rc;
     if (!u_off) return fail(GFFX_E_INVALID, "gffx_hip_union_add_spans: u_off is NULL");
     const uint64_t n = u_off[U->n_seq];
@@ -597,7 +571,7 @@ extern "C" int gffx_hip_union_add_spans(gffx_hip_union *U, const uint64_t *u_off
 }
 
 extern "C" int gffx_hip_union_finish(gffx_hip_union *U) {
-    int rc = union_enter(U, "gffx_hip_union_finish");
+    int rc = enter_handle(U, "gffx_hip_union_finish");
     if (rc) return rc;
     if (U->finished) return GFFX_OK;
     const uint32_t n_seq = U->n_seq;
@@ -636,7 +610,7 @@ extern "C" int gffx_hip_union_finish(gffx_hip_union *U) {
             d_off[c + 1] = dir.size();
         }
     }
-    if (i != U->n_spans) return union_fail(U, fail(GFFX_E_HIP, "gffx_hip_union_finish: the spans are not in seqid order"));
+    if (i != U->n_spans) return keep_failure(U, fail(GFFX_E_HIP, "gffx_hip_union_finish: the spans are not in seqid order"));
     auto up = [&](const void *src, size_t bytes, void **dst) -> int {
         GFFX_HIP_TRY(hipMalloc(dst, std::max<size_t>(bytes, 16)));
         if (bytes) GFFX_HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
@@ -647,7 +621,7 @@ extern "C" int gffx_hip_union_finish(gffx_hip_union *U) {
         (rc = up(dir.data(), dir.size() * 4, &U->tables[4])) || (rc = up(d_off.data(), d_off.size() * 8, &U->tables[5])) ||
         (rc = up(d_meta.data(), d_meta.size() * sizeof(uint2), &U->tables[6]))) {
         union_drop_tables(U);
-        return union_fail(U, rc);
+        return keep_failure(U, rc);
     }
     U->finished = true;
     return GFFX_OK;
@@ -656,7 +630,7 @@ extern "C" int gffx_hip_union_finish(gffx_hip_union *U) {
 extern "C" uint64_t gffx_hip_union_n_spans(const gffx_hip_union *U) { return U ? U->n_spans : 0; }
 
 extern "C" int gffx_hip_union_copy_spans(gffx_hip_union *U, uint64_t *u_off, uint32_t *us, uint32_t *ue, uint64_t *pb) {
-    int rc = union_enter(U, "gffx_hip_union_copy_spans");
+    int rc = enter_handle(U, "gffx_hip_union_copy_spans");
     if (rc) return rc;
     if (!U->finished) return fail(GFFX_E_STATE, "gffx_hip_union_copy_spans: call gffx_hip_union_finish first");
     if (u_off) std::copy(U->u_off.begin(), U->u_off.end(), u_off);
@@ -676,7 +650,7 @@ extern "C" int gffx_hip_union_stats(const gffx_hip_union *U, double *kernel_ms, 
 
 extern "C" int gffx_hip_union_segments_covered(gffx_hip_union *U, uint64_t n_seg, const uint32_t *seg_seq, const uint32_t *seg_start,
                                                const uint32_t *seg_end, uint32_t *covered_out) {
-    int rc = union_enter(U, "gffx_hip_union_segments_covered");
+    int rc = enter_handle(U, "gffx_hip_union_segments_covered");
     if (rc) return rc;
     if (!U->finished) return fail(GFFX_E_STATE, "gffx_hip_union_segments_covered: call gffx_hip_union_finish first");
     if (n_seg && (!seg_seq || !seg_start || !seg_end || !covered_out))
@@ -692,7 +666,7 @@ extern "C" int gffx_hip_union_segments_covered(gffx_hip_union *U, uint64_t n_seg
         }
         U->cap_seg = 0;
         for (uint32_t *&p : U->d_seg)
-            if ((rc = union_alloc(&p, n_seg))) return rc;
+            if ((rc = dev_alloc_padded(&p, n_seg))) return rc;
         U->cap_seg = n_seg;
     }
     GFFX_HIP_TRY(hipMemcpyAsync(U->d_seg[0], seg_seq, n_seg * 4, hipMemcpyHostToDevice, U->stream));

@@ -118,8 +118,6 @@ inline int dev_upload(T **p, const std::vector<T> &v) {
     return GFFX_OK;
 }
 
-
-
 }  // namespace gffx
 
 using namespace gffx;

@@ -100,13 +100,12 @@ extern "C" int gffx_hip_regions_append_parts(gffx_hip_regions *R, int k, uint32_
 extern "C" int gffx_hip_batch_set_regions_store(gffx_hip_batch *b, const gffx_hip_regions *R, int k, uint64_t first, uint64_t n_rows) {
     int rc = batch_check_nq(b, n_rows, "gffx_hip_batch_set_regions_store");
     if (rc) return rc;
-    if (!R || (k != 0 && k != 1)) return fail(GFFX_E_INVALID, "gffx_hip_batch_set_regions_store: bad argument");
-    if (R->device != b->ix->device) return fail(GFFX_E_INVALID, "gffx_hip_batch_set_regions_store: store and batch on different devices");
-    if (first + n_rows > R->last_n[k]) return fail(GFFX_E_INVALID, "gffx_hip_batch_set_regions_store: rows beyond the last append");
+    const uint32_t *rows = nullptr;
+    if ((rc = store_slot_rows(R, k, first, n_rows, b->ix->device, "gffx_hip_batch_set_regions_store", "batch", &rows))) return rc;
     GFFX_HIP_TRY(hipSetDevice(R->device));
     if ((rc = batch_own_stream(b))) return rc;
     GFFX_HIP_TRY(hipStreamWaitEvent(b->stream, R->copied[k], 0));
-    b->q = QueryView{R->d + 3 * (R->last_first[k] + first), nullptr, nullptr, nullptr};
+    b->q = QueryView{rows, nullptr, nullptr, nullptr};
     b->nq = n_rows;
     b->have_regions = true;
     {

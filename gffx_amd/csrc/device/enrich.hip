@@ -126,14 +126,14 @@ int perm_run(gffx_hip_classmap *H, const uint32_t *rows, uint64_t nq, uint64_t f
     const uint32_t n_groups = (H->n_perm + 1 + kPermGroup - 1) / kPermGroup;
     const uint64_t tiles = (nq + kClassThreads - 1) / kClassThreads, tiles_per_launch = std::max<uint64_t>(1, H->perm_launch_blocks / n_groups);
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    GFFX_CLASSMAP_TRY(perm_event(H, &e0));
+    GFFX_KEEP_TRY(H, perm_event(H, &e0));
     if (const int rc = perm_event(H, &e1)) {
         H->perm_ev_free.push_back(e0);  // (it stays the object's)
-        return classmap_fail(H, rc);
+        return keep_failure(H, rc);
     }
     H->perm_ev.emplace_back(e0, e1);
-    GFFX_CLASSMAP_HIP(hipMemsetAsync(H->perm_ctl, 0, 4, H->stream));
-    GFFX_CLASSMAP_HIP(hipEventRecord(e0, H->stream));
+    GFFX_KEEP_HIP(H, hipMemsetAsync(H->perm_ctl, 0, 4, H->stream));
+    GFFX_KEEP_HIP(H, hipEventRecord(e0, H->stream));
     hipLaunchKernelGGL(k_classmap_perm_check, dim3((uint32_t)std::min<uint64_t>((nq + kClassThreads - 1) / kClassThreads, kPermCheckBlocks)), dim3(kClassThreads), 0, H->stream, rows, (u64)nq,
                        H->n_seq, H->perm_ctl);
     for (uint64_t t0 = 0; t0 < tiles; t0 += tiles_per_launch) {
@@ -141,8 +141,8 @@ int perm_run(gffx_hip_classmap *H, const uint32_t *rows, uint64_t nq, uint64_t f
         hipLaunchKernelGGL(k_classmap_permute, dim3((uint32_t)(n * n_groups)), dim3(kClassThreads), 0, H->stream, M, rows, (u64)nq, (u64)first_row,
                            (const uint32_t *)H->perm_len, H->n_perm, (u64)H->perm_seed, (u64)t0, n_groups, bases, regions, unplaced, (const uint32_t *)H->perm_ctl);
     }
-    GFFX_CLASSMAP_HIP(hipGetLastError());
-    GFFX_CLASSMAP_HIP(hipEventRecord(e1, H->stream));
+    GFFX_KEEP_HIP(H, hipGetLastError());
+    GFFX_KEEP_HIP(H, hipEventRecord(e1, H->stream));
     return GFFX_OK;
 }
 
@@ -155,7 +155,7 @@ extern "C" int gffx_hip_classmap_perm_begin(gffx_hip_classmap *H, const uint32_t
     if (rc) return rc;
     if (H->n_seq && !seq_len) return fail(GFFX_E_INVALID, "gffx_hip_classmap_perm_begin: seq_len is NULL");
     if (n_perm > enrich::kMaxPerms) return fail(GFFX_E_INVALID, "gffx_hip_classmap_perm_begin: %u permutations (at most %u are possible)", n_perm, enrich::kMaxPerms);
-    GFFX_CLASSMAP_HIP(hipStreamSynchronize(H->stream));  // (no run adds to the totals that go away next)
+    GFFX_KEEP_HIP(H, hipStreamSynchronize(H->stream));  // (no run adds to the totals that go away next)
     classmap_perm_drop(H);
     H->n_perm = n_perm, H->perm_seed = seed;
     H->perm_launch_blocks = kPermMaxBlocks;
@@ -164,13 +164,13 @@ extern "C" int gffx_hip_classmap_perm_begin(gffx_hip_classmap *H, const uint32_t
         if (v >= 1 && (uint64_t)v <= kPermMaxBlocks) H->perm_launch_blocks = (uint64_t)v;
     }
     const uint64_t words = 2 * perm_cells(H) + 1;
-    GFFX_CLASSMAP_TRY(classmap_alloc(&H->perm_totals, words));
-    GFFX_CLASSMAP_TRY(classmap_alloc(&H->perm_len, H->n_seq));
-    GFFX_CLASSMAP_TRY(classmap_alloc(&H->perm_ctl, 2));
-    GFFX_CLASSMAP_HIP(hipMemsetAsync(H->perm_totals, 0, words * 8, H->stream));
-    GFFX_CLASSMAP_HIP(hipMemsetAsync(H->perm_ctl, 0, 8, H->stream));
-    if (H->n_seq) GFFX_CLASSMAP_HIP(hipMemcpyAsync(H->perm_len, seq_len, (size_t)H->n_seq * 4, hipMemcpyHostToDevice, H->stream));
-    GFFX_CLASSMAP_HIP(hipStreamSynchronize(H->stream));  // (the caller's lengths are free)
+    GFFX_KEEP_TRY(H, dev_alloc_padded(&H->perm_totals, words));
+    GFFX_KEEP_TRY(H, dev_alloc_padded(&H->perm_len, H->n_seq));
+    GFFX_KEEP_TRY(H, dev_alloc_padded(&H->perm_ctl, 2));
+    GFFX_KEEP_HIP(H, hipMemsetAsync(H->perm_totals, 0, words * 8, H->stream));
+    GFFX_KEEP_HIP(H, hipMemsetAsync(H->perm_ctl, 0, 8, H->stream));
+    if (H->n_seq) GFFX_KEEP_HIP(H, hipMemcpyAsync(H->perm_len, seq_len, (size_t)H->n_seq * 4, hipMemcpyHostToDevice, H->stream));
+    GFFX_KEEP_HIP(H, hipStreamSynchronize(H->stream));  // (the caller's lengths are free)
     H->perm_open = H->perm_waited = true;
     return GFFX_OK;
 }
@@ -181,9 +181,9 @@ extern "C" int gffx_hip_classmap_perm_run_host(gffx_hip_classmap *H, const uint3
     if (nq && !regions) return fail(GFFX_E_INVALID, "gffx_hip_classmap_perm_run_host: regions is NULL");
     if (nq) {
         // (growing frees the old array, which waits for the device: an earlier run has read it by then)
-        GFFX_CLASSMAP_TRY(classmap_ensure(H->perm_regions, 3 * nq, "the regions"));
-        GFFX_CLASSMAP_HIP(hipMemcpyAsync(H->perm_regions.p, regions, nq * 12, hipMemcpyHostToDevice, H->stream));
-        GFFX_CLASSMAP_HIP(hipStreamSynchronize(H->stream));  // (the caller's array is free; the kernels below are not waited for)
+        GFFX_KEEP_TRY(H, classmap_ensure(H->perm_regions, 3 * nq, "the regions"));
+        GFFX_KEEP_HIP(H, hipMemcpyAsync(H->perm_regions.p, regions, nq * 12, hipMemcpyHostToDevice, H->stream));
+        GFFX_KEEP_HIP(H, hipStreamSynchronize(H->stream));  // (the caller's array is free; the kernels below are not waited for)
     }
     return perm_run(H, H->perm_regions.p, nq, first_row);
 }
@@ -191,11 +191,10 @@ extern "C" int gffx_hip_classmap_perm_run_host(gffx_hip_classmap *H, const uint3
 extern "C" int gffx_hip_classmap_perm_run_store(gffx_hip_classmap *H, const gffx_hip_regions *R, int k, uint64_t first, uint64_t n_rows, uint64_t first_row) {
     const int rc = perm_ready(H, "gffx_hip_classmap_perm_run_store");
     if (rc) return rc;
-    if (!R || (k != 0 && k != 1)) return fail(GFFX_E_INVALID, "gffx_hip_classmap_perm_run_store: bad argument");
-    if (R->device != H->device) return fail(GFFX_E_INVALID, "gffx_hip_classmap_perm_run_store: store and class map on different devices");
-    if (first + n_rows > R->last_n[k]) return fail(GFFX_E_INVALID, "gffx_hip_classmap_perm_run_store: rows beyond the last append");
-    if (R->pending[k]) GFFX_CLASSMAP_HIP(hipStreamWaitEvent(H->stream, R->copied[k], 0));
-    return perm_run(H, R->d + 3 * (R->last_first[k] + first), n_rows, first_row);  // (the slot is read in place: _perm_wait before it is appended to again)
+    const uint32_t *rows = nullptr;
+    if (const int bad = store_slot_rows(R, k, first, n_rows, H->device, "gffx_hip_classmap_perm_run_store", "class map", &rows)) return bad;
+    if (R->pending[k]) GFFX_KEEP_HIP(H, hipStreamWaitEvent(H->stream, R->copied[k], 0));
+    return perm_run(H, rows, n_rows, first_row);  // (the slot is read in place: _perm_wait before it is appended to again)
 }
 
 extern "C" int gffx_hip_classmap_perm_wait(gffx_hip_classmap *H) {
@@ -203,8 +202,8 @@ extern "C" int gffx_hip_classmap_perm_wait(gffx_hip_classmap *H) {
     if (rc) return rc;
     if (H->perm_waited) return GFFX_OK;
     uint32_t ctl[2] = {0, 0};
-    GFFX_CLASSMAP_HIP(hipMemcpyAsync(ctl, H->perm_ctl, 8, hipMemcpyDeviceToHost, H->stream));
-    GFFX_CLASSMAP_HIP(hipStreamSynchronize(H->stream));
+    GFFX_KEEP_HIP(H, hipMemcpyAsync(ctl, H->perm_ctl, 8, hipMemcpyDeviceToHost, H->stream));
+    GFFX_KEEP_HIP(H, hipStreamSynchronize(H->stream));
     H->perm_kernel_ms = 0;
     for (auto &pr : H->perm_ev) {
         float ms = 0.f;
@@ -214,8 +213,8 @@ extern "C" int gffx_hip_classmap_perm_wait(gffx_hip_classmap *H) {
     H->perm_ev.clear();
     H->perm_waited = true;
     if (ctl[1]) {
-        GFFX_CLASSMAP_HIP(hipMemsetAsync(H->perm_ctl, 0, 8, H->stream));
-        GFFX_CLASSMAP_HIP(hipStreamSynchronize(H->stream));
+        GFFX_KEEP_HIP(H, hipMemsetAsync(H->perm_ctl, 0, 8, H->stream));
+        GFFX_KEEP_HIP(H, hipStreamSynchronize(H->stream));
         // (the runs with such a row added nothing; the others stand, and the object stays usable)
         return fail(GFFX_E_CHR_RANGE, "gffx_hip_classmap_perm_wait: a region has chr >= %u: its run is void", H->n_seq);
     }
@@ -227,9 +226,9 @@ extern "C" int gffx_hip_classmap_perm_copy_totals(gffx_hip_classmap *H, uint64_t
     if (rc) return rc;
     if (!H->perm_waited) return fail(GFFX_E_STATE, "gffx_hip_classmap_perm_copy_totals: call gffx_hip_classmap_perm_wait first");
     const uint64_t cells = perm_cells(H);
-    if (bases) GFFX_CLASSMAP_HIP(hipMemcpy(bases, H->perm_totals, cells * 8, hipMemcpyDeviceToHost));
-    if (regions) GFFX_CLASSMAP_HIP(hipMemcpy(regions, H->perm_totals + cells, cells * 8, hipMemcpyDeviceToHost));
-    if (unplaced) GFFX_CLASSMAP_HIP(hipMemcpy(unplaced, H->perm_totals + 2 * cells, 8, hipMemcpyDeviceToHost));
+    if (bases) GFFX_KEEP_HIP(H, hipMemcpy(bases, H->perm_totals, cells * 8, hipMemcpyDeviceToHost));
+    if (regions) GFFX_KEEP_HIP(H, hipMemcpy(regions, H->perm_totals + cells, cells * 8, hipMemcpyDeviceToHost));
+    if (unplaced) GFFX_KEEP_HIP(H, hipMemcpy(unplaced, H->perm_totals + 2 * cells, 8, hipMemcpyDeviceToHost));
     return GFFX_OK;
 }
 

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "gffx_device.hpp"
+#include "handle_status.hpp"
 #include "meta_core.hpp"
 #include "pileup_core.hpp"
 #include "radix_sort.hpp"
@@ -292,12 +293,10 @@ __global__ __launch_bounds__(kPileupThreads) void k_pileup_meta_geometry(uint32_
 
 using namespace gffx;
 
-struct gffx_hip_pileup {
-    int device = 0;
+struct gffx_hip_pileup : gffx::HandleStatus {
+    static constexpr const char *kName = "pileup", *kNoun = "pileup";
     uint32_t n_seq = 0;
     uint64_t n_seg = 0;
-    int status = GFFX_OK;  // the first error: the object only reports it again
-    std::string message;
     hipStream_t stream = nullptr;
     // two folds in flight, each: 0 start, 1 keys done, 2 sorts start (the host looked at the error word in between), 3 sorts done,
     // 4 scan done, 5 segments done, 6 the error word is on the host, 7 the meta kernel done (recorded between 5 and 6)
@@ -336,34 +335,6 @@ struct gffx_hip_pileup {
 
 namespace {
 
-int pileup_fail(gffx_hip_pileup *P, int rc) {  // rc came from fail(): keep it and its message
-    if (P->status == GFFX_OK) P->status = rc, P->message = g_last_error;
-    return rc;
-}
-#define GFFX_PILEUP_TRY(expr)                  \
-    do {                                       \
-        const int _rc = (expr);                \
-        if (_rc) return pileup_fail(P, _rc);   \
-    } while (0)
-
-// a HIP call of an entry point that works on the handle: its failure, too, is kept (argument errors are not: the call is
-// refused and the handle stays usable)
-#define GFFX_PILEUP_HIP(expr) GFFX_PILEUP_TRY([&]() -> int { GFFX_HIP_TRY(expr); return GFFX_OK; }())
-
-int pileup_enter(const gffx_hip_pileup *P, const char *who) {
-    if (!P) return fail(GFFX_E_INVALID, "%s: pileup is NULL", who);
-    if (P->status != GFFX_OK) return fail(P->status, "%s: the pileup failed earlier: %s", who, P->message.c_str());
-    GFFX_HIP_TRY(hipSetDevice(P->device));
-    return GFFX_OK;
-}
-
-template <typename T>
-int pileup_alloc(T **p, uint64_t n) {
-    *p = nullptr;
-    GFFX_HIP_TRY(hipMalloc((void **)p, std::max<uint64_t>(n, 4) * sizeof(T)));
-    return GFFX_OK;
-}
-
 // the fold behind event set j is through: its stage times, and what the sort said
 int pileup_collect(gffx_hip_pileup *P, int j) {
     if (!P->pending[j]) return GFFX_OK;
@@ -397,10 +368,10 @@ int pileup_reserve(gffx_hip_pileup *P, uint64_t m) {
         const uint64_t tiles = (cap + kPileupScanTile - 1) / kPileupScanTile;
         const uint64_t work = DeviceSort::work_words(cap, P->plan.n_passes);
         for (int k = 0; k < 2; ++k)
-            if ((rc = pileup_alloc(&P->ks[k], 2 * cap)) || (rc = pileup_alloc(&P->ke[k], 2 * cap)) || (rc = pileup_alloc(&P->co[k], cap)) ||
-                (rc = pileup_alloc(&P->pre[k], cap + 1)))
+            if ((rc = dev_alloc_padded(&P->ks[k], 2 * cap)) || (rc = dev_alloc_padded(&P->ke[k], 2 * cap)) || (rc = dev_alloc_padded(&P->co[k], cap)) ||
+                (rc = dev_alloc_padded(&P->pre[k], cap + 1)))
                 return rc;
-        if ((rc = pileup_alloc(&P->tile_sum, 2 * tiles)) || (rc = pileup_alloc(&P->work, work))) return rc;
+        if ((rc = dev_alloc_padded(&P->tile_sum, 2 * tiles)) || (rc = dev_alloc_padded(&P->work, work))) return rc;
         P->cap = cap, P->cap_work = work, P->cap_tiles = tiles;
     }
     return GFFX_OK;
@@ -553,9 +524,9 @@ extern "C" int gffx_hip_pileup_create(int device, uint32_t n_seq, uint64_t n_seg
     GFFX_HIP_TRY(hipHostMalloc((void **)&P->h_ctl, 3 * 32, hipHostMallocDefault));
     std::memset(P->h_ctl, 0, 3 * 32);
     int rc;
-    if ((rc = pileup_alloc(&P->ctl, 8)) || (rc = pileup_alloc(&P->off, (uint64_t)n_seq + 1)) || (rc = pileup_alloc(&P->d_acc, n_seg))) return rc;
+    if ((rc = dev_alloc_padded(&P->ctl, 8)) || (rc = dev_alloc_padded(&P->off, (uint64_t)n_seq + 1)) || (rc = dev_alloc_padded(&P->d_acc, n_seg))) return rc;
     for (uint32_t *&p : P->d_seg)
-        if ((rc = pileup_alloc(&p, n_seg))) return rc;
+        if ((rc = dev_alloc_padded(&p, n_seg))) return rc;
     GFFX_HIP_TRY(hipMemsetAsync(P->d_acc, 0, std::max<uint64_t>(n_seg, 4) * 8, P->stream));
     if (n_seg) {
         GFFX_HIP_TRY(hipMemcpyAsync(P->d_seg[0], seg_seq, n_seg * 4, hipMemcpyHostToDevice, P->stream));
@@ -568,7 +539,7 @@ extern "C" int gffx_hip_pileup_create(int device, uint32_t n_seq, uint64_t n_seg
 }
 
 extern "C" int gffx_hip_pileup_add_host(gffx_hip_pileup *P, const uint32_t *rows, uint64_t n_rows) {
-    int rc = pileup_enter(P, "gffx_hip_pileup_add_host");
+    int rc = enter_handle(P, "gffx_hip_pileup_add_host");
     if (rc) return rc;
     if (n_rows && !rows) return fail(GFFX_E_INVALID, "gffx_hip_pileup_add_host: rows is NULL");
     const uint64_t want = std::min<uint64_t>(n_rows, kPileupFold);
@@ -577,65 +548,63 @@ extern "C" int gffx_hip_pileup_add_host(gffx_hip_pileup *P, const uint32_t *rows
         P->h_stage = nullptr, P->cap_stage = 0;
         hipError_t e = hipHostMalloc((void **)&P->h_stage, want * 12, hipHostMallocDefault);
         if (e != hipSuccess)
-            return pileup_fail(P, fail(GFFX_E_OOM, "hipHostMalloc of a %llu-row staging buffer failed: %s", (unsigned long long)want, hipGetErrorString(e)));
+            return keep_failure(P, fail(GFFX_E_OOM, "hipHostMalloc of a %llu-row staging buffer failed: %s", (unsigned long long)want, hipGetErrorString(e)));
         P->cap_stage = want;
     }
     if (want > P->cap_rows) {
-        GFFX_PILEUP_HIP(hipStreamSynchronize(P->stream));
-        if (P->d_rows) GFFX_PILEUP_HIP(hipFree(P->d_rows));
+        GFFX_KEEP_HIP(P, hipStreamSynchronize(P->stream));
+        if (P->d_rows) GFFX_KEEP_HIP(P, hipFree(P->d_rows));
         P->d_rows = nullptr, P->cap_rows = 0;
-        GFFX_PILEUP_TRY(pileup_alloc(&P->d_rows, 3 * want));
+        GFFX_KEEP_TRY(P, dev_alloc_padded(&P->d_rows, 3 * want));
         P->cap_rows = want;
     }
     for (uint64_t at = 0; at < n_rows; at += kPileupFold) {
         const uint64_t m = std::min<uint64_t>(kPileupFold, n_rows - at);
-        GFFX_PILEUP_TRY(pileup_reserve(P, m));
+        GFFX_KEEP_TRY(P, pileup_reserve(P, m));
         std::memcpy(P->h_stage, rows + 3 * at, m * 12);  // (a fold returns after its rows were read: the buffer is free again)
-        GFFX_PILEUP_HIP(hipMemcpyAsync(P->d_rows, P->h_stage, m * 12, hipMemcpyHostToDevice, P->stream));
-        GFFX_PILEUP_TRY(pileup_fold(P, P->d_rows, m));
+        GFFX_KEEP_HIP(P, hipMemcpyAsync(P->d_rows, P->h_stage, m * 12, hipMemcpyHostToDevice, P->stream));
+        GFFX_KEEP_TRY(P, pileup_fold(P, P->d_rows, m));
     }
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_pileup_add_store(gffx_hip_pileup *P, const gffx_hip_regions *R, int k, uint64_t first, uint64_t n_rows) {
-    int rc = pileup_enter(P, "gffx_hip_pileup_add_store");
+    int rc = enter_handle(P, "gffx_hip_pileup_add_store");
     if (rc) return rc;
-    if (!R || (k != 0 && k != 1)) return fail(GFFX_E_INVALID, "gffx_hip_pileup_add_store: bad argument");
-    if (R->device != P->device) return fail(GFFX_E_INVALID, "gffx_hip_pileup_add_store: store and pileup on different devices");
-    if (first + n_rows > R->last_n[k]) return fail(GFFX_E_INVALID, "gffx_hip_pileup_add_store: rows beyond the last append");
-    if (R->pending[k]) GFFX_PILEUP_HIP(hipStreamWaitEvent(P->stream, R->copied[k], 0));
-    const uint32_t *src = R->d + 3 * (R->last_first[k] + first);
+    const uint32_t *src = nullptr;
+    if ((rc = store_slot_rows(R, k, first, n_rows, P->device, "gffx_hip_pileup_add_store", "pileup", &src))) return rc;
+    if (R->pending[k]) GFFX_KEEP_HIP(P, hipStreamWaitEvent(P->stream, R->copied[k], 0));
     for (uint64_t at = 0; at < n_rows; at += kPileupFold) {
         const uint64_t m = std::min<uint64_t>(kPileupFold, n_rows - at);
-        GFFX_PILEUP_TRY(pileup_reserve(P, m));
-        GFFX_PILEUP_TRY(pileup_fold(P, src + 3 * at, m));  // (the slot is read in place: no copy)
+        GFFX_KEEP_TRY(P, pileup_reserve(P, m));
+        GFFX_KEEP_TRY(P, pileup_fold(P, src + 3 * at, m));  // (the slot is read in place: no copy)
     }
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_pileup_copy(gffx_hip_pileup *P, uint64_t *bases) {
-    int rc = pileup_enter(P, "gffx_hip_pileup_copy");
+    int rc = enter_handle(P, "gffx_hip_pileup_copy");
     if (rc) return rc;
     if (P->n_seg && !bases) return fail(GFFX_E_INVALID, "gffx_hip_pileup_copy: bases is NULL");
-    GFFX_PILEUP_TRY(pileup_drain(P));
-    if (P->n_seg) GFFX_PILEUP_HIP(hipMemcpy(bases, P->d_acc, P->n_seg * 8, hipMemcpyDeviceToHost));
+    GFFX_KEEP_TRY(P, pileup_drain(P));
+    if (P->n_seg) GFFX_KEEP_HIP(P, hipMemcpy(bases, P->d_acc, P->n_seg * 8, hipMemcpyDeviceToHost));
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_pileup_reset(gffx_hip_pileup *P) {
-    int rc = pileup_enter(P, "gffx_hip_pileup_reset");
+    int rc = enter_handle(P, "gffx_hip_pileup_reset");
     if (rc) return rc;
-    GFFX_PILEUP_HIP(hipMemsetAsync(P->d_acc, 0, std::max<uint64_t>(P->n_seg, 4) * 8, P->stream));  // (behind the folds enqueued so far)
+    GFFX_KEEP_HIP(P, hipMemsetAsync(P->d_acc, 0, std::max<uint64_t>(P->n_seg, 4) * 8, P->stream));  // (behind the folds enqueued so far)
     if (P->meta) {  // the column totals and the matrix; length and features are the features' own and stay
-        GFFX_PILEUP_HIP(hipMemsetAsync(P->d_col, 0, (size_t)P->meta_cols * 8, P->stream));
-        if (P->meta_matrix) GFFX_PILEUP_HIP(hipMemsetAsync(P->d_matrix, 0, std::max<uint64_t>(P->n_feat * P->meta_cols, 4) * 8, P->stream));
+        GFFX_KEEP_HIP(P, hipMemsetAsync(P->d_col, 0, (size_t)P->meta_cols * 8, P->stream));
+        if (P->meta_matrix) GFFX_KEEP_HIP(P, hipMemsetAsync(P->d_matrix, 0, std::max<uint64_t>(P->n_feat * P->meta_cols, 4) * 8, P->stream));
     }
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_pileup_meta_set(gffx_hip_pileup *P, uint64_t n_feat, const uint32_t *feat_seq, const uint32_t *feat_start, const uint32_t *feat_end,
                                         const uint8_t *feat_minus, const uint32_t *seq_len, const gffx_hip_meta_layout *layout, int keep_matrix) {
-    int rc = pileup_enter(P, "gffx_hip_pileup_meta_set");
+    int rc = enter_handle(P, "gffx_hip_pileup_meta_set");
     if (rc) return rc;
     if (!layout) return fail(GFFX_E_INVALID, "gffx_hip_pileup_meta_set: layout is NULL");
     if (n_feat && (!feat_seq || !feat_start || !feat_end || !feat_minus)) return fail(GFFX_E_INVALID, "gffx_hip_pileup_meta_set: NULL feature array");
@@ -651,45 +620,45 @@ extern "C" int gffx_hip_pileup_meta_set(gffx_hip_pileup *P, uint64_t n_feat, con
             return fail(GFFX_E_INVALID, "gffx_hip_pileup_meta_set: feature %llu has chr %u >= %u", (unsigned long long)i, feat_seq[i], P->n_seq);
         if (feat_start[i] >= feat_end[i]) return fail(GFFX_E_INVALID, "gffx_hip_pileup_meta_set: feature %llu has start >= end", (unsigned long long)i);
     }
-    GFFX_PILEUP_TRY(pileup_drain(P));  // (folds in flight read the features that are replaced here)
+    GFFX_KEEP_TRY(P, pileup_drain(P));  // (folds in flight read the features that are replaced here)
     pileup_meta_free(P);
-    for (uint32_t *&p : P->d_feat) GFFX_PILEUP_TRY(pileup_alloc(&p, n_feat));
-    GFFX_PILEUP_TRY(pileup_alloc(&P->d_feat_minus, n_feat));
-    GFFX_PILEUP_TRY(pileup_alloc(&P->d_col, 3 * B));
-    if (seq_len) GFFX_PILEUP_TRY(pileup_alloc(&P->d_seq_len, (uint64_t)P->n_seq));
-    if (keep_matrix) GFFX_PILEUP_TRY(pileup_alloc(&P->d_matrix, n_feat * B));
+    for (uint32_t *&p : P->d_feat) GFFX_KEEP_TRY(P, dev_alloc_padded(&p, n_feat));
+    GFFX_KEEP_TRY(P, dev_alloc_padded(&P->d_feat_minus, n_feat));
+    GFFX_KEEP_TRY(P, dev_alloc_padded(&P->d_col, 3 * B));
+    if (seq_len) GFFX_KEEP_TRY(P, dev_alloc_padded(&P->d_seq_len, (uint64_t)P->n_seq));
+    if (keep_matrix) GFFX_KEEP_TRY(P, dev_alloc_padded(&P->d_matrix, n_feat * B));
     if (n_feat) {
-        GFFX_PILEUP_HIP(hipMemcpyAsync(P->d_feat[0], feat_seq, n_feat * 4, hipMemcpyHostToDevice, P->stream));
-        GFFX_PILEUP_HIP(hipMemcpyAsync(P->d_feat[1], feat_start, n_feat * 4, hipMemcpyHostToDevice, P->stream));
-        GFFX_PILEUP_HIP(hipMemcpyAsync(P->d_feat[2], feat_end, n_feat * 4, hipMemcpyHostToDevice, P->stream));
-        GFFX_PILEUP_HIP(hipMemcpyAsync(P->d_feat_minus, feat_minus, n_feat, hipMemcpyHostToDevice, P->stream));
+        GFFX_KEEP_HIP(P, hipMemcpyAsync(P->d_feat[0], feat_seq, n_feat * 4, hipMemcpyHostToDevice, P->stream));
+        GFFX_KEEP_HIP(P, hipMemcpyAsync(P->d_feat[1], feat_start, n_feat * 4, hipMemcpyHostToDevice, P->stream));
+        GFFX_KEEP_HIP(P, hipMemcpyAsync(P->d_feat[2], feat_end, n_feat * 4, hipMemcpyHostToDevice, P->stream));
+        GFFX_KEEP_HIP(P, hipMemcpyAsync(P->d_feat_minus, feat_minus, n_feat, hipMemcpyHostToDevice, P->stream));
     }
-    if (seq_len && P->n_seq) GFFX_PILEUP_HIP(hipMemcpyAsync(P->d_seq_len, seq_len, (size_t)P->n_seq * 4, hipMemcpyHostToDevice, P->stream));
-    GFFX_PILEUP_HIP(hipMemsetAsync(P->d_col, 0, std::max<uint64_t>(3 * B, 4) * 8, P->stream));
-    if (keep_matrix) GFFX_PILEUP_HIP(hipMemsetAsync(P->d_matrix, 0, std::max<uint64_t>(n_feat * B, 4) * 8, P->stream));
+    if (seq_len && P->n_seq) GFFX_KEEP_HIP(P, hipMemcpyAsync(P->d_seq_len, seq_len, (size_t)P->n_seq * 4, hipMemcpyHostToDevice, P->stream));
+    GFFX_KEEP_HIP(P, hipMemsetAsync(P->d_col, 0, std::max<uint64_t>(3 * B, 4) * 8, P->stream));
+    if (keep_matrix) GFFX_KEEP_HIP(P, hipMemsetAsync(P->d_matrix, 0, std::max<uint64_t>(n_feat * B, 4) * 8, P->stream));
     if (n_feat) {
         const MetaFeatures F{P->d_feat[0], P->d_feat[1], P->d_feat[2], P->d_feat_minus, P->d_seq_len, (u64)n_feat};
         hipLaunchKernelGGL(k_pileup_meta_geometry, dim3((uint32_t)((n_feat + kMetaGeometrySlice - 1) / kMetaGeometrySlice), (uint32_t)((B + kPileupThreads - 1) / kPileupThreads)),
                            dim3(kPileupThreads), 0, P->stream, P->n_seq, F, lay, (uint32_t)B, P->d_col + B, P->d_col + 2 * B);
-        GFFX_PILEUP_HIP(hipGetLastError());
+        GFFX_KEEP_HIP(P, hipGetLastError());
     }
-    GFFX_PILEUP_HIP(hipStreamSynchronize(P->stream));  // (the caller's arrays are free again)
+    GFFX_KEEP_HIP(P, hipStreamSynchronize(P->stream));  // (the caller's arrays are free again)
     P->meta = true, P->meta_matrix = keep_matrix != 0;
     P->n_feat = n_feat, P->meta_cols = (uint32_t)B, P->meta_layout = lay;
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_pileup_meta_copy(gffx_hip_pileup *P, uint64_t *col_bases, uint64_t *col_len, uint64_t *col_features, uint64_t *matrix) {
-    int rc = pileup_enter(P, "gffx_hip_pileup_meta_copy");
+    int rc = enter_handle(P, "gffx_hip_pileup_meta_copy");
     if (rc) return rc;
     if (!P->meta) return fail(GFFX_E_INVALID, "gffx_hip_pileup_meta_copy: the pileup has no features (gffx_hip_pileup_meta_set)");
     if (matrix && !P->meta_matrix) return fail(GFFX_E_INVALID, "gffx_hip_pileup_meta_copy: the matrix was not kept");
-    GFFX_PILEUP_TRY(pileup_drain(P));
+    GFFX_KEEP_TRY(P, pileup_drain(P));
     const size_t B = P->meta_cols;
-    if (col_bases) GFFX_PILEUP_HIP(hipMemcpy(col_bases, P->d_col, B * 8, hipMemcpyDeviceToHost));
-    if (col_len) GFFX_PILEUP_HIP(hipMemcpy(col_len, P->d_col + B, B * 8, hipMemcpyDeviceToHost));
-    if (col_features) GFFX_PILEUP_HIP(hipMemcpy(col_features, P->d_col + 2 * B, B * 8, hipMemcpyDeviceToHost));
-    if (matrix && P->n_feat) GFFX_PILEUP_HIP(hipMemcpy(matrix, P->d_matrix, P->n_feat * B * 8, hipMemcpyDeviceToHost));
+    if (col_bases) GFFX_KEEP_HIP(P, hipMemcpy(col_bases, P->d_col, B * 8, hipMemcpyDeviceToHost));
+    if (col_len) GFFX_KEEP_HIP(P, hipMemcpy(col_len, P->d_col + B, B * 8, hipMemcpyDeviceToHost));
+    if (col_features) GFFX_KEEP_HIP(P, hipMemcpy(col_features, P->d_col + 2 * B, B * 8, hipMemcpyDeviceToHost));
+    if (matrix && P->n_feat) GFFX_KEEP_HIP(P, hipMemcpy(matrix, P->d_matrix, P->n_feat * B * 8, hipMemcpyDeviceToHost));
     return GFFX_OK;
 }
 
@@ -707,8 +676,8 @@ extern "C" int gffx_hip_pileup_stage_ms(const gffx_hip_pileup *Pc, double *keys,
     if (!Pc) return fail(GFFX_E_INVALID, "gffx_hip_pileup_stage_ms: pileup is NULL");
     gffx_hip_pileup *P = const_cast<gffx_hip_pileup *>(Pc);
     if (P->status == GFFX_OK && (P->pending[0] || P->pending[1])) {
-        GFFX_PILEUP_HIP(hipSetDevice(P->device));
-        GFFX_PILEUP_TRY(pileup_drain(P));
+        GFFX_KEEP_HIP(P, hipSetDevice(P->device));
+        GFFX_KEEP_TRY(P, pileup_drain(P));
     }
     if (keys) *keys = P->stage_ms[0];
     if (sorts) *sorts = P->stage_ms[1];

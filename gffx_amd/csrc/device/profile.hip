@@ -339,11 +339,9 @@ __global__ __launch_bounds__(kProfileThreads) void k_profile_spans(const uint32_
 
 using namespace gffx;
 
-struct gffx_hip_profile {
-    int device = 0;
+struct gffx_hip_profile : gffx::HandleStatus {
+    static constexpr const char *kName = "profile", *kNoun = "profile";
     uint32_t n_seq = 0;
-    int status = GFFX_OK;  // the first error: the object only reports it again
-    std::string message;
     hipStream_t stream = nullptr;
     // the fold in flight: 0 start, 1 events done, 2 sort starts (the host looked at the error word in between), 3 sort done,
     // 4 running depth done, 5 points done, 6 the error word and the point count are on the host
@@ -373,34 +371,6 @@ struct gffx_hip_profile {
 
 namespace {
 
-int profile_fail(gffx_hip_profile *P, int rc) {  // rc came from fail(): keep it and its message
-    if (P->status == GFFX_OK) P->status = rc, P->message = g_last_error;
-    return rc;
-}
-#define GFFX_PROFILE_TRY(expr)                 \
-    do {                                       \
-        const int _rc = (expr);                \
-        if (_rc) return profile_fail(P, _rc);  \
-    } while (0)
-
-// a HIP call of an entry point that works on the handle: its failure, too, is kept (argument errors are not: the call is
-// refused and the handle stays usable)
-#define GFFX_PROFILE_HIP(expr) GFFX_PROFILE_TRY([&]() -> int { GFFX_HIP_TRY(expr); return GFFX_OK; }())
-
-int profile_enter(const gffx_hip_profile *P, const char *who) {
-    if (!P) return fail(GFFX_E_INVALID, "%s: profile is NULL", who);
-    if (P->status != GFFX_OK) return fail(P->status, "%s: the profile failed earlier: %s", who, P->message.c_str());
-    GFFX_HIP_TRY(hipSetDevice(P->device));
-    return GFFX_OK;
-}
-
-template <typename T>
-int profile_alloc(T **p, uint64_t n) {
-    *p = nullptr;
-    GFFX_HIP_TRY(hipMalloc((void **)p, std::max<uint64_t>(n, 4) * sizeof(T)));
-    return GFFX_OK;
-}
-
 // the fold in flight is through: its stage times, what the sort said, and how many points there are now
 int profile_collect(gffx_hip_profile *P) {
     if (!P->pending) return GFFX_OK;
@@ -426,8 +396,8 @@ int profile_reserve(gffx_hip_profile *P, uint64_t need) {
     if (need > P->cap) {
         const uint64_t cap = std::min<uint64_t>(need + need / 4 + 1024, 1ull << 30);
         uint32_t *a = nullptr, *b = nullptr;
-        if ((rc = profile_alloc(&a, 3 * cap))) return rc;
-        if ((rc = profile_alloc(&b, 3 * cap))) {
+        if ((rc = dev_alloc_padded(&a, 3 * cap))) return rc;
+        if ((rc = dev_alloc_padded(&b, 3 * cap))) {
             (void)hipFree(a);
             return rc;
         }
@@ -448,7 +418,7 @@ int profile_reserve(gffx_hip_profile *P, uint64_t need) {
         GFFX_HIP_TRY(hipStreamSynchronize(P->stream));
         if (P->work) GFFX_HIP_TRY(hipFree(P->work));
         P->work = nullptr, P->cap_work = 0;
-        if ((rc = profile_alloc(&P->work, want_work))) return rc;
+        if ((rc = dev_alloc_padded(&P->work, want_work))) return rc;
         P->cap_work = want_work;
     }
     if (want_tiles > P->cap_tiles) {
@@ -459,7 +429,7 @@ int profile_reserve(gffx_hip_profile *P, uint64_t need) {
         }
         P->cap_tiles = 0;
         for (u64 *&p : P->tile)
-            if ((rc = profile_alloc(&p, want_tiles))) return rc;
+            if ((rc = dev_alloc_padded(&p, want_tiles))) return rc;
         P->cap_tiles = want_tiles;
     }
     return GFFX_OK;
@@ -470,7 +440,7 @@ int profile_rows_room(gffx_hip_profile *P, uint64_t want) {  // d_rows for `want
     GFFX_HIP_TRY(hipStreamSynchronize(P->stream));
     if (P->d_rows) GFFX_HIP_TRY(hipFree(P->d_rows));
     P->d_rows = nullptr, P->cap_rows = 0;
-    const int rc = profile_alloc(&P->d_rows, 3 * want);
+    const int rc = dev_alloc_padded(&P->d_rows, 3 * want);
     if (rc) return rc;
     P->cap_rows = want;
     return GFFX_OK;
@@ -591,13 +561,13 @@ extern "C" int gffx_hip_profile_create(int device, uint32_t n_seq, gffx_hip_prof
     GFFX_HIP_TRY(hipHostMalloc((void **)&P->h_ctl, 2 * 32, hipHostMallocDefault));
     std::memset(P->h_ctl, 0, 2 * 32);
     int rc;
-    if ((rc = profile_alloc(&P->ctl, 8)) || (rc = profile_alloc(&P->d_poff, (uint64_t)n_seq + 1))) return rc;
+    if ((rc = dev_alloc_padded(&P->ctl, 8)) || (rc = dev_alloc_padded(&P->d_poff, (uint64_t)n_seq + 1))) return rc;
     *out = P.release();
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_profile_add_host(gffx_hip_profile *P, const uint32_t *rows, uint64_t n_rows) {
-    int rc = profile_enter(P, "gffx_hip_profile_add_host");
+    int rc = enter_handle(P, "gffx_hip_profile_add_host");
     if (rc) return rc;
     if (n_rows && !rows) return fail(GFFX_E_INVALID, "gffx_hip_profile_add_host: rows is NULL");
     if ((rc = profile_budget(P, n_rows, "gffx_hip_profile_add_host"))) return rc;
@@ -607,51 +577,49 @@ extern "C" int gffx_hip_profile_add_host(gffx_hip_profile *P, const uint32_t *ro
         P->h_stage = nullptr, P->cap_stage = 0;
         hipError_t e = hipHostMalloc((void **)&P->h_stage, want * 12, hipHostMallocDefault);
         if (e != hipSuccess)
-            return profile_fail(P, fail(GFFX_E_OOM, "hipHostMalloc of a %llu-row staging buffer failed: %s", (unsigned long long)want, hipGetErrorString(e)));
+            return keep_failure(P, fail(GFFX_E_OOM, "hipHostMalloc of a %llu-row staging buffer failed: %s", (unsigned long long)want, hipGetErrorString(e)));
         P->cap_stage = want;
     }
-    GFFX_PROFILE_TRY(profile_rows_room(P, want));
+    GFFX_KEEP_TRY(P, profile_rows_room(P, want));
     for (uint64_t at = 0; at < n_rows; at += kProfileFold) {
         const uint64_t m = std::min<uint64_t>(kProfileFold, n_rows - at);
-        GFFX_PROFILE_TRY(profile_collect(P));
-        GFFX_PROFILE_TRY(profile_reserve(P, P->n_points + 2 * m));
+        GFFX_KEEP_TRY(P, profile_collect(P));
+        GFFX_KEEP_TRY(P, profile_reserve(P, P->n_points + 2 * m));
         std::memcpy(P->h_stage, rows + 3 * at, m * 12);  // (a fold returns after its rows were read: the buffer is free again)
-        GFFX_PROFILE_HIP(hipMemcpyAsync(P->d_rows, P->h_stage, m * 12, hipMemcpyHostToDevice, P->stream));
-        GFFX_PROFILE_TRY(profile_fold(P, P->d_rows, m, nullptr, 0));
+        GFFX_KEEP_HIP(P, hipMemcpyAsync(P->d_rows, P->h_stage, m * 12, hipMemcpyHostToDevice, P->stream));
+        GFFX_KEEP_TRY(P, profile_fold(P, P->d_rows, m, nullptr, 0));
         P->budget += m;
     }
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_profile_add_store(gffx_hip_profile *P, const gffx_hip_regions *R, int k, uint64_t first, uint64_t n_rows) {
-    int rc = profile_enter(P, "gffx_hip_profile_add_store");
+    int rc = enter_handle(P, "gffx_hip_profile_add_store");
     if (rc) return rc;
-    if (!R || (k != 0 && k != 1)) return fail(GFFX_E_INVALID, "gffx_hip_profile_add_store: bad argument");
-    if (R->device != P->device) return fail(GFFX_E_INVALID, "gffx_hip_profile_add_store: store and profile on different devices");
-    if (first + n_rows > R->last_n[k]) return fail(GFFX_E_INVALID, "gffx_hip_profile_add_store: rows beyond the last append");
+    const uint32_t *src = nullptr;
+    if ((rc = store_slot_rows(R, k, first, n_rows, P->device, "gffx_hip_profile_add_store", "profile", &src))) return rc;
     if ((rc = profile_budget(P, n_rows, "gffx_hip_profile_add_store"))) return rc;
-    if (R->pending[k]) GFFX_PROFILE_HIP(hipStreamWaitEvent(P->stream, R->copied[k], 0));
-    const uint32_t *src = R->d + 3 * (R->last_first[k] + first);
+    if (R->pending[k]) GFFX_KEEP_HIP(P, hipStreamWaitEvent(P->stream, R->copied[k], 0));
     for (uint64_t at = 0; at < n_rows; at += kProfileFold) {
         const uint64_t m = std::min<uint64_t>(kProfileFold, n_rows - at);
-        GFFX_PROFILE_TRY(profile_collect(P));
-        GFFX_PROFILE_TRY(profile_reserve(P, P->n_points + 2 * m));
-        GFFX_PROFILE_TRY(profile_fold(P, src + 3 * at, m, nullptr, 0));  // (the slot is read in place: no copy)
+        GFFX_KEEP_TRY(P, profile_collect(P));
+        GFFX_KEEP_TRY(P, profile_reserve(P, P->n_points + 2 * m));
+        GFFX_KEEP_TRY(P, profile_fold(P, src + 3 * at, m, nullptr, 0));  // (the slot is read in place: no copy)
         P->budget += m;
     }
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_profile_add_points(gffx_hip_profile *P, const uint64_t *p_off, const uint32_t *pos, const uint32_t *depth) {
-    int rc = profile_enter(P, "gffx_hip_profile_add_points");
+    int rc = enter_handle(P, "gffx_hip_profile_add_points");
     if (rc) return rc;
     if (!p_off) return fail(GFFX_E_INVALID, "gffx_hip_profile_add_points: p_off is NULL");
     const uint64_t n = p_off[P->n_seq];
     if (n && (!pos || !depth)) return fail(GFFX_E_INVALID, "gffx_hip_profile_add_points: NULL point array");
     // (p_off is looked at here: the arrays cannot be read without it; everything else is checked on the device)
-    if (p_off[0] != 0) return profile_fail(P, fail(GFFX_E_INVALID, "gffx_hip_profile_add_points: p_off does not start at 0"));
+    if (p_off[0] != 0) return keep_failure(P, fail(GFFX_E_INVALID, "gffx_hip_profile_add_points: p_off does not start at 0"));
     for (uint32_t c = 0; c < P->n_seq; ++c)
-        if (p_off[c + 1] < p_off[c] || p_off[c + 1] > n) return profile_fail(P, fail(GFFX_E_INVALID, "gffx_hip_profile_add_points: p_off is not ascending"));
+        if (p_off[c + 1] < p_off[c] || p_off[c + 1] > n) return keep_failure(P, fail(GFFX_E_INVALID, "gffx_hip_profile_add_points: p_off is not ascending"));
     if (!n) return GFFX_OK;
     std::vector<uint32_t> rec(3 * n);
     uint32_t deepest = 0;
@@ -661,24 +629,24 @@ extern "C" int gffx_hip_profile_add_points(gffx_hip_profile *P, const uint64_t *
             deepest = std::max(deepest, depth[i]);
         }
     if ((rc = profile_budget(P, deepest, "gffx_hip_profile_add_points"))) return rc;
-    GFFX_PROFILE_TRY(profile_collect(P));
-    GFFX_PROFILE_TRY(profile_reserve(P, P->n_points + n));
-    GFFX_PROFILE_TRY(profile_rows_room(P, n));
-    GFFX_PROFILE_HIP(hipMemcpy(P->d_rows, rec.data(), n * 12, hipMemcpyHostToDevice));  // (no fold reads d_rows any more: each returned behind its `read`)
-    GFFX_PROFILE_TRY(profile_fold(P, nullptr, 0, P->d_rows, n));
+    GFFX_KEEP_TRY(P, profile_collect(P));
+    GFFX_KEEP_TRY(P, profile_reserve(P, P->n_points + n));
+    GFFX_KEEP_TRY(P, profile_rows_room(P, n));
+    GFFX_KEEP_HIP(P, hipMemcpy(P->d_rows, rec.data(), n * 12, hipMemcpyHostToDevice));  // (no fold reads d_rows any more: each returned behind its `read`)
+    GFFX_KEEP_TRY(P, profile_fold(P, nullptr, 0, P->d_rows, n));
     P->budget += deepest;
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_profile_finish(gffx_hip_profile *P) {
-    int rc = profile_enter(P, "gffx_hip_profile_finish");
+    int rc = enter_handle(P, "gffx_hip_profile_finish");
     if (rc) return rc;
-    GFFX_PROFILE_TRY(profile_collect(P));
+    GFFX_KEEP_TRY(P, profile_collect(P));
     if (P->finished) return GFFX_OK;
     hipLaunchKernelGGL(k_profile_offsets, dim3(P->n_seq / kProfileThreads + 1), dim3(kProfileThreads), 0, P->stream, (const uint32_t *)P->buf[P->cur],
                        (u64)P->n_points, P->n_seq, P->d_poff);
-    GFFX_PROFILE_HIP(hipGetLastError());
-    GFFX_PROFILE_HIP(hipStreamSynchronize(P->stream));
+    GFFX_KEEP_HIP(P, hipGetLastError());
+    GFFX_KEEP_HIP(P, hipStreamSynchronize(P->stream));
     P->finished = true;
     return GFFX_OK;
 }
@@ -690,19 +658,19 @@ extern "C" uint64_t gffx_hip_profile_n_points(const gffx_hip_profile *Pc) {
     if (P->status == GFFX_OK && P->pending) {
         if (hipSetDevice(P->device) != hipSuccess) return 0;
         const int rc = profile_collect(P);
-        if (rc) return (void)profile_fail(P, rc), 0;
+        if (rc) return (void)keep_failure(P, rc), 0;
     }
     return P->n_points;
 }
 
 extern "C" int gffx_hip_profile_copy_points(gffx_hip_profile *P, uint64_t *p_off, uint32_t *pos, uint32_t *depth) {
-    int rc = profile_enter(P, "gffx_hip_profile_copy_points");
+    int rc = enter_handle(P, "gffx_hip_profile_copy_points");
     if (rc) return rc;
     if (!P->finished || P->pending) return fail(GFFX_E_STATE, "gffx_hip_profile_copy_points: call gffx_hip_profile_finish first");
-    if (p_off) GFFX_PROFILE_HIP(hipMemcpy(p_off, P->d_poff, ((uint64_t)P->n_seq + 1) * 8, hipMemcpyDeviceToHost));
+    if (p_off) GFFX_KEEP_HIP(P, hipMemcpy(p_off, P->d_poff, ((uint64_t)P->n_seq + 1) * 8, hipMemcpyDeviceToHost));
     if ((pos || depth) && P->n_points) {
         std::vector<uint32_t> rec(3 * P->n_points);
-        GFFX_PROFILE_HIP(hipMemcpy(rec.data(), P->buf[P->cur], P->n_points * 12, hipMemcpyDeviceToHost));
+        GFFX_KEEP_HIP(P, hipMemcpy(rec.data(), P->buf[P->cur], P->n_points * 12, hipMemcpyDeviceToHost));
         for (uint64_t i = 0; i < P->n_points; ++i) {
             if (pos) pos[i] = rec[3 * i + 1];
             if (depth) depth[i] = rec[3 * i + 2];
@@ -712,14 +680,14 @@ extern "C" int gffx_hip_profile_copy_points(gffx_hip_profile *P, uint64_t *p_off
 }
 
 extern "C" int gffx_hip_profile_union_at_least(gffx_hip_profile *P, uint32_t T, gffx_hip_union **out) {
-    int rc = profile_enter(P, "gffx_hip_profile_union_at_least");
+    int rc = enter_handle(P, "gffx_hip_profile_union_at_least");
     if (rc) return rc;
     if (!out) return fail(GFFX_E_INVALID, "gffx_hip_profile_union_at_least: out is NULL");
     *out = nullptr;
     if (T == 0) return fail(GFFX_E_INVALID, "gffx_hip_profile_union_at_least: T is 0 (every base has depth >= 0)");
     if (!P->finished || P->pending) return fail(GFFX_E_STATE, "gffx_hip_profile_union_at_least: call gffx_hip_profile_finish first");
     gffx_hip_union *raw = nullptr;
-    GFFX_PROFILE_TRY(gffx_hip_union_create(P->device, P->n_seq, &raw));
+    GFFX_KEEP_TRY(P, gffx_hip_union_create(P->device, P->n_seq, &raw));
     std::unique_ptr<gffx_hip_union, void (*)(gffx_hip_union *)> U(raw, gffx_hip_union_destroy);
     const u64 np = P->n_points;
     if (np) {
@@ -727,30 +695,30 @@ extern "C" int gffx_hip_profile_union_at_least(gffx_hip_profile *P, uint32_t T, 
         const uint32_t *pts = P->buf[P->cur];
         hipLaunchKernelGGL(k_profile_span_count, dim3(tiles), dim3(kProfileThreads), 0, P->stream, pts, np, T, P->tile[2]);
         hipLaunchKernelGGL(k_profile_carry_count, dim3(1), dim3(kProfileThreads), 0, P->stream, P->tile[2], tiles, reinterpret_cast<u64 *>(P->ctl + 4));
-        GFFX_PROFILE_HIP(hipGetLastError());
-        GFFX_PROFILE_HIP(hipMemcpyAsync(P->h_ctl, P->ctl, 32, hipMemcpyDeviceToHost, P->stream));
-        GFFX_PROFILE_HIP(hipStreamSynchronize(P->stream));
+        GFFX_KEEP_HIP(P, hipGetLastError());
+        GFFX_KEEP_HIP(P, hipMemcpyAsync(P->h_ctl, P->ctl, 32, hipMemcpyDeviceToHost, P->stream));
+        GFFX_KEEP_HIP(P, hipStreamSynchronize(P->stream));
         const uint64_t spans = (uint64_t)P->h_ctl[4] | ((uint64_t)P->h_ctl[5] << 32);
         if (spans) {
-            GFFX_PROFILE_TRY(profile_alloc(&U->rec_a, 3 * spans));
-            GFFX_PROFILE_TRY(profile_alloc(&U->rec_b, 3 * spans));
+            GFFX_KEEP_TRY(P, dev_alloc_padded(&U->rec_a, 3 * spans));
+            GFFX_KEEP_TRY(P, dev_alloc_padded(&U->rec_b, 3 * spans));
             U->cap = std::max<uint64_t>(spans, 1);
             hipLaunchKernelGGL(k_profile_spans, dim3(tiles), dim3(kProfileThreads), 0, P->stream, pts, np, T, (const u64 *)P->tile[2], (u64)spans, U->rec_a);
-            GFFX_PROFILE_HIP(hipGetLastError());
-            GFFX_PROFILE_HIP(hipStreamSynchronize(P->stream));  // (the union reads rec_a on its own stream)
+            GFFX_KEEP_HIP(P, hipGetLastError());
+            GFFX_KEEP_HIP(P, hipStreamSynchronize(P->stream));  // (the union reads rec_a on its own stream)
             U->n_spans = spans;
         }
     }
     U->rows_added = P->rows_added;
-    GFFX_PROFILE_TRY(gffx_hip_union_finish(U.get()));
+    GFFX_KEEP_TRY(P, gffx_hip_union_finish(U.get()));
     *out = U.release();
     return GFFX_OK;
 }
 
 extern "C" int gffx_hip_profile_reset(gffx_hip_profile *P) {
-    int rc = profile_enter(P, "gffx_hip_profile_reset");
+    int rc = enter_handle(P, "gffx_hip_profile_reset");
     if (rc) return rc;
-    GFFX_PROFILE_TRY(profile_collect(P));
+    GFFX_KEEP_TRY(P, profile_collect(P));
     P->n_points = 0, P->budget = 0, P->finished = false;
     return GFFX_OK;
 }
@@ -760,8 +728,8 @@ extern "C" int gffx_hip_profile_stage_ms(const gffx_hip_profile *Pc, double *eve
     if (!Pc) return fail(GFFX_E_INVALID, "gffx_hip_profile_stage_ms: profile is NULL");
     gffx_hip_profile *P = const_cast<gffx_hip_profile *>(Pc);
     if (P->status == GFFX_OK && P->pending) {
-        GFFX_PROFILE_HIP(hipSetDevice(P->device));
-        GFFX_PROFILE_TRY(profile_collect(P));
+        GFFX_KEEP_HIP(P, hipSetDevice(P->device));
+        GFFX_KEEP_TRY(P, profile_collect(P));
     }
     if (events) *events = P->stage_ms[0];
     if (sort) *sort = P->stage_ms[1];

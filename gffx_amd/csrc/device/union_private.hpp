@@ -6,13 +6,12 @@
 #include <vector>
 
 #include "gffx_device.hpp"
+#include "handle_status.hpp"
 #include "radix_sort.hpp"
 
-struct gffx_hip_union {
-    int device = 0;
+struct gffx_hip_union : gffx::HandleStatus {
+    static constexpr const char *kName = "union", *kNoun = "union";
     uint32_t n_seq = 0;
-    int status = GFFX_OK;  // the first error: the object only reports it again
-    std::string message;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     uint32_t *rec_a = nullptr, *rec_b = nullptr;  // rec_a[0 .. n_spans) = the spans so far as {seqid, start, end} records

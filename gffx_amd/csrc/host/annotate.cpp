@@ -5,20 +5,12 @@
 // streams chunk by chunk through a region store like `gffx closest`: the output -- one line per region in input order --
 // depends neither on the chunk size nor on -t.
 #include <cstdio>
-#include <cstring>
 
-#include "intersect_internal.hpp"
 #include "layer_rows.hpp"
+#include "region_feed.hpp"
 #include "table_output.hpp"
 
 namespace gffx::commands::annotate {
-
-namespace {
-
-using ClassMapHandle = Handle<gffx_hip_classmap, gffx_hip_classmap_destroy>;
-using intersect::SeqidTable;
-
-}  // namespace
 
 void run(const AnnotateArgs &args) {
     const bool verbose = args.common.verbose;
@@ -35,39 +27,13 @@ void run(const AnnotateArgs &args) {
     std::vector<uint64_t> per_layer(T, 0);
     uint64_t skipped = 0;
     layer_rows::collect(args.common.input, layers, index_data.seqid_to_num, threads, verbose, rows, per_layer, skipped, nullptr);
-    for (uint32_t k = 0; k < T; ++k) {
-        if (!per_layer[k]) std::fprintf(stderr, "[WARN] no line of %s has type '%s': its column is zero\n", args.common.input.c_str(), layers[k].c_str());
-        if (verbose) std::fprintf(stderr, "[DEBUG] annotate: layer %u '%s': %llu lines\n", k, layers[k].c_str(), (unsigned long long)per_layer[k]);
-    }
-    if (verbose) std::fprintf(stderr, "[DEBUG] annotate: %llu lines skipped (a seqid the index does not know)\n", (unsigned long long)skipped);
+    layer_rows::report(args.common.input, layers, per_layer, ": its column is zero", verbose ? "annotate" : nullptr, skipped);
     timer.lap("Layer rows from the line table");
-    std::vector<uint32_t> all_rows;
-    std::optional<MappedFile> bed_file;
-    bool device_rows = false;
-    size_t chunk_rows = 1;
-    const size_t chunk_bytes = intersect::stream_chunk_bytes();
-    if (args.region) {
-        const auto [chr, s, e] = intersect::parse_region(*args.region, index_data.seqid_to_num, args.common);
-        all_rows = {chr, s, e};
-    } else {
-        device_rows = bed::route(*args.bed) == bed::Route::Device;
-        bed_file.emplace(*args.bed);
-    }
+    RegionFeed feed(args.region, args.bed, index_data, args.common);
     warm.wait();
-    if (args.bed && device_rows) {
-        all_rows = bed::read_rows(*args.bed, index_data.seqid_to_num, bed::kIntersect, args.device, verbose);
-        timer.lap("BED rows read on the device");
-    }
-    if (args.bed)
-        chunk_rows = (device_rows ? std::min(chunk_bytes / intersect::kMinBedRowBytes, std::max<size_t>(all_rows.size() / 3, 1))
-                                  : std::min(chunk_bytes, std::max<size_t>(bed_file->size(), 1)) / intersect::kMinBedRowBytes) + 16;
-    ClassMapHandle h;
-    if (gffx_hip_classmap_create(args.device, n_seq, T, OutPtr(h)) != GFFX_OK) hip_fail("gffx_hip_classmap_create");
-    if (gffx_hip_classmap_add_rows_host(h.get(), rows.data(), rows.size() / 4) != GFFX_OK) hip_fail("gffx_hip_classmap_add_rows_host");
-    if (gffx_hip_classmap_finish(h.get()) != GFFX_OK) hip_fail("gffx_hip_classmap_finish");
-    std::vector<uint32_t>().swap(rows);
-    RegionsHandle store;
-    if (gffx_hip_regions_create(args.device, 0, chunk_rows, 0, OutPtr(store)) != GFFX_OK) hip_fail("gffx_hip_regions_create");
+    feed.open(args.device, verbose, timer);
+    const ClassMapHandle h = layer_rows::build_class_map(args.device, n_seq, T, rows);
+    feed.create_store(args.device);
     timer.lap("Class map + buffers");
     Output out(args.common.output);
     {
@@ -81,12 +47,10 @@ void run(const AnnotateArgs &args) {
     std::string text;
     uint64_t regions = 0;
     double kernel_ms = 0;
-    size_t chunk = 0;
     // n rows sit in staging buffer k: to the store, through the device, to the output
-    auto serve = [&](int k, uint64_t n) {
-        const uint32_t *stage = gffx_hip_regions_staging(store.get(), k);
-        if (gffx_hip_regions_append(store.get(), k, n) != GFFX_OK) hip_fail("gffx_hip_regions_append");
-        if (gffx_hip_classmap_run_store(h.get(), store.get(), k, 0, n) != GFFX_OK) hip_fail("gffx_hip_classmap_run_store");
+    feed.run(threads, [&](gffx_hip_regions *store, int k, const uint32_t *stage, uint64_t n) {
+        if (gffx_hip_regions_append(store, k, n) != GFFX_OK) hip_fail("gffx_hip_regions_append");
+        if (gffx_hip_classmap_run_store(h.get(), store, k, 0, n) != GFFX_OK) hip_fail("gffx_hip_classmap_run_store");
         if (gffx_hip_classmap_wait(h.get()) != GFFX_OK) hip_fail("gffx_hip_classmap_wait");
         counts.resize(n * (T + 1)), cls.resize(n);
         if (gffx_hip_classmap_copy_counts(h.get(), counts.data()) != GFFX_OK || gffx_hip_classmap_copy_class(h.get(), cls.data()) != GFFX_OK)
@@ -111,37 +75,7 @@ void run(const AnnotateArgs &args) {
             for (uint32_t c = 0; c <= T; ++c) sum_bases[c] += counts[i * (T + 1) + c];
         }
         regions += n;
-        ++chunk;
-    };
-    auto staging = [&](int k) {
-        if (gffx_hip_regions_wait_staging(store.get(), k) != GFFX_OK) hip_fail("gffx_hip_regions_wait_staging");
-        return gffx_hip_regions_staging(store.get(), k);
-    };
-    if (args.region || device_rows) {
-        const size_t n_all = all_rows.size() / 3, step = chunk_rows > 16 ? chunk_rows - 16 : 1;
-        for (size_t at = 0; at < n_all; at += step) {
-            const size_t n = std::min(step, n_all - at);
-            const int k = static_cast<int>(chunk & 1);
-            std::memcpy(staging(k), all_rows.data() + 3 * at, n * 12);
-            serve(k, n);
-        }
-    } else {
-        const std::string_view bed_text = bed_file->view();
-        const SeqidTable seqids(index_data.seqid_to_num);
-        std::vector<std::vector<uint32_t>> piece;
-        intersect::for_each_line_chunk(bed_text, chunk_bytes, [&](size_t pos, size_t z, bool last) {
-            intersect::parse_bed_pieces(bed_text, pos, z, last, seqids, threads, piece);
-            const int k = static_cast<int>(chunk & 1);
-            uint32_t *dst = staging(k);
-            uint64_t n = 0;
-            for (const auto &p : piece) {
-                std::memcpy(dst + 3 * n, p.data(), p.size() * 4);
-                n += p.size() / 3;
-            }
-            if (n) serve(k, n);
-            return true;
-        });
-    }
+    });
     out.close();
     if (args.summary) {
         Output sum(args.summary);
@@ -155,14 +89,14 @@ void run(const AnnotateArgs &args) {
         sum.close();
     }
     timer.lap("Regions through the device + writing");
-    if (verbose) std::fprintf(stderr, "[DEBUG] annotate: %llu regions in %zu chunks\n", (unsigned long long)regions, chunk);
+    if (verbose) std::fprintf(stderr, "[DEBUG] annotate: %llu regions in %zu chunks\n", (unsigned long long)regions, feed.chunks());
     const double total_ms = timer.total();
     double stage[6] = {0, 0, 0, 0, 0, 0};
     (void)gffx_hip_classmap_stage_ms(h.get(), stage);
     g_run_stats.count("regions", (double)regions);
     g_run_stats.count("layers", (double)T);
     g_run_stats.count("points", (double)gffx_hip_classmap_n_points(h.get()));
-    g_run_stats.count("chunks", (double)chunk);
+    g_run_stats.count("chunks", (double)feed.chunks());
     g_run_stats.count("kernel_ms", kernel_ms);
     g_run_stats.count("class_map_build_ms", stage[0] + stage[1] + stage[2] + stage[3] + stage[4] + stage[5]);
     g_run_stats.count("threads", (double)threads);

@@ -6,6 +6,8 @@
 //                       `gffx index`, so that later runs upload it without touching the GFF text
 #include <algorithm>
 #include <atomic>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 
 #include "gffx.hpp"
@@ -384,3 +386,39 @@ BlockTable load_or_build_block_table(const std::string &gff_path, const index_lo
 }
 
 }  // namespace gffx::commands::depth
+
+namespace gffx {
+
+void write_line_images(const std::string &input, bool verbose) {
+    const char *lt = std::getenv("GFFX_LINE_TABLE");
+    if (lt && std::string(lt) == "off") {
+        std::remove(append_suffix(input, ".lsoa").c_str());  // an image of an earlier index run would be stale
+        std::remove(append_suffix(input, ".lall").c_str());
+        return;
+    }
+    const index_loader::GofMap gof = index_loader::load_gof(input);
+    const MappedFile text(input);
+    const unsigned hw = std::thread::hardware_concurrency();
+    // Both images are optional accelerators (the commands fall back to the text walk without them): a failure to write one
+    // -- a full or read-only directory, a quota -- is a warning, the partial file is removed, and the index the reference
+    // defines (the eight side-cars) stands.
+    try {
+        const auto t = commands::depth::build_block_table(gof, text.view(), std::min(hw ? hw : 1u, 12u));
+        commands::depth::write_block_table(append_suffix(input, ".lsoa"), t, text.size(), index_loader::line_table_key(input, gof));
+        if (verbose) std::printf("Line table image: %zu lines in %zu blocks.\n", t.line_start.size(), t.block_line_off.size() - 1);
+    } catch (const Error &e) {
+        std::fprintf(stderr, "[WARN] line table image %s not written: %s\n", append_suffix(input, ".lsoa").c_str(), e.what());
+        std::remove(append_suffix(input, ".lsoa").c_str());
+    }
+    // ... and the all-line table `<gff>.lall` of intersect's per-line mode (line_index.cpp)
+    try {
+        const auto all = commands::intersect::build_all_lines(text.view(), std::min(hw ? hw : 1u, 12u));
+        commands::intersect::write_all_lines(append_suffix(input, ".lall"), all, text.size(), index_loader::line_table_key(input, gof));
+        if (verbose) std::printf("All-line table: %zu lines, %zu seqid names, %zu types.\n", all.ls.size(), all.seq_names.size(), all.type_names.size());
+    } catch (const Error &e) {
+        std::fprintf(stderr, "[WARN] all-line table %s not written: %s\n", append_suffix(input, ".lall").c_str(), e.what());
+        std::remove(append_suffix(input, ".lall").c_str());
+    }
+}
+
+}  // namespace gffx

@@ -4,10 +4,9 @@
 // chunk is answered and written before the next one is parsed: memory is bounded by a chunk, and the output -- one line per
 // answered root in kept-row order -- depends neither on the chunk size nor on -t.
 #include <cstdio>
-#include <cstring>
 
 #include "../device/closest_core.hpp"
-#include "intersect_internal.hpp"
+#include "region_feed.hpp"
 #include "table_output.hpp"
 
 namespace gffx::commands::closest {
@@ -15,7 +14,6 @@ namespace gffx::commands::closest {
 namespace {
 
 using ClosestHandle = Handle<gffx_hip_closest, gffx_hip_closest_destroy>;
-using intersect::SeqidTable;
 
 // `.fts`: the ID of feature fid is line fid
 std::vector<std::string_view> fts_lines(std::string_view data) {
@@ -97,75 +95,24 @@ void run(const ClosestArgs &args) {
     timer.lap("Loading tree index + .fts");
     const uint32_t side_flag = args.side == Side::Left ? uint32_t(GFFX_CLOSEST_LEFT_ONLY) : args.side == Side::Right ? uint32_t(GFFX_CLOSEST_RIGHT_ONLY) : 0u;
     const uint32_t flags = (args.ignore_overlaps ? uint32_t(GFFX_CLOSEST_IGNORE_OVERLAPS) : 0u) | side_flag;
-    // what the run will hand over at once: one region, the device reader's rows in slices, or the rows of a chunk of text
-    std::vector<uint32_t> all_rows;
-    std::optional<MappedFile> bed_file;
-    bool device_rows = false;
-    size_t chunk_rows = 1;
-    const size_t chunk_bytes = intersect::stream_chunk_bytes();
-    if (args.region) {
-        const auto [chr, s, e] = intersect::parse_region(*args.region, index_data.seqid_to_num, args.common);
-        all_rows = {chr, s, e};
-    } else {
-        device_rows = bed::route(*args.bed) == bed::Route::Device;
-        bed_file.emplace(*args.bed);
-    }
+    RegionFeed feed(args.region, args.bed, index_data, args.common);
     warm.wait();
     index_data.ensure_device(args.device);
     timer.lap("Index upload");
-    if (args.bed && device_rows) {
-        all_rows = bed::read_rows(*args.bed, index_data.seqid_to_num, bed::kIntersect, args.device, verbose);
-        timer.lap("BED rows read on the device");
-    }
-    if (args.bed)
-        chunk_rows = (device_rows ? std::min(chunk_bytes / intersect::kMinBedRowBytes, std::max<size_t>(all_rows.size() / 3, 1))
-                                  : std::min(chunk_bytes, std::max<size_t>(bed_file->size(), 1)) / intersect::kMinBedRowBytes) + 16;
+    feed.open(args.device, verbose, timer);
     ClosestHandle h;
-    if (gffx_hip_closest_create(index_data.device_index.get(), chunk_rows, OutPtr(h)) != GFFX_OK) hip_fail("gffx_hip_closest_create");
-    RegionsHandle store;
-    if (gffx_hip_regions_create(args.device, 0, chunk_rows, 0, OutPtr(store)) != GFFX_OK) hip_fail("gffx_hip_regions_create");
+    if (gffx_hip_closest_create(index_data.device_index.get(), feed.chunk_rows(), OutPtr(h)) != GFFX_OK) hip_fail("gffx_hip_closest_create");
+    feed.create_store(args.device);
     timer.lap("End table + buffers");
     Output out(args.common.output);
     out.write("chr\tstart\tend\tid\tfeature_start\tfeature_end\tdistance\n");
     Runner r{index_data, ids, h.get(), threads, out};
-    size_t chunk = 0;
     // n rows sit in staging buffer k: to the store, through the device, to the output
-    auto serve = [&](int k, uint64_t n) {
-        uint32_t *stage = gffx_hip_regions_staging(store.get(), k);
-        if (gffx_hip_regions_append(store.get(), k, n) != GFFX_OK) hip_fail("gffx_hip_regions_append");
-        if (gffx_hip_closest_run_store(h.get(), store.get(), k, 0, n, flags) != GFFX_OK) hip_fail("gffx_hip_closest_run_store");
-        r.finish(stage, n);  // (the staging buffer still holds the rows: it is refilled two chunks on)
-        ++chunk;
-    };
-    auto staging = [&](int k) {
-        if (gffx_hip_regions_wait_staging(store.get(), k) != GFFX_OK) hip_fail("gffx_hip_regions_wait_staging");
-        return gffx_hip_regions_staging(store.get(), k);
-    };
-    if (args.region || device_rows) {
-        const size_t n_all = all_rows.size() / 3, step = chunk_rows > 16 ? chunk_rows - 16 : 1;
-        for (size_t at = 0; at < n_all; at += step) {
-            const size_t n = std::min(step, n_all - at);
-            const int k = static_cast<int>(chunk & 1);
-            std::memcpy(staging(k), all_rows.data() + 3 * at, n * 12);
-            serve(k, n);
-        }
-    } else {
-        const std::string_view text = bed_file->view();
-        const SeqidTable seqids(index_data.seqid_to_num);
-        std::vector<std::vector<uint32_t>> piece;
-        intersect::for_each_line_chunk(text, chunk_bytes, [&](size_t pos, size_t z, bool last) {
-            intersect::parse_bed_pieces(text, pos, z, last, seqids, threads, piece);
-            const int k = static_cast<int>(chunk & 1);
-            uint32_t *dst = staging(k);
-            uint64_t n = 0;
-            for (const auto &p : piece) {
-                std::memcpy(dst + 3 * n, p.data(), p.size() * 4);
-                n += p.size() / 3;
-            }
-            if (n) serve(k, n);
-            return true;
-        });
-    }
+    feed.run(threads, [&](gffx_hip_regions *store, int k, const uint32_t *stage, uint64_t n) {
+        if (gffx_hip_regions_append(store, k, n) != GFFX_OK) hip_fail("gffx_hip_regions_append");
+        if (gffx_hip_closest_run_store(h.get(), store, k, 0, n, flags) != GFFX_OK) hip_fail("gffx_hip_closest_run_store");
+        r.finish(stage, n);
+    });
     out.close();
     timer.lap("Regions through the device + writing");
     if (verbose)
@@ -178,7 +125,7 @@ void run(const ClosestArgs &args) {
     g_run_stats.count("regions", (double)r.regions);
     g_run_stats.count("answered_roots", (double)r.pairs);
     g_run_stats.count("regions_without_answer", (double)r.unanswered);
-    g_run_stats.count("chunks", (double)chunk);
+    g_run_stats.count("chunks", (double)feed.chunks());
     g_run_stats.count("kernel_ms", r.kernel_ms);
     g_run_stats.count("end_table_build_ms", build_ms);
     g_run_stats.count("pair_buffer_grows", (double)grows);

@@ -29,6 +29,7 @@
 #include <future>
 
 #include "gffx.hpp"
+#include "source_read.hpp"
 
 namespace gffx::commands::coverage {
 
@@ -63,16 +64,6 @@ uint64_t covered(const std::vector<Span> &cov, uint32_t a, uint32_t b) {  // cov
         if (e > s) t += e - s;
     }
     return t;
-}
-
-size_t batch_rows_from_env() {  // GFFX_COVERAGE_BATCH_ROWS (gffx.hpp)
-    const char *e = std::getenv("GFFX_COVERAGE_BATCH_ROWS");
-    if (e && *e) {
-        char *end = nullptr;
-        const unsigned long long v = std::strtoull(e, &end, 10);
-        if (end && !*end && v > 0) return static_cast<size_t>(std::min<unsigned long long>(v, 1ull << 28));
-    }
-    return 4u << 20;
 }
 
 struct Seg {
@@ -247,7 +238,7 @@ void run(const CoverageArgs &args) {
             double union_ms = 0;
         };
         std::vector<PerDevice> pd(D);
-        const size_t kBatch = batch_rows_from_env();
+        const size_t kBatch = source::batch_rows_from_env("GFFX_COVERAGE_BATCH_ROWS");
         const size_t cap = std::min(n_regions, kBatch);
         parallel_for(D, D, [&](size_t d) {
             PerDevice &P = pd[d];

@@ -14,6 +14,7 @@
 
 #include "fast_fields.hpp"
 #include "gffx.hpp"
+#include "source_read.hpp"
 
 namespace gffx::commands::depth {
 
@@ -36,16 +37,6 @@ std::string_view trim_end_unicode_ws(std::string_view s) {  // str::trim_end()
             }
         if (!cut) return s;
     }
-}
-
-size_t batch_rows_from_env() {  // GFFX_DEPTH_BATCH_ROWS (gffx.hpp)
-    const char *e = std::getenv("GFFX_DEPTH_BATCH_ROWS");
-    if (e && *e >= '0' && *e <= '9') {  // (strtoull alone would take "-5" for a huge number)
-        char *end = nullptr;
-        const unsigned long long v = std::strtoull(e, &end, 10);
-        if (end && !*end && v > 0) return static_cast<size_t>(std::min<unsigned long long>(v, 1ull << 28));
-    }
-    return 4u << 20;
 }
 
 }  // namespace
@@ -262,7 +253,7 @@ void run(const DepthArgs &args) {
         std::vector<PerDevice> pd(D);
         // regions stream through Join A in batches (the reference's BATCH_SIZE, depth.rs:24, only bounds memory:
         // every merge is min / max / sum); 4 Mi rows unless GFFX_DEPTH_BATCH_ROWS says otherwise
-        const size_t kBatch = batch_rows_from_env();
+        const size_t kBatch = source::batch_rows_from_env("GFFX_DEPTH_BATCH_ROWS");
         const size_t cap = std::min(n_rows, kBatch);
         // (one thread per device; a device's failure is an Error of its thread: the first device's in the list is reported)
         parallel_for(D, D, [&](size_t d) {

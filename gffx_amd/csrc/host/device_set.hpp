@@ -24,6 +24,7 @@ using LinesHandle = Handle<gffx_hip_lines, gffx_hip_lines_destroy>;
 using UnionHandle = Handle<gffx_hip_union, gffx_hip_union_destroy>;
 using PileupHandle = Handle<gffx_hip_pileup, gffx_hip_pileup_destroy>;
 using ProfileHandle = Handle<gffx_hip_profile, gffx_hip_profile_destroy>;
+using ClassMapHandle = Handle<gffx_hip_classmap, gffx_hip_classmap_destroy>;
 using IdsHandle = Handle<gffx_hip_ids, gffx_hip_ids_destroy>;
 using AttrsHandle = Handle<gffx_hip_attrs, gffx_hip_attrs_destroy>;
 

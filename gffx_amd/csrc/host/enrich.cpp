@@ -6,19 +6,15 @@
 // sums (gffx_hip_classmap_perm_*): the output depends neither on the chunk size nor on -t.
 #include <cmath>
 #include <cstdio>
-#include <cstring>
 
 #include "genome_file.hpp"
-#include "intersect_internal.hpp"
 #include "layer_rows.hpp"
+#include "region_feed.hpp"
 #include "table_output.hpp"
 
 namespace gffx::commands::enrich {
 
 namespace {
-
-using ClassMapHandle = Handle<gffx_hip_classmap, gffx_hip_classmap_destroy>;
-using intersect::SeqidTable;
 
 void append_float(std::string &s, double v) {
     char buf[48];
@@ -75,75 +71,26 @@ void run(const EnrichArgs &args) {
         seq_len = seq_end;
         if (verbose) std::fprintf(stderr, "[INFO] enrich: no -g: a seqid's length is the largest end of its lines, which understates the chromosome\n");
     }
-    for (uint32_t k = 0; k < T; ++k) {
-        if (!per_layer[k]) std::fprintf(stderr, "[WARN] no line of %s has type '%s': its class is empty\n", args.common.input.c_str(), layers[k].c_str());
-        if (verbose) std::fprintf(stderr, "[DEBUG] enrich: layer %u '%s': %llu lines\n", k, layers[k].c_str(), (unsigned long long)per_layer[k]);
-    }
-    if (verbose) std::fprintf(stderr, "[DEBUG] enrich: %llu lines skipped (a seqid the index does not know)\n", (unsigned long long)skipped);
+    layer_rows::report(args.common.input, layers, per_layer, ": its class is empty", verbose ? "enrich" : nullptr, skipped);
     timer.lap("Layer rows from the line table");
-    const bool device_rows = bed::route(args.bed) == bed::Route::Device;
-    std::optional<MappedFile> bed_file;
-    bed_file.emplace(args.bed);
-    const size_t chunk_bytes = intersect::stream_chunk_bytes();
+    RegionFeed feed(std::nullopt, args.bed, index_data, args.common);
     warm.wait();
-    std::vector<uint32_t> all_rows;
-    if (device_rows) {
-        all_rows = bed::read_rows(args.bed, index_data.seqid_to_num, bed::kIntersect, args.device, verbose);
-        timer.lap("BED rows read on the device");
-    }
-    const size_t chunk_rows = (device_rows ? std::min(chunk_bytes / intersect::kMinBedRowBytes, std::max<size_t>(all_rows.size() / 3, 1))
-                                           : std::min(chunk_bytes, std::max<size_t>(bed_file->size(), 1)) / intersect::kMinBedRowBytes) + 16;
-    ClassMapHandle h;
-    if (gffx_hip_classmap_create(args.device, n_seq, T, OutPtr(h)) != GFFX_OK) hip_fail("gffx_hip_classmap_create");
-    if (gffx_hip_classmap_add_rows_host(h.get(), rows.data(), rows.size() / 4) != GFFX_OK) hip_fail("gffx_hip_classmap_add_rows_host");
-    if (gffx_hip_classmap_finish(h.get()) != GFFX_OK) hip_fail("gffx_hip_classmap_finish");
-    std::vector<uint32_t>().swap(rows);
+    feed.open(args.device, verbose, timer);
+    const ClassMapHandle h = layer_rows::build_class_map(args.device, n_seq, T, rows);
     if (gffx_hip_classmap_perm_begin(h.get(), seq_len.data(), N, args.seed) != GFFX_OK) hip_fail("gffx_hip_classmap_perm_begin");
-    RegionsHandle store;
-    if (gffx_hip_regions_create(args.device, 0, chunk_rows, 0, OutPtr(store)) != GFFX_OK) hip_fail("gffx_hip_regions_create");
+    feed.create_store(args.device);
     timer.lap("Class map + buffers");
     uint64_t regions = 0;
     double kernel_ms = 0;
-    size_t chunk = 0;
     // n rows sit in staging buffer k: to the store and into the totals; `regions` is the global row of the first of them
-    auto serve = [&](int k, uint64_t n) {
-        if (gffx_hip_regions_append(store.get(), k, n) != GFFX_OK) hip_fail("gffx_hip_regions_append");
-        if (gffx_hip_classmap_perm_run_store(h.get(), store.get(), k, 0, n, regions) != GFFX_OK) hip_fail("gffx_hip_classmap_perm_run_store");
+    feed.run(threads, [&](gffx_hip_regions *store, int k, const uint32_t *, uint64_t n) {
+        if (gffx_hip_regions_append(store, k, n) != GFFX_OK) hip_fail("gffx_hip_regions_append");
+        if (gffx_hip_classmap_perm_run_store(h.get(), store, k, 0, n, regions) != GFFX_OK) hip_fail("gffx_hip_classmap_perm_run_store");
         if (gffx_hip_classmap_perm_wait(h.get()) != GFFX_OK) hip_fail("gffx_hip_classmap_perm_wait");
         double ms = 0;
         if (gffx_hip_classmap_perm_last_kernel_ms(h.get(), &ms) == GFFX_OK) kernel_ms += ms;
         regions += n;
-        ++chunk;
-    };
-    auto staging = [&](int k) {
-        if (gffx_hip_regions_wait_staging(store.get(), k) != GFFX_OK) hip_fail("gffx_hip_regions_wait_staging");
-        return gffx_hip_regions_staging(store.get(), k);
-    };
-    if (device_rows) {
-        const size_t n_all = all_rows.size() / 3, step = chunk_rows > 16 ? chunk_rows - 16 : 1;
-        for (size_t at = 0; at < n_all; at += step) {
-            const size_t n = std::min(step, n_all - at);
-            const int k = static_cast<int>(chunk & 1);
-            std::memcpy(staging(k), all_rows.data() + 3 * at, n * 12);
-            serve(k, n);
-        }
-    } else {
-        const std::string_view bed_text = bed_file->view();
-        const SeqidTable seqids(index_data.seqid_to_num);
-        std::vector<std::vector<uint32_t>> piece;
-        intersect::for_each_line_chunk(bed_text, chunk_bytes, [&](size_t pos, size_t z, bool last) {
-            intersect::parse_bed_pieces(bed_text, pos, z, last, seqids, threads, piece);
-            const int k = static_cast<int>(chunk & 1);
-            uint32_t *dst = staging(k);
-            uint64_t n = 0;
-            for (const auto &p : piece) {
-                std::memcpy(dst + 3 * n, p.data(), p.size() * 4);
-                n += p.size() / 3;
-            }
-            if (n) serve(k, n);
-            return true;
-        });
-    }
+    });
     const size_t cells = (static_cast<size_t>(N) + 1) * (T + 1);
     std::vector<uint64_t> B(cells, 0), R(cells, 0);
     uint64_t unplaced = 0;
@@ -183,7 +130,7 @@ void run(const EnrichArgs &args) {
     if (unplaced)
         std::fprintf(stderr, "[WARN] %llu regions are wider than their seqid's length%s and stayed where they are in every permutation\n", (unsigned long long)unplaced,
                      args.genome ? "" : " (no -g: the length is the largest end of the seqid's lines)");
-    if (verbose) std::fprintf(stderr, "[DEBUG] enrich: %llu regions in %zu chunks\n", (unsigned long long)regions, chunk);
+    if (verbose) std::fprintf(stderr, "[DEBUG] enrich: %llu regions in %zu chunks\n", (unsigned long long)regions, feed.chunks());
     const double total_ms = timer.total();
     double stage[6] = {0, 0, 0, 0, 0, 0};
     (void)gffx_hip_classmap_stage_ms(h.get(), stage);
@@ -192,7 +139,7 @@ void run(const EnrichArgs &args) {
     g_run_stats.count("permutations", (double)N);
     g_run_stats.count("unplaced", (double)unplaced);
     g_run_stats.count("points", (double)gffx_hip_classmap_n_points(h.get()));
-    g_run_stats.count("chunks", (double)chunk);
+    g_run_stats.count("chunks", (double)feed.chunks());
     g_run_stats.count("kernel_ms", kernel_ms);
     g_run_stats.count("class_map_build_ms", stage[0] + stage[1] + stage[2] + stage[3] + stage[4] + stage[5]);
     g_run_stats.count("threads", (double)threads);

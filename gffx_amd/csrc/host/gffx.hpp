@@ -149,6 +149,9 @@ void build_index(const std::string &gff, const std::string &attr_key, const std:
 // the same files, the arrays behind them built on HIP device `device` (gffx_hip_gff_*: device/gff.hip); no fallback
 void build_index_device(const std::string &gff, const std::string &attr_key, const std::string &skip_types,
                         int device, bool verbose);
+// additions, after either: the all-line SoA image `<gff>.lsoa` of depth / coverage (block_table.cpp) and the all-line table
+// `<gff>.lall` of intersect's per-line mode (line_index.cpp).  A failure to write one is a warning; GFFX_LINE_TABLE=off removes both.
+void write_line_images(const std::string &gff, bool verbose);
 
 // ---- index_loader ------------------------------------------------------------------------------
 namespace index_loader {

@@ -1,6 +1,6 @@
-// layer_rows.hpp -- the rows of the class map's layers from a GFF file, shared by `gffx annotate` and `gffx enrich`: -T names
-// the layers in priority order, the lines come from the all-line table `<gff>.lall` (or from the text when there is none:
-// GFFX_LINE_TABLE=parse, a stale or missing image).
+// layer_rows.hpp -- the rows of the class map's layers from a GFF file and the map built from them, shared by `gffx annotate`
+// and `gffx enrich` (`gffx meta` takes its features the same way): -T names the layers in priority order, the lines come from
+// the all-line table `<gff>.lall` (or from the text when there is none: GFFX_LINE_TABLE=parse, a stale or missing image).
 #pragma once
 #include <cstdio>
 #include <string>
@@ -69,6 +69,27 @@ inline void collect(const std::string &gff_path, const std::vector<std::string> 
     }
     if (verbose && use_all) std::fprintf(stderr, "[INFO] all-line table from %s.lall (%llu lines)\n", gff_path.c_str(), (unsigned long long)all.n_lines);
     if (verbose && !use_all) std::fprintf(stderr, "[INFO] all-line table not used (%s): parsing the text\n", why.c_str());
+}
+
+// What the user hears about the layers: a [WARN] line for every name without a line (tail: what that means for the command);
+// with debug_cmd (NULL: none of it) a [DEBUG] line per layer and one for the lines that collect() skipped.
+inline void report(const std::string &gff_path, const std::vector<std::string> &layers, const std::vector<uint64_t> &per_layer, const char *tail,
+                   const char *debug_cmd, uint64_t skipped) {
+    for (size_t k = 0; k < layers.size(); ++k) {
+        if (!per_layer[k]) std::fprintf(stderr, "[WARN] no line of %s has type '%s'%s\n", gff_path.c_str(), layers[k].c_str(), tail);
+        if (debug_cmd) std::fprintf(stderr, "[DEBUG] %s: layer %zu '%s': %llu lines\n", debug_cmd, k, layers[k].c_str(), (unsigned long long)per_layer[k]);
+    }
+    if (debug_cmd) std::fprintf(stderr, "[DEBUG] %s: %llu lines skipped (a seqid the index does not know)\n", debug_cmd, (unsigned long long)skipped);
+}
+
+// The finished class map of collect()'s rows on `device`; the rows are given up.
+inline ClassMapHandle build_class_map(int device, uint32_t n_seq, uint32_t n_layers, std::vector<uint32_t> &rows) {
+    ClassMapHandle h;
+    if (gffx_hip_classmap_create(device, n_seq, n_layers, OutPtr(h)) != GFFX_OK) hip_fail("gffx_hip_classmap_create");
+    if (gffx_hip_classmap_add_rows_host(h.get(), rows.data(), rows.size() / 4) != GFFX_OK) hip_fail("gffx_hip_classmap_add_rows_host");
+    if (gffx_hip_classmap_finish(h.get()) != GFFX_OK) hip_fail("gffx_hip_classmap_finish");
+    std::vector<uint32_t>().swap(rows);
+    return h;
 }
 
 }  // namespace gffx::commands::layer_rows

@@ -7,10 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <map>
-
-#include <thread>
 
 #include "gffx.hpp"
 
@@ -265,138 +262,133 @@ const char *kIndexUsage =
     "  -g, --gpu                      Build the side-cars on the HIP device (same bytes; no CPU fallback)\n"
     "      --device <N>               HIP device of --gpu [default: 0]\n";
 
-size_t parse_size(const std::string &v, const char *flag) {
-    const auto x = parse_u32_rust(v);
-    if (!x) throw UsageError(std::string("invalid value '") + v + "' for '" + flag + "'");
-    return *x;
-}
-
-int run_intersect_cli(int argc, char **argv) {
-    static const std::vector<OptSpec> specs = {
-        {'i', "input", true},   {'o', "output", true},     {'e', "entire_group", false}, {'T', "types", true},
-        {'t', "threads", true}, {'v', "verbose", false},   {'r', "region", true},        {'b', "bed", true},
-        {'c', "contained", false}, {'C', "contains-region", false}, {'O', "overlap", false},
-        {'I', "invert", false}, {0, "device", true},       {0, "gpus", true},           {0, "stats-json", true},
-        {'h', "help", false}};
-    const auto o = parse_opts(argc, argv, 2, specs);
-    if (o.count("help")) {
-        std::fputs(kIntersectUsage, stdout);
-        return 0;
+// What the scan found on a command's line, with the checks and conversions the commands share.  A `label` is the option as
+// the help text prints it ("--threads <NUM>"): the messages quote it.
+class Opts {
+  public:
+    Opts(int argc, char **argv, const std::vector<OptSpec> &specs) : got_(parse_opts(argc, argv, 2, specs)) {}
+    bool has(const char *name) const { return got_.count(name) > 0; }
+    const std::string &str(const char *name) const { return got_.at(name)[0]; }
+    std::optional<std::string> opt(const char *name) const { return has(name) ? std::optional<std::string>(str(name)) : std::nullopt; }
+    // a number as the reference's u32 / usize options take it; `fallback` without the option
+    size_t size(const char *name, const char *label, size_t fallback) const {
+        if (!has(name)) return fallback;
+        const auto x = parse_u32_rust(str(name));
+        if (!x) throw UsageError("invalid value '" + str(name) + "' for '" + label + "'");
+        return *x;
     }
+    using Labelled = std::pair<const char *, const char *>;  // {name, label}
+    // all of them, or the message that lists the missing ones in this order
+    void require(std::initializer_list<Labelled> wanted) const {
+        std::string missing;
+        for (const auto &[name, label] : wanted)
+            if (!has(name)) missing += std::string("\n  ") + label;
+        if (!missing.empty()) throw UsageError("the following required arguments were not provided:" + missing);
+    }
+    void conflict(const Labelled &a, const Labelled &b) const {
+        if (has(a.first) && has(b.first)) throw UsageError(std::string("the argument '") + a.second + "' cannot be used with '" + b.second + "'");
+    }
+    // a required group of two options
+    void exactly_one(const char *a, const char *label_a, const char *b, const char *label_b) const {
+        conflict({a, label_a}, {b, label_b});
+        if (!has(a) && !has(b)) require({{a, (std::string("<") + label_a + "|" + label_b + ">").c_str()}});
+    }
+    // the place of the option's value among `values`; 0 without the option
+    int choice(const char *name, const char *label, std::initializer_list<const char *> values) const {
+        if (!has(name)) return 0;
+        std::string all;
+        int k = 0;
+        for (const char *v : values) {
+            if (str(name) == v) return k;
+            all += (k++ ? ", " : "") + std::string(v);
+        }
+        throw UsageError("invalid value '" + str(name) + "' for '" + label + "'\n  [possible values: " + all + "]");
+    }
+    // ---- the blocks every command repeats
+    void common(std::string &input, std::optional<std::string> &output, size_t &threads, bool &verbose, const char *threads_label = "--threads <NUM>") const {
+        input = str("input");
+        output = opt("output");
+        threads = size("threads", threads_label, threads);
+        verbose = has("verbose");
+    }
+    void common(CommonArgs &c) const { common(c.input, c.output, c.threads, c.verbose); }
+    void group_filters(CommonArgs &c) const {  // -e and -T of intersect, extract and search
+        c.entire_group = has("entire_group");
+        c.types = opt("types");
+    }
+    int device() const { return static_cast<int>(size("device", "--device <N>", 0)); }
+    int gpus() const { return static_cast<int>(std::max<size_t>(1, std::min<size_t>(64, size("gpus", "--gpus <N>", 1)))); }
+    void stats_json() const {
+        if (has("stats-json")) g_run_stats.path = str("stats-json");
+    }
+
+  private:
+    std::map<std::string, std::vector<std::string>> got_;
+};
+
+constexpr const char *kInput = "--input <FILE>", *kSource = "--source <SOURCE>", *kRegion = "--region <REGION>", *kBed = "--bed <BED>",
+                     *kTypes = "--types <T1,T2,...>";
+
+void run_intersect_cli(const Opts &o) {
     commands::intersect::IntersectArgs a;
-    if (!o.count("input")) throw UsageError("the following required arguments were not provided:\n  --input <FILE>");
-    a.common.input = o.at("input")[0];
-    if (o.count("output")) a.common.output = o.at("output")[0];
-    a.common.entire_group = o.count("entire_group") > 0;
-    if (o.count("types")) a.common.types = o.at("types")[0];
-    if (o.count("threads")) a.common.threads = parse_size(o.at("threads")[0], "--threads <NUM>");
-    a.common.verbose = o.count("verbose") > 0;
-    if (o.count("region")) a.region = o.at("region")[0];
-    if (o.count("bed")) a.bed = o.at("bed")[0];
-    // ArgGroup "regions": required, exactly one (intersect.rs:37-39)
-    if (a.region && a.bed)
-        throw UsageError("the argument '--region <REGION>' cannot be used with '--bed <BED>'");
-    if (!a.region && !a.bed)
-        throw UsageError("the following required arguments were not provided:\n  <--region <REGION>|--bed <BED>>");
-    a.contained = o.count("contained") > 0;
-    a.contains_region = o.count("contains-region") > 0;
-    a.overlap = o.count("overlap") > 0;
+    o.require({{"input", kInput}});
+    o.common(a.common);
+    o.group_filters(a.common);
+    o.exactly_one("region", kRegion, "bed", kBed);  // ArgGroup "regions": required, exactly one (intersect.rs:37-39)
+    a.region = o.opt("region");
+    a.bed = o.opt("bed");
+    a.contained = o.has("contained");
+    a.contains_region = o.has("contains-region");
+    a.overlap = o.has("overlap");
     if (a.contained + a.contains_region + a.overlap > 1)  // ArgGroup "mode" (intersect.rs:40-42)
         throw UsageError("the arguments '--contained', '--contains-region' and '--overlap' cannot be used together");
-    a.invert = o.count("invert") > 0;
-    if (o.count("device")) a.device = static_cast<int>(parse_size(o.at("device")[0], "--device <N>"));
-    if (o.count("gpus")) a.gpus = static_cast<int>(std::max<size_t>(1, std::min<size_t>(64, parse_size(o.at("gpus")[0], "--gpus <N>"))));
-    if (o.count("stats-json")) g_run_stats.path = o.at("stats-json")[0];
+    a.invert = o.has("invert");
+    a.device = o.device();
+    a.gpus = o.gpus();
+    o.stats_json();
     commands::intersect::run(a);
-    return 0;
 }
 
-int run_extract_cli(int argc, char **argv) {
-    static const std::vector<OptSpec> specs = {
-        {'i', "input", true},   {'o', "output", true},   {'e', "entire_group", false}, {'T', "types", true},
-        {'t', "threads", true}, {'v', "verbose", false}, {'f', "feature-id", true},    {'F', "feature-file", true},
-        {0, "device", true},    {0, "stats-json", true}, {'h', "help", false}};
-    const auto o = parse_opts(argc, argv, 2, specs);
-    if (o.count("help")) {
-        std::fputs(kExtractUsage, stdout);
-        return 0;
-    }
+void run_extract_cli(const Opts &o) {
     commands::extract::ExtractArgs a;
-    if (!o.count("input")) throw UsageError("the following required arguments were not provided:\n  --input <FILE>");
-    a.common.input = o.at("input")[0];
-    if (o.count("output")) a.common.output = o.at("output")[0];
-    a.common.entire_group = o.count("entire_group") > 0;
-    if (o.count("types")) a.common.types = o.at("types")[0];
-    if (o.count("threads")) a.common.threads = parse_size(o.at("threads")[0], "--threads <NUM>");
-    a.common.verbose = o.count("verbose") > 0;
-    if (o.count("feature-id")) a.feature_id = o.at("feature-id")[0];
-    if (o.count("feature-file")) a.feature_file = o.at("feature-file")[0];
-    // ArgGroup "feature": required, exactly one (extract.rs:21-25)
-    if (a.feature_id && a.feature_file)
-        throw UsageError("the argument '--feature-id <FEATURE_ID>' cannot be used with '--feature-file <FEATURE_FILE>'");
-    if (!a.feature_id && !a.feature_file)
-        throw UsageError("the following required arguments were not provided:\n  <--feature-file <FEATURE_FILE>|--feature-id <FEATURE_ID>>");
-    if (o.count("device")) a.device = static_cast<int>(parse_size(o.at("device")[0], "--device <N>"));
-    if (o.count("stats-json")) g_run_stats.path = o.at("stats-json")[0];
+    o.require({{"input", kInput}});
+    o.common(a.common);
+    o.group_filters(a.common);
+    // ArgGroup "feature": required, exactly one (extract.rs:21-25); clap names the pair one way round in the conflict and
+    // the other way round in the usage
+    o.conflict({"feature-id", "--feature-id <FEATURE_ID>"}, {"feature-file", "--feature-file <FEATURE_FILE>"});
+    o.exactly_one("feature-file", "--feature-file <FEATURE_FILE>", "feature-id", "--feature-id <FEATURE_ID>");
+    a.feature_id = o.opt("feature-id");
+    a.feature_file = o.opt("feature-file");
+    a.device = o.device();
+    o.stats_json();
     commands::extract::run_extract(a);
-    return 0;
 }
 
-int run_search_cli(int argc, char **argv) {
-    static const std::vector<OptSpec> specs = {
-        {'i', "input", true},   {'o', "output", true},   {'e', "entire_group", false}, {'T', "types", true},
-        {'t', "threads", true}, {'v', "verbose", false}, {'A', "attr-list", true},     {'a', "attr", true},
-        {'r', "regex", false},  {0, "device", true},     {0, "stats-json", true},      {'h', "help", false}};
-    const auto o = parse_opts(argc, argv, 2, specs);
-    if (o.count("help")) {
-        std::fputs(kSearchUsage, stdout);
-        return 0;
-    }
+void run_search_cli(const Opts &o) {
     commands::search::SearchArgs a;
-    if (!o.count("input")) throw UsageError("the following required arguments were not provided:\n  --input <FILE>");
-    a.common.input = o.at("input")[0];
-    if (o.count("output")) a.common.output = o.at("output")[0];
-    a.common.entire_group = o.count("entire_group") > 0;
-    if (o.count("types")) a.common.types = o.at("types")[0];
-    if (o.count("threads")) a.common.threads = parse_size(o.at("threads")[0], "--threads <NUM>");
-    a.common.verbose = o.count("verbose") > 0;
-    if (o.count("attr-list")) a.attr_list = o.at("attr-list")[0];
-    if (o.count("attr")) a.attr = o.at("attr")[0];
-    a.regex = o.count("regex") > 0;
-    // ArgGroup "attr_input": required, exactly one (search.rs:19-24)
-    if (a.attr_list && a.attr) throw UsageError("the argument '--attr-list <ATTR_LIST>' cannot be used with '--attr <ATTR>'");
-    if (!a.attr_list && !a.attr)
-        throw UsageError("the following required arguments were not provided:\n  <--attr-list <ATTR_LIST>|--attr <ATTR>>");
-    if (o.count("device")) a.device = static_cast<int>(parse_size(o.at("device")[0], "--device <N>"));
-    if (o.count("stats-json")) g_run_stats.path = o.at("stats-json")[0];
+    o.require({{"input", kInput}});
+    o.common(a.common);
+    o.group_filters(a.common);
+    o.exactly_one("attr-list", "--attr-list <ATTR_LIST>", "attr", "--attr <ATTR>");  // ArgGroup "attr_input" (search.rs:19-24)
+    a.attr_list = o.opt("attr-list");
+    a.attr = o.opt("attr");
+    a.regex = o.has("regex");
+    a.device = o.device();
+    o.stats_json();
     commands::search::run_search(a);
-    return 0;
 }
 
-int run_depth_cli(int argc, char **argv) {
-    static const std::vector<OptSpec> specs = {{'i', "input", true},   {'s', "source", true},   {'o', "output", true},
-                                               {0, "bin-shift", true}, {'t', "threads", true},  {'v', "verbose", false},
-                                               {0, "device", true},    {0, "gpus", true},       {0, "stats-json", true}, {'h', "help", false}};
-    const auto o = parse_opts(argc, argv, 2, specs);
-    if (o.count("help")) {
-        std::fputs(kDepthUsage, stdout);
-        return 0;
-    }
+void run_depth_cli(const Opts &o) {
     commands::depth::DepthArgs a;
-    if (!o.count("input") || !o.count("source"))
-        throw UsageError(std::string("the following required arguments were not provided:") +
-                         (o.count("input") ? "" : "\n  --input <FILE>") + (o.count("source") ? "" : "\n  --source <SOURCE>"));
-    a.input = o.at("input")[0];
-    a.source = o.at("source")[0];
-    if (o.count("output")) a.output = o.at("output")[0];
-    if (o.count("bin-shift")) a.bin_shift = static_cast<uint32_t>(parse_size(o.at("bin-shift")[0], "--bin-shift <BIN_SHIFT>"));
-    if (o.count("threads")) a.threads = parse_size(o.at("threads")[0], "--threads <THREADS>");
-    a.verbose = o.count("verbose") > 0;
-    if (o.count("device")) a.device = static_cast<int>(parse_size(o.at("device")[0], "--device <N>"));
-    if (o.count("gpus")) a.gpus = static_cast<int>(std::max<size_t>(1, std::min<size_t>(64, parse_size(o.at("gpus")[0], "--gpus <N>"))));
-    if (o.count("stats-json")) g_run_stats.path = o.at("stats-json")[0];
+    o.require({{"input", kInput}, {"source", kSource}});
+    a.source = o.str("source");
+    a.bin_shift = static_cast<uint32_t>(o.size("bin-shift", "--bin-shift <BIN_SHIFT>", a.bin_shift));
+    o.common(a.input, a.output, a.threads, a.verbose, "--threads <THREADS>");
+    a.device = o.device();
+    a.gpus = o.gpus();
+    o.stats_json();
     commands::depth::run(a);
-    return 0;
 }
 
 // --thresholds T1,T2,...: one to eight integers in 1 .. 4294967295, no duplicates
@@ -421,70 +413,33 @@ std::vector<uint32_t> parse_thresholds(const std::string &v) {
     return out;
 }
 
-int run_coverage_cli(int argc, char **argv) {
-    static const std::vector<OptSpec> specs = {{'i', "input", true},   {'s', "source", true},   {'o', "output", true},
-                                               {'t', "threads", true}, {'v', "verbose", false}, {0, "device", true},
-                                               {0, "gpus", true},      {0, "stats-json", true}, {0, "mean-depth", false},
-                                               {0, "thresholds", true}, {0, "bedgraph", true},  {'h', "help", false}};
-    const auto o = parse_opts(argc, argv, 2, specs);
-    if (o.count("help")) {
-        std::fputs(kCoverageUsage, stdout);
-        return 0;
-    }
+void run_coverage_cli(const Opts &o) {
     commands::coverage::CoverageArgs a;
-    if (!o.count("input") || !o.count("source"))
-        throw UsageError(std::string("the following required arguments were not provided:") +
-                         (o.count("input") ? "" : "\n  --input <FILE>") + (o.count("source") ? "" : "\n  --source <SOURCE>"));
-    a.input = o.at("input")[0];
-    a.source = o.at("source")[0];
-    if (o.count("output")) a.output = o.at("output")[0];
-    if (o.count("threads")) a.threads = parse_size(o.at("threads")[0], "--threads <NUM>");
-    a.verbose = o.count("verbose") > 0;
-    if (o.count("device")) a.device = static_cast<int>(parse_size(o.at("device")[0], "--device <N>"));
-    if (o.count("gpus")) a.gpus = static_cast<int>(std::max<size_t>(1, std::min<size_t>(64, parse_size(o.at("gpus")[0], "--gpus <N>"))));
-    if (o.count("stats-json")) g_run_stats.path = o.at("stats-json")[0];
-    a.mean_depth = o.count("mean-depth") > 0;
-    if (o.count("thresholds")) a.thresholds = parse_thresholds(o.at("thresholds")[0]);
-    if (o.count("bedgraph")) a.bedgraph = o.at("bedgraph")[0];
+    o.require({{"input", kInput}, {"source", kSource}});
+    a.source = o.str("source");
+    o.common(a.input, a.output, a.threads, a.verbose);
+    a.device = o.device();
+    a.gpus = o.gpus();
+    o.stats_json();
+    a.mean_depth = o.has("mean-depth");
+    if (o.has("thresholds")) a.thresholds = parse_thresholds(o.str("thresholds"));
+    a.bedgraph = o.opt("bedgraph");
     commands::coverage::run(a);
-    return 0;
 }
 
-int run_closest_cli(int argc, char **argv) {
-    static const std::vector<OptSpec> specs = {{'i', "input", true},   {'o', "output", true},          {'r', "region", true}, {'b', "bed", true},
-                                               {0, "ignore-overlaps", false}, {0, "side", true},       {'t', "threads", true}, {'v', "verbose", false},
-                                               {0, "device", true},    {0, "stats-json", true},        {'h', "help", false}};
-    const auto o = parse_opts(argc, argv, 2, specs);
-    if (o.count("help")) {
-        std::fputs(kClosestUsage, stdout);
-        return 0;
-    }
+void run_closest_cli(const Opts &o) {
     commands::closest::ClosestArgs a;
-    if (!o.count("input")) throw UsageError("the following required arguments were not provided:\n  --input <FILE>");
-    a.common.input = o.at("input")[0];
-    if (o.count("output")) a.common.output = o.at("output")[0];
-    if (o.count("threads")) a.common.threads = parse_size(o.at("threads")[0], "--threads <NUM>");
-    a.common.verbose = o.count("verbose") > 0;
-    if (o.count("region")) a.region = o.at("region")[0];
-    if (o.count("bed")) a.bed = o.at("bed")[0];
-    if (a.region && a.bed) throw UsageError("the argument '--region <REGION>' cannot be used with '--bed <BED>'");
-    if (!a.region && !a.bed) throw UsageError("the following required arguments were not provided:\n  <--region <REGION>|--bed <BED>>");
-    a.ignore_overlaps = o.count("ignore-overlaps") > 0;
-    if (o.count("side")) {
-        const std::string &v = o.at("side")[0];
-        if (v == "both")
-            a.side = commands::closest::Side::Both;
-        else if (v == "left")
-            a.side = commands::closest::Side::Left;
-        else if (v == "right")
-            a.side = commands::closest::Side::Right;
-        else
-            throw UsageError("invalid value '" + v + "' for '--side <SIDE>'\n  [possible values: both, left, right]");
-    }
-    if (o.count("device")) a.device = static_cast<int>(parse_size(o.at("device")[0], "--device <N>"));
-    if (o.count("stats-json")) g_run_stats.path = o.at("stats-json")[0];
+    o.require({{"input", kInput}});
+    o.common(a.common);
+    o.exactly_one("region", kRegion, "bed", kBed);
+    a.region = o.opt("region");
+    a.bed = o.opt("bed");
+    a.ignore_overlaps = o.has("ignore-overlaps");
+    const commands::closest::Side sides[] = {commands::closest::Side::Both, commands::closest::Side::Left, commands::closest::Side::Right};
+    a.side = sides[o.choice("side", "--side <SIDE>", {"both", "left", "right"})];
+    a.device = o.device();
+    o.stats_json();
     commands::closest::run(a);
-    return 0;
 }
 
 // -T: one to 32 names, none empty, none twice
@@ -504,118 +459,60 @@ std::vector<std::string> parse_layers(const std::string &v) {
     return layers;
 }
 
-int run_annotate_cli(int argc, char **argv) {
-    static const std::vector<OptSpec> specs = {{'i', "input", true},   {'o', "output", true},  {'r', "region", true}, {'b', "bed", true},
-                                               {'T', "types", true},   {0, "summary", true},   {'t', "threads", true}, {'v', "verbose", false},
-                                               {0, "device", true},    {0, "stats-json", true}, {'h', "help", false}};
-    const auto o = parse_opts(argc, argv, 2, specs);
-    if (o.count("help")) {
-        std::fputs(kAnnotateUsage, stdout);
-        return 0;
-    }
+void run_annotate_cli(const Opts &o) {
     commands::annotate::AnnotateArgs a;
-    if (!o.count("input")) throw UsageError("the following required arguments were not provided:\n  --input <FILE>");
-    a.common.input = o.at("input")[0];
-    if (o.count("output")) a.common.output = o.at("output")[0];
-    if (o.count("threads")) a.common.threads = parse_size(o.at("threads")[0], "--threads <NUM>");
-    a.common.verbose = o.count("verbose") > 0;
-    if (o.count("region")) a.region = o.at("region")[0];
-    if (o.count("bed")) a.bed = o.at("bed")[0];
-    if (a.region && a.bed) throw UsageError("the argument '--region <REGION>' cannot be used with '--bed <BED>'");
-    if (!a.region && !a.bed) throw UsageError("the following required arguments were not provided:\n  <--region <REGION>|--bed <BED>>");
-    if (!o.count("types")) throw UsageError("the following required arguments were not provided:\n  --types <T1,T2,...>");
-    a.layers = parse_layers(o.at("types")[0]);
-    if (o.count("summary")) a.summary = o.at("summary")[0];
-    if (o.count("device")) a.device = static_cast<int>(parse_size(o.at("device")[0], "--device <N>"));
-    if (o.count("stats-json")) g_run_stats.path = o.at("stats-json")[0];
+    o.require({{"input", kInput}});
+    o.common(a.common);
+    o.exactly_one("region", kRegion, "bed", kBed);
+    a.region = o.opt("region");
+    a.bed = o.opt("bed");
+    o.require({{"types", kTypes}});
+    a.layers = parse_layers(o.str("types"));
+    a.summary = o.opt("summary");
+    a.device = o.device();
+    o.stats_json();
     commands::annotate::run(a);
-    return 0;
 }
 
-int run_enrich_cli(int argc, char **argv) {
-    static const std::vector<OptSpec> specs = {{'i', "input", true},   {'o', "output", true},       {'b', "bed", true},     {'T', "types", true},
-                                               {'n', "permutations", true}, {0, "seed", true},      {'g', "genome", true},  {0, "perms", true},
-                                               {'t', "threads", true}, {'v', "verbose", false},     {0, "device", true},    {0, "stats-json", true},
-                                               {'h', "help", false}};
-    const auto o = parse_opts(argc, argv, 2, specs);
-    if (o.count("help")) {
-        std::fputs(kEnrichUsage, stdout);
-        return 0;
-    }
+void run_enrich_cli(const Opts &o) {
     commands::enrich::EnrichArgs a;
-    std::string missing;
-    for (const char *name : {"input", "bed", "types", "permutations"})
-        if (!o.count(name))
-            missing += std::string("\n  --") + name + (std::string(name) == "input" ? " <FILE>" : std::string(name) == "bed" ? " <BED>" : std::string(name) == "types" ? " <T1,T2,...>" : " <N>");
-    if (!missing.empty()) throw UsageError("the following required arguments were not provided:" + missing);
-    a.common.input = o.at("input")[0];
-    if (o.count("output")) a.common.output = o.at("output")[0];
-    if (o.count("threads")) a.common.threads = parse_size(o.at("threads")[0], "--threads <NUM>");
-    a.common.verbose = o.count("verbose") > 0;
-    a.bed = o.at("bed")[0];
-    a.layers = parse_layers(o.at("types")[0]);
-    {
-        const std::string &v = o.at("permutations")[0];
-        const size_t n = parse_size(v, "--permutations <N>");
-        if (n < 1 || n > (1u << 20)) throw UsageError("invalid value '" + v + "' for '--permutations <N>': 1 to 1048576 are possible");
-        a.n_perm = static_cast<uint32_t>(n);
-    }
-    if (o.count("seed")) {
-        const std::string &v = o.at("seed")[0];
+    o.require({{"input", kInput}, {"bed", kBed}, {"types", kTypes}, {"permutations", "--permutations <N>"}});
+    o.common(a.common);
+    a.bed = o.str("bed");
+    a.layers = parse_layers(o.str("types"));
+    const size_t n = o.size("permutations", "--permutations <N>", 0);
+    if (n < 1 || n > (1u << 20)) throw UsageError("invalid value '" + o.str("permutations") + "' for '--permutations <N>': 1 to 1048576 are possible");
+    a.n_perm = static_cast<uint32_t>(n);
+    if (o.has("seed")) {
+        const std::string &v = o.str("seed");
         char *end = nullptr;
         errno = 0;
         const unsigned long long s = std::strtoull(v.c_str(), &end, 10);
         if (v.empty() || v[0] < '0' || v[0] > '9' || *end || errno == ERANGE) throw UsageError("invalid value '" + v + "' for '--seed <S>': a number below 2^64 is expected");
         a.seed = s;
     }
-    if (o.count("genome")) a.genome = o.at("genome")[0];
-    if (o.count("perms")) a.perms = o.at("perms")[0];
-    if (o.count("device")) a.device = static_cast<int>(parse_size(o.at("device")[0], "--device <N>"));
-    if (o.count("stats-json")) g_run_stats.path = o.at("stats-json")[0];
+    a.genome = o.opt("genome");
+    a.perms = o.opt("perms");
+    a.device = o.device();
+    o.stats_json();
     commands::enrich::run(a);
-    return 0;
 }
 
-int run_meta_cli(int argc, char **argv) {
-    static const std::vector<OptSpec> specs = {{'i', "input", true},    {'s', "source", true},     {'o', "output", true},  {'T', "types", true},
-                                               {0, "anchor", true},     {0, "scale", true},        {'u', "upstream", true}, {'d', "downstream", true},
-                                               {'w', "bin", true},      {'g', "genome", true},     {0, "matrix", true},    {'t', "threads", true},
-                                               {'v', "verbose", false}, {0, "device", true},       {0, "gpus", true},      {0, "stats-json", true},
-                                               {'h', "help", false}};
-    const auto o = parse_opts(argc, argv, 2, specs);
-    if (o.count("help")) {
-        std::fputs(kMetaUsage, stdout);
-        return 0;
-    }
+void run_meta_cli(const Opts &o) {
     commands::meta::MetaArgs a;
-    if (!o.count("input") || !o.count("source"))
-        throw UsageError(std::string("the following required arguments were not provided:") + (o.count("input") ? "" : "\n  --input <FILE>") +
-                         (o.count("source") ? "" : "\n  --source <SOURCE>"));
-    a.common.input = o.at("input")[0];
-    a.source = o.at("source")[0];
-    if (o.count("output")) a.common.output = o.at("output")[0];
-    if (o.count("threads")) a.common.threads = parse_size(o.at("threads")[0], "--threads <NUM>");
-    a.common.verbose = o.count("verbose") > 0;
-    if (o.count("types")) a.types = parse_layers(o.at("types")[0]);
-    if (o.count("anchor") && o.count("scale")) throw UsageError("the argument '--anchor <ANCHOR>' cannot be used with '--scale <M>'");
+    o.require({{"input", kInput}, {"source", kSource}});
+    a.source = o.str("source");
+    o.common(a.common);
+    if (o.has("types")) a.types = parse_layers(o.str("types"));
+    o.conflict({"anchor", "--anchor <ANCHOR>"}, {"scale", "--scale <M>"});
     gffx_hip_meta_layout &y = a.layout;
-    if (o.count("anchor")) {
-        const std::string &v = o.at("anchor")[0];
-        if (v == "tss")
-            y.anchor = 0;
-        else if (v == "tes")
-            y.anchor = 1;
-        else if (v == "center")
-            y.anchor = 2;
-        else
-            throw UsageError("invalid value '" + v + "' for '--anchor <ANCHOR>'\n  [possible values: tss, tes, center]");
-    }
-    if (o.count("upstream")) y.up = static_cast<uint32_t>(parse_size(o.at("upstream")[0], "--upstream <UP>"));
-    if (o.count("downstream")) y.down = static_cast<uint32_t>(parse_size(o.at("downstream")[0], "--downstream <DOWN>"));
-    if (o.count("bin")) y.bin = static_cast<uint32_t>(parse_size(o.at("bin")[0], "--bin <BIN>"));
-    if (o.count("scale")) {
+    y.anchor = static_cast<uint32_t>(o.choice("anchor", "--anchor <ANCHOR>", {"tss", "tes", "center"}));
+    y.up = static_cast<uint32_t>(o.size("upstream", "--upstream <UP>", y.up));
+    y.down = static_cast<uint32_t>(o.size("downstream", "--downstream <DOWN>", y.down));
+    y.bin = static_cast<uint32_t>(o.size("bin", "--bin <BIN>", y.bin));
+    if (o.has("scale")) {
         y.mode = 1;
-        y.body_bins = static_cast<uint32_t>(parse_size(o.at("scale")[0], "--scale <M>"));
+        y.body_bins = static_cast<uint32_t>(o.size("scale", "--scale <M>", 0));
         if (y.body_bins == 0) throw UsageError("invalid value '0' for '--scale <M>': at least one body column is needed");
     }
     if (y.bin == 0) throw UsageError("invalid value '0' for '--bin <BIN>': a column has at least one base");
@@ -625,73 +522,72 @@ int run_meta_cli(int argc, char **argv) {
     if (gffx_hip_pileup_meta_columns(&y) > gffx_hip_pileup_meta_max_columns())
         throw UsageError(std::to_string(gffx_hip_pileup_meta_columns(&y)) + " columns exceed the limit of " + std::to_string(gffx_hip_pileup_meta_max_columns()) +
                          ": choose a larger --bin or a smaller --scale");
-    if (o.count("genome")) a.genome = o.at("genome")[0];
-    if (o.count("matrix")) a.matrix = o.at("matrix")[0];
-    if (o.count("device")) a.device = static_cast<int>(parse_size(o.at("device")[0], "--device <N>"));
-    if (o.count("gpus")) a.gpus = static_cast<int>(std::max<size_t>(1, std::min<size_t>(64, parse_size(o.at("gpus")[0], "--gpus <N>"))));
-    if (o.count("stats-json")) g_run_stats.path = o.at("stats-json")[0];
+    a.genome = o.opt("genome");
+    a.matrix = o.opt("matrix");
+    a.device = o.device();
+    a.gpus = o.gpus();
+    o.stats_json();
     commands::meta::run(a);
-    return 0;
 }
 
-int run_index_cli(int argc, char **argv) {
-    static const std::vector<OptSpec> specs = {{'i', "input", true},
-                                               {'a', "attribute", true},
-                                               {'s', "skip-types", true},
-                                               {'v', "verbose", false},
-                                               {'g', "gpu", false},
-                                               {0, "device", true},
-                                               {'h', "help", false}};
-    const auto o = parse_opts(argc, argv, 2, specs);
-    if (o.count("help")) {
-        std::fputs(kIndexUsage, stdout);
-        return 0;
-    }
-    if (!o.count("input")) throw UsageError("the following required arguments were not provided:\n  --input <INPUT>");
-    const std::string input = o.at("input")[0];
-    const std::string attr = o.count("attribute") ? o.at("attribute")[0] : "gene_name";  // commands/index.rs:15
-    const std::string skip = o.count("skip-types")
-                                 ? o.at("skip-types")[0]
-                                 : "remark,note,comment,region,gap,assembly_gap,contig,scaffold,source";  // :18
-    const bool verbose = o.count("verbose") > 0;
+void run_index_cli(const Opts &o) {
+    o.require({{"input", "--input <INPUT>"}});
+    const std::string &input = o.str("input");
+    const std::string attr = o.has("attribute") ? o.str("attribute") : "gene_name";  // commands/index.rs:15
+    const std::string skip = o.has("skip-types") ? o.str("skip-types") : "remark,note,comment,region,gap,assembly_gap,contig,scaffold,source";  // :18
+    const bool verbose = o.has("verbose");
     if (verbose) std::printf("Indexing: %s\n", input.c_str());  // commands/index.rs:26-28
-    // addition: --gpu builds the same eight files from arrays made on the device (GFFX_INDEX_CHUNK_BYTES: the text per pass)
-    if (o.count("gpu"))
-        build_index_device(input, attr, skip, o.count("device") ? static_cast<int>(parse_size(o.at("device")[0], "--device <N>")) : 0, verbose);
+    // addition: --gpu builds the same eight files from arrays made on the device (GFFX_INDEX_CHUNK_BYTES: the text per pass);
+    // --device is read with it only
+    if (o.has("gpu"))
+        build_index_device(input, attr, skip, o.device(), verbose);
     else
         build_index(input, attr, skip, verbose);
-    // addition: the all-line SoA image `<gff>.lsoa` for depth / coverage (block_table.cpp); GFFX_LINE_TABLE=off skips it
-    const char *lt = std::getenv("GFFX_LINE_TABLE");
-    if (!(lt && std::string(lt) == "off")) {
-        const index_loader::GofMap gof = index_loader::load_gof(input);
-        const MappedFile text(input);
-        unsigned hw = std::thread::hardware_concurrency();
-        // Both images are optional accelerators (the commands fall back to the text walk without them): a failure to write one
-        // -- a full or read-only directory, a quota -- is a warning, the partial file is removed, and the index the reference
-        // defines (the eight side-cars above) stands.
-        try {
-            const auto t = commands::depth::build_block_table(gof, text.view(), std::min(hw ? hw : 1u, 12u));
-            commands::depth::write_block_table(append_suffix(input, ".lsoa"), t, text.size(), index_loader::line_table_key(input, gof));
-            if (verbose) std::printf("Line table image: %zu lines in %zu blocks.\n", t.line_start.size(), t.block_line_off.size() - 1);
-        } catch (const Error &e) {
-            std::fprintf(stderr, "[WARN] line table image %s not written: %s\n", append_suffix(input, ".lsoa").c_str(), e.what());
-            std::remove(append_suffix(input, ".lsoa").c_str());
-        }
-        // ... and the all-line table `<gff>.lall` of intersect's per-line mode (line_index.cpp)
-        try {
-            const auto all = commands::intersect::build_all_lines(text.view(), std::min(hw ? hw : 1u, 12u));
-            commands::intersect::write_all_lines(append_suffix(input, ".lall"), all, text.size(), index_loader::line_table_key(input, gof));
-            if (verbose) std::printf("All-line table: %zu lines, %zu seqid names, %zu types.\n", all.ls.size(), all.seq_names.size(), all.type_names.size());
-        } catch (const Error &e) {
-            std::fprintf(stderr, "[WARN] all-line table %s not written: %s\n", append_suffix(input, ".lall").c_str(), e.what());
-            std::remove(append_suffix(input, ".lall").c_str());
-        }
-    } else {
-        std::remove(append_suffix(input, ".lsoa").c_str());  // an image of an earlier index run would be stale
-        std::remove(append_suffix(input, ".lall").c_str());
-    }
+    write_line_images(input, verbose);
     if (verbose) std::printf("Index created successfully.\n");
-    return 0;
+}
+
+// The subcommands in the order of the top-level help; every one also takes -h / --help.
+struct Command {
+    const char *name, *usage;
+    void (*run)(const Opts &);
+    std::vector<OptSpec> specs;
+};
+const std::vector<Command> &commands_table() {
+    static const std::vector<Command> table = {
+        {"index", kIndexUsage, run_index_cli,
+         {{'i', "input", true}, {'a', "attribute", true}, {'s', "skip-types", true}, {'v', "verbose", false}, {'g', "gpu", false}, {0, "device", true}}},
+        {"intersect", kIntersectUsage, run_intersect_cli,
+         {{'i', "input", true}, {'o', "output", true}, {'e', "entire_group", false}, {'T', "types", true}, {'t', "threads", true}, {'v', "verbose", false},
+          {'r', "region", true}, {'b', "bed", true}, {'c', "contained", false}, {'C', "contains-region", false}, {'O', "overlap", false}, {'I', "invert", false},
+          {0, "device", true}, {0, "gpus", true}, {0, "stats-json", true}}},
+        {"extract", kExtractUsage, run_extract_cli,
+         {{'i', "input", true}, {'o', "output", true}, {'e', "entire_group", false}, {'T', "types", true}, {'t', "threads", true}, {'v', "verbose", false},
+          {'f', "feature-id", true}, {'F', "feature-file", true}, {0, "device", true}, {0, "stats-json", true}}},
+        {"search", kSearchUsage, run_search_cli,
+         {{'i', "input", true}, {'o', "output", true}, {'e', "entire_group", false}, {'T', "types", true}, {'t', "threads", true}, {'v', "verbose", false},
+          {'A', "attr-list", true}, {'a', "attr", true}, {'r', "regex", false}, {0, "device", true}, {0, "stats-json", true}}},
+        {"depth", kDepthUsage, run_depth_cli,
+         {{'i', "input", true}, {'s', "source", true}, {'o', "output", true}, {0, "bin-shift", true}, {'t', "threads", true}, {'v', "verbose", false},
+          {0, "device", true}, {0, "gpus", true}, {0, "stats-json", true}}},
+        {"coverage", kCoverageUsage, run_coverage_cli,
+         {{'i', "input", true}, {'s', "source", true}, {'o', "output", true}, {'t', "threads", true}, {'v', "verbose", false}, {0, "device", true},
+          {0, "gpus", true}, {0, "stats-json", true}, {0, "mean-depth", false}, {0, "thresholds", true}, {0, "bedgraph", true}}},
+        {"closest", kClosestUsage, run_closest_cli,
+         {{'i', "input", true}, {'o', "output", true}, {'r', "region", true}, {'b', "bed", true}, {0, "ignore-overlaps", false}, {0, "side", true},
+          {'t', "threads", true}, {'v', "verbose", false}, {0, "device", true}, {0, "stats-json", true}}},
+        {"annotate", kAnnotateUsage, run_annotate_cli,
+         {{'i', "input", true}, {'o', "output", true}, {'r', "region", true}, {'b', "bed", true}, {'T', "types", true}, {0, "summary", true},
+          {'t', "threads", true}, {'v', "verbose", false}, {0, "device", true}, {0, "stats-json", true}}},
+        {"enrich", kEnrichUsage, run_enrich_cli,
+         {{'i', "input", true}, {'o', "output", true}, {'b', "bed", true}, {'T', "types", true}, {'n', "permutations", true}, {0, "seed", true},
+          {'g', "genome", true}, {0, "perms", true}, {'t', "threads", true}, {'v', "verbose", false}, {0, "device", true}, {0, "stats-json", true}}},
+        {"meta", kMetaUsage, run_meta_cli,
+         {{'i', "input", true}, {'s', "source", true}, {'o', "output", true}, {'T', "types", true}, {0, "anchor", true}, {0, "scale", true},
+          {'u', "upstream", true}, {'d', "downstream", true}, {'w', "bin", true}, {'g', "genome", true}, {0, "matrix", true}, {'t', "threads", true},
+          {'v', "verbose", false}, {0, "device", true}, {0, "gpus", true}, {0, "stats-json", true}}},
+    };
+    return table;
 }
 
 }  // namespace
@@ -705,45 +601,17 @@ int cli_main(int argc, char **argv) {
             std::fputs(kTopUsage, stdout);
             return 0;
         }
-        if (cmd == "intersect") {
-            usage = kIntersectUsage;
-            return run_intersect_cli(argc, argv);
-        }
-        if (cmd == "index") {
-            usage = kIndexUsage;
-            return run_index_cli(argc, argv);
-        }
-        if (cmd == "extract") {
-            usage = kExtractUsage;
-            return run_extract_cli(argc, argv);
-        }
-        if (cmd == "search") {
-            usage = kSearchUsage;
-            return run_search_cli(argc, argv);
-        }
-        if (cmd == "depth") {
-            usage = kDepthUsage;
-            return run_depth_cli(argc, argv);
-        }
-        if (cmd == "coverage") {
-            usage = kCoverageUsage;
-            return run_coverage_cli(argc, argv);
-        }
-        if (cmd == "closest") {
-            usage = kClosestUsage;
-            return run_closest_cli(argc, argv);
-        }
-        if (cmd == "annotate") {
-            usage = kAnnotateUsage;
-            return run_annotate_cli(argc, argv);
-        }
-        if (cmd == "enrich") {
-            usage = kEnrichUsage;
-            return run_enrich_cli(argc, argv);
-        }
-        if (cmd == "meta") {
-            usage = kMetaUsage;
-            return run_meta_cli(argc, argv);
+        for (const Command &c : commands_table()) {
+            if (cmd != c.name) continue;
+            usage = c.usage;
+            std::vector<OptSpec> specs = c.specs;
+            specs.push_back({'h', "help", false});
+            const Opts o(argc, argv, specs);
+            if (o.has("help"))
+                std::fputs(usage, stdout);
+            else
+                c.run(o);
+            return 0;
         }
         throw UsageError("unrecognized subcommand '" + cmd + "' (this build carries the intersect, extract, search, depth, coverage, closest, annotate, enrich and meta paths only)");
     } catch (const UsageError &e) {

@@ -14,21 +14,12 @@
 #include "genome_file.hpp"
 #include "intersect_internal.hpp"
 #include "layer_rows.hpp"
+#include "source_read.hpp"
 #include "table_output.hpp"
 
 namespace gffx::commands::meta {
 
 namespace {
-
-size_t batch_rows_from_env() {  // GFFX_META_BATCH_ROWS (gffx.hpp)
-    const char *e = std::getenv("GFFX_META_BATCH_ROWS");
-    if (e && *e) {
-        char *end = nullptr;
-        const unsigned long long v = std::strtoull(e, &end, 10);
-        if (end && !*end && v > 0) return static_cast<size_t>(std::min<unsigned long long>(v, 1ull << 28));
-    }
-    return 4u << 20;
-}
 
 // column j of the layout: its part and the offsets it spans (relative to the anchor, to the 5' end, in body columns, to the 3' end)
 void append_column_label(std::string &s, const gffx_hip_meta_layout &y, uint64_t j) {
@@ -81,8 +72,7 @@ void run(const MetaArgs &args) {
             f_id[i].assign(si.id);
             unstranded += !si.stranded;
         }
-        for (size_t k = 0; k < args.types.size(); ++k)
-            if (!per_type[k]) std::fprintf(stderr, "[WARN] no line of %s has type '%s'\n", args.common.input.c_str(), args.types[k].c_str());
+        layer_rows::report(args.common.input, args.types, per_type, "", nullptr, skipped);
         if (unstranded)
             std::fprintf(stderr, "[WARN] %llu features have neither '+' nor '-' in column 7 and were taken as '+'\n", (unsigned long long)unstranded);
         if (verbose)
@@ -111,7 +101,7 @@ void run(const MetaArgs &args) {
         double fold_ms = 0, meta_ms = 0;
     };
     std::vector<PerDevice> pd(D);
-    const size_t kBatch = batch_rows_from_env();
+    const size_t kBatch = source::batch_rows_from_env("GFFX_META_BATCH_ROWS");
     const size_t cap = std::max<size_t>(std::min(src.n_rows, kBatch), 1);
     parallel_for(D, D, [&](size_t d) {
         PerDevice &P = pd[d];

@@ -30,6 +30,18 @@ inline uint64_t chunk_bytes_from_env(const char *name, uint64_t fallback) {
     return fallback;
 }
 
+// the rows per device batch of depth, coverage and meta in the environment variable `name` (gffx.hpp): a positive decimal
+// number, capped at 1 << 28; anything else -- a sign or a blank in front too, which strtoull alone would take -- is ignored
+inline size_t batch_rows_from_env(const char *name) {
+    const char *e = std::getenv(name);
+    if (e && *e >= '0' && *e <= '9') {
+        char *end = nullptr;
+        const unsigned long long v = std::strtoull(e, &end, 10);
+        if (end && !*end && v > 0) return static_cast<size_t>(std::min<unsigned long long>(v, 1ull << 28));
+    }
+    return 4u << 20;
+}
+
 template <class H>
 struct Reader {  // the read-back entry points of a source handle, and its format's stage names (keys of --stats-json)
     int (*stage_ms)(const H *, double *, double *, double *);

@@ -51,6 +51,7 @@ def test_the_bytes_are_the_hand_written_text_on_every_route(inp):
     assert _run(inp, ["-b", inp["bed"]], {"GFFX_CHUNK_BYTES": "200"}) == (0, [], want)
     assert _run(inp, ["-b", inp["bed"]], {"GFFX_CHUNK_BYTES": "1"}) == (0, [], want)  # a chunk per line
     assert _run(inp, ["-b", inp["bed"]], {"GFFX_BED_DEVICE": "1"}) == (0, [], want)
+    assert _run(inp, ["-b", inp["bed"] + ".gz"], {"GFFX_CHUNK_BYTES": "12"}) == (0, [], want)  # the device reader's rows, two per slice
     assert _run(inp, ["-b", inp["bed"], "-t", "1"]) == (0, [], want)
     assert _run(inp, ["-b", inp["bed"], "-t", "16"], out=str(inp["dir"] / "out.tsv")) == (0, [], want)
     assert _run(inp, ["-b", inp["bed"]], {"GFFX_LINE_TABLE": "parse"}) == (0, [], want)  # without the .lall image

@@ -63,7 +63,7 @@ def test_the_definition_on_every_route(inp):
     assert unplaced == 2 and len({tuple(r) for r in B[1:].tolist()}) > 1  # chrA's regions do move now
     want_perms = ed.perms_text(B, R)
     routes = [([], None, None), ([], None, inp["bed"] + ".gz"), ([], {"GFFX_BED_DEVICE": "1"}, None), ([], {"GFFX_CHUNK_BYTES": "200"}, None),
-              ([], {"GFFX_CHUNK_BYTES": "1"}, None), (["-t", "1"], None, None), (["-t", "16"], {"GFFX_LINE_TABLE": "parse"}, None)]
+              ([], {"GFFX_CHUNK_BYTES": "1"}, None), ([], {"GFFX_CHUNK_BYTES": "12"}, inp["bed"] + ".gz"), (["-t", "1"], None, None), (["-t", "16"], {"GFFX_LINE_TABLE": "parse"}, None)]
     tables = set()
     for extra, knobs, bed in routes:
         rc, errors, warns, table, perms = _run(inp, ["-n", "20", "--seed", "5"] + extra, knobs, bed)

@@ -518,3 +518,81 @@ def test_refusals_leave_the_store_usable(world):
     big.wait()
     _assert_pairs_pass(big, world.oix, rows[:60], OverlapMode.Overlap, False, "the full store's last append")
     lt.close(), big.close(), small.close(), ring.close(), full.close()
+
+
+# ---------------------------------------------------------------------------------------------- the slot check of the seven consumers
+def test_every_consumer_refuses_rows_beyond_the_last_append(world):
+    """Four rows are appended from buffer 0.  Every entry point that reads a slot refuses first = 2^64 - 1 with two rows (the
+    sum wraps to 1) and first = 5 with none, with GFFX_E_INVALID and before anything is launched; the same call over the
+    four rows then gives what the object gives for the rows handed over from the host."""
+    pool = world.pool[world.pool[:, 1] < world.pool[:, 2]]
+    rows = np.ascontiguousarray(pool[40:44])
+    store = engine.RegionStore(0, 16, False)
+    store.staging(0)[:4] = rows
+    store.append(0, 4)
+    seg = (rows[:, 0], rows[:, 1], rows[:, 2] + 50)  # the pileup's segments: the rows themselves, a little longer
+
+    def refused(call):
+        for first, n in ((2 ** 64 - 1, 2), (5, 0)):
+            with pytest.raises(E) as ei:
+                call(first, n)
+            assert ei.value.code == -1 and "rows beyond the last append" in str(ei.value), (first, n)
+
+    def same(got, want):
+        got, want = (got, want) if isinstance(got, tuple) else ((got,), (want,))
+        assert len(got) == len(want) and all(np.array_equal(g, w) for g, w in zip(got, want))
+
+    b = engine.QueryBatch(world.ix, 16)
+    refused(lambda f, n: b.set_regions_store(store, 0, f, n))
+    b.set_regions_store(store, 0, 0, 4)
+    b.run(OverlapMode.Overlap, False, PAIRS)
+    b.wait()
+    _assert_pairs_pass(b, world.oix, rows, OverlapMode.Overlap, False, "after the refusals")
+    b.close()
+
+    u, want = engine.RegionUnion(N_SEQ), engine.RegionUnion(N_SEQ)
+    refused(lambda f, n: u.add_store(store, 0, f, n))
+    u.add_store(store, 0, 0, 4), u.finish()
+    want.add(rows), want.finish()
+    assert u.n_spans > 0
+    same(tuple(u.spans()), tuple(want.spans()))
+    u.close(), want.close()
+
+    p, want = engine.Pileup(N_SEQ, *seg), engine.Pileup(N_SEQ, *seg)
+    refused(lambda f, n: p.add_store(store, 0, f, n))
+    p.add_store(store, 0, 0, 4), want.add(rows)
+    assert p.bases().sum() > 0
+    same(p.bases(), want.bases())
+    p.close(), want.close()
+
+    d, want = engine.DepthProfile(N_SEQ), engine.DepthProfile(N_SEQ)
+    refused(lambda f, n: d.add_store(store, 0, f, n))
+    d.add_store(store, 0, 0, 4), d.finish()
+    want.add(rows), want.finish()
+    assert d.n_points > 0
+    same(tuple(d.points()), tuple(want.points()))
+    d.close(), want.close()
+
+    c = engine.Closest(world.ix, 16)
+    want = c.run(rows)
+    refused(lambda f, n: c.run_store(store, 0, f, n))
+    same(tuple(c.run_store(store, 0, 0, 4)), tuple(want))
+    c.close()
+
+    m = engine.ClassMap(N_SEQ, 2)
+    m.add_rows(np.array([[0, 0, 100, 60000], [1, 1, 5, 900000], [1, 0, 30000, 200000]], dtype=np.uint32))
+    m.finish()
+    want = m.run(rows)
+    refused(lambda f, n: m.run_store(store, 0, f, n))
+    same(tuple(m.run_store(store, 0, 0, 4)), tuple(want))
+    seq_len = np.full(N_SEQ, 1 << 28, dtype=np.uint32)
+    m.perm_begin(seq_len, 3, seed=7)
+    m.perm_run(rows)
+    want = m.perm_totals()
+    m.perm_begin(seq_len, 3, seed=7)
+    refused(lambda f, n: m.perm_run_store(store, 0, f, n))
+    m.perm_run_store(store, 0, 0, 4)
+    got = m.perm_totals()
+    assert got[2] == want[2]
+    same(got[:2], want[:2])
+    m.close(), store.close()
