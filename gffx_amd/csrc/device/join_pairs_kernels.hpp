@@ -40,7 +40,11 @@
 //   * a kept word is parked by TWO: v_add_co shifts the bit string's top bit into vcc, the LDS write and the advance of the
 //     lane's cursor run under that lane mask (s_and_saveexec / s_mov exec: scalar unit) -- no position arithmetic, no branch;
 //   * nothing that MAY issue a vector memory operation stands between the line loads and their use (a conditional store
-//     there makes the compiler wait for the loads with vmcnt(0), i.e. for the stores' acknowledgements too);
+//     there makes the compiler wait for the loads with vmcnt(0), i.e. for the stores' acknowledgements too); likewise behind
+//     every request of the next round's regions stands ONE unconditional memory operation, so that the wait for them is a counted
+//     one: with pair_load_round the counts store stands in FRONT of the request and the regions are waited for where they are
+//     unpacked, right behind it; with pair_request_round (QAHEAD) the counts store stands BEHIND the request and the regions are
+//     waited for at the next round's top;
 //   * the index view's twenty pointers stay in the kernarg segment and are only read on the rare paths.
 // The waves of a block cooperate as in round 3: a wave is the unit (no block barrier in the round loop); ONE pair segment per
 // block round is reserved by ARRIVAL in LDS -- the last wave to arrive issues the device atomic (same-address device atomics
@@ -753,6 +757,65 @@ __device__ __forceinline__ void pair_load_round(const QueryView &q, unsigned lon
     }
 }
 
+// The same in two steps (template argument QAHEAD of k_join_pairs): pair_request_round issues the three 16-byte loads
+// into registers that are NOT looked at -- the rows' or the columns' layout, whichever the batch has --, pair_take_round unpacks them
+// where the regions are needed, at the top of the round they belong to, and runs the partial round's element-wise path.  In ONE step
+// the two layouts meet in qc / qs / qe right behind the loads: twelve register copies there, each a wait for a load that was issued a
+// few instructions before -- and, the counter being in order, for every store in front of it: the "prefetch" was waited for where it
+// was requested.
+struct PairRaw {
+    gffx_v4u a, b, c;
+};
+template <uint32_t kChunk>
+__device__ __forceinline__ void pair_request_round(const QueryView &q, unsigned long long nq, unsigned long long r, uint32_t t4, PairRaw &w) {
+    const unsigned long long base = r * kChunk;  // (uniform)
+    constexpr int kNt = 2;                       // nt: streamed once
+    const unsigned long long left = base < nq ? nq - base : 0ull;
+    const uint32_t rows = (uint32_t)min(left, (unsigned long long)kChunk);
+    // ONE sequence of loads for both layouts, descriptors and offsets picked by scalar selects: two sequences would meet in w behind
+    // a branch, with the same copies.  (The rows' second and third 16 bytes in the VECTOR offset, where the range check sees them.)
+    const bool aos = q.aos != nullptr;
+    const uint32_t words = aos ? 3u : 1u, bytes = rows * 4u * words;
+    const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>((aos ? q.aos : q.chr) + words * base), 0, bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>((aos ? q.aos : q.start) + words * base), 0, bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>((aos ? q.aos : q.end) + words * base), 0, bytes, 0x00020000);
+    const uint32_t o = 4u * words * t4;
+    w.a = __builtin_amdgcn_raw_buffer_load_b128(r0, o, 0, kNt);
+    w.b = __builtin_amdgcn_raw_buffer_load_b128(r1, o + (aos ? 16u : 0u), 0, kNt);
+    w.c = __builtin_amdgcn_raw_buffer_load_b128(r2, o + (aos ? 32u : 0u), 0, kNt);
+}
+template <uint32_t kChunk>
+__device__ __forceinline__ void pair_take_round(const QueryView &q, unsigned long long nq, int vec_ok, uint32_t n_chr, unsigned long long r, uint32_t t4,
+                                                const PairRaw &w, uint32_t (&qc)[4], uint32_t (&qs)[4], uint32_t (&qe)[4], bool &bad) {
+    const unsigned long long base = r * kChunk;  // (uniform)
+    if (q.aos) {  // (uniform)
+        qc[0] = w.a.x, qs[0] = w.a.y, qe[0] = w.a.z;
+        qc[1] = w.a.w, qs[1] = w.b.x, qe[1] = w.b.y;
+        qc[2] = w.b.z, qs[2] = w.b.w, qe[2] = w.c.x;
+        qc[3] = w.c.y, qs[3] = w.c.z, qe[3] = w.c.w;
+    } else {
+        qc[0] = w.a.x, qc[1] = w.a.y, qc[2] = w.a.z, qc[3] = w.a.w;
+        qs[0] = w.b.x, qs[1] = w.b.y, qs[2] = w.b.z, qs[3] = w.b.w;
+        qe[0] = w.c.x, qe[1] = w.c.y, qe[2] = w.c.z, qe[3] = w.c.w;
+    }
+    if (base < nq && !(vec_ok && base + kChunk <= nq)) {  // (as in pair_load_round)
+        const unsigned long long i0 = base + t4;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            qc[k] = n_chr;
+            qs[k] = 0, qe[k] = 1;
+            if (i0 + k < nq) {
+                pair_load_region(q, i0 + k, qc[k], qs[k], qe[k]);
+                bad |= qc[k] >= n_chr;
+                qc[k] = min(qc[k], n_chr);
+            }
+        }
+        // (a batch's last round only.  None of its loads is left in flight: registers that MAY still be loaded behind this branch would
+        //  make the wait for the regions s_waitcnt vmcnt(0) in every round)
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    }
+}
+
 // T: threads per block (512: two blocks per CU; 1024: one, half the reservation atomics)
 // OFFS: per-region offsets are written (GFFX_OUT_OFFSETS / _OFFSETS32): each lane parks its place inside the round's segment
 // POS: the words a pass emits are index positions (table win_pos), not root_fids
@@ -762,7 +825,10 @@ __device__ __forceinline__ void pair_load_round(const QueryView &q, unsigned lon
 //      it: behind a run-time record index and next to the ticket code's control flow the compiler re-loads the record's fields from
 //      the kernarg segment in the loop (the root kernel 12 -> 42 scalar loads, each one an s_waitcnt lgkmcnt(0)): +2 % per pair pass,
 //      +5-10 % per root pass for the plain launch, +1-2 % for a launch that serves a group (profiles/r06_single_batch_regression.txt)
-template <int MODE, bool META_LDS, int T, bool OFFS, bool POS, bool WIDE = false, int KIND = kLaunchPlain>
+// QAHEAD: the next round's regions are requested in one step and unpacked in another (pair_request_round / pair_take_round): in flight
+//      under the scan, the parking, the arrival and the loop's top instead of waited for where they are requested.  The narrow form
+//      without per-region offsets (what bench.py times); the other instantiations keep pair_load_round.
+template <int MODE, bool META_LDS, int T, bool OFFS, bool POS, bool WIDE = false, int KIND = kLaunchPlain, bool QAHEAD = false>
 __global__ __launch_bounds__(T, 4) void k_join_pairs(PairArgs A) {
     constexpr bool DYN = KIND == kLaunchGroup, TICK = KIND == kLaunchTickets;
     constexpr bool CONT = WIDE && MODE == GFFX_MODE_CONTAINED;        // a wide lane keeps the roots of its run that end inside the region (inverted: beyond it)
@@ -807,8 +873,16 @@ __global__ __launch_bounds__(T, 4) void k_join_pairs(PairArgs A) {
     uint32_t qc[4], qs[4], qe[4];  // the round's 4 consecutive regions of the thread
     bool bad = false;              // a region's seqid is out of range
     auto load_round = [&](unsigned long long r) { pair_load_round<kChunk>(q, nq, S.vec_ok, n_chr, r, t4, qc, qs, qe, bad); };
+    PairRaw rr;  // (QAHEAD) the requested round, as loaded
+    auto request_round = [&](unsigned long long r) { pair_request_round<kChunk>(q, nq, r, t4, rr); };
+    auto take_round = [&](unsigned long long r) { pair_take_round<kChunk>(q, nq, S.vec_ok, n_chr, r, t4, rr, qc, qs, qe, bad); };
     const unsigned long long n_rounds = (nq + kChunk - 1) / kChunk;
-    if (lb < n_rounds) load_round(lb);  // in flight while the tables are staged
+    if (lb < n_rounds) {  // in flight while the tables are staged
+        if constexpr (QAHEAD)
+            request_round(lb);
+        else
+            load_round(lb);
+    }
     const uint4 *cm;
     if (META_LDS) {
         for (uint32_t i = tid; i <= n_chr; i += T) s_meta[i] = A.pv.meta[i];
@@ -948,11 +1022,20 @@ __global__ __launch_bounds__(T, 4) void k_join_pairs(PairArgs A) {
     };
     uint32_t k_round = 0, slot_now = 0;  // the block's rounds, counted; k_round % D
     uint32_t k_tick = 0;                 // ... those whose successor was taken by ticket
-    // The first round's regions are waited for HERE, once: pending at the loop's entry (with possibly nothing issued after them)
-    // they would turn the wait at the top of EVERY round into s_waitcnt vmcnt(0) -- a drain of the previous round's stores
-    // and of its reservation atomic -- because the compiler merges the entry's state with the back edge's.
+    // THE INVARIANT OF THE LOOP'S ENTRY, either order: the compiler merges the entry's state with the back edge's, so regions that are
+    // pending at the entry with possibly nothing issued behind them turn the wait at the top of EVERY round into s_waitcnt vmcnt(0) --
+    // a drain of the previous round's stores and of its reservation atomic.
+    //   * QAHEAD: the regions are unpacked at the top of every round, the first one's too, so they ARE pending here.  Behind EVERY
+    //     request stands exactly one unconditional memory operation: in the loop the counts store, here a store through an EMPTY
+    //     descriptor (the range check drops it: no memory is touched).  A block without a round (the host gives none: every batch of a
+    //     launch has between one block and a block per round) issues that store alone and leaves.
+    //   * otherwise: the first round's regions are waited for HERE, once, and nothing is pending at the entry.
+    if constexpr (QAHEAD) {
+        __builtin_amdgcn_raw_buffer_store_b32(0u, __builtin_amdgcn_make_buffer_rsrc(out.counts, 0, 0, 0x00020000), 0, 0, 0);
+    } else {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(qc[k]), "+v"(qs[k]), "+v"(qe[k]));
+        for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(qc[k]), "+v"(qs[k]), "+v"(qe[k]));
+    }
     for (unsigned long long r = lb; r < n_rounds; ++k_round) {
         const unsigned long long base = r * kChunk;  // (uniform) first region of the round
         const unsigned long long i0 = base + t4;     // this thread's 4 consecutive regions
@@ -971,6 +1054,7 @@ __global__ __launch_bounds__(T, 4) void k_join_pairs(PairArgs A) {
         uint32_t iswm = 0;                        // ... as a bit per region
         bool bigr[4];                             // (ContainsRegion, a wide lane) the region ends beyond what the line's coordinates reach
         uint32_t mb[4] = {0, 0, 0, 0};            // ... the entries whose true ends decide (pair_wide_resolve)
+        if constexpr (QAHEAD) take_round(r);  // (the wait for the regions requested a round ago: counted, the counts store is behind them)
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             bad |= full && qc[k] >= n_chr;  // (a partial round's rows were checked when they were loaded)
@@ -1267,7 +1351,7 @@ __global__ __launch_bounds__(T, 4) void k_join_pairs(PairArgs A) {
         // ---- the wave that issued the previous round's reservation atomic posts what it returned: every load of this round
         // has been waited for, so the atomic -- issued before them -- is back without another wait
         post_pending();
-        {
+        auto store_counts = [&]() {
             // counts: ONE 16-byte buffer store per thread on every path (rows beyond the batch fall outside the descriptor and
             // are dropped by the range check).  A conditional store here would make "no memory operation was issued after the
             // region prefetch" a possible path, and the wait for the prefetched regions at the top of the next round would
@@ -1278,10 +1362,13 @@ __global__ __launch_bounds__(T, 4) void k_join_pairs(PairArgs A) {
             cv.x = cnt[0], cv.y = cnt[1], cv.z = cnt[2], cv.w = cnt[3];
             __builtin_amdgcn_raw_buffer_store_b128(cv, __builtin_amdgcn_make_buffer_rsrc(out.counts + base, 0, rows * 4u, 0x00020000),
                                                    4u * t4, 0, 2 /* nt */);
-        }
+        };
+        if constexpr (!QAHEAD) store_counts();
         // ---- the oldest round in flight leaves (its segment base was posted a round ago), THEN the next round's regions are
         // requested -- the regions of this one are done with, their registers are free: the stores above are older than the
         // loads the top of the next round waits for, and nothing conditional but the reservation atomic is younger
+        // (QAHEAD: the counts store goes BEHIND the request -- the one unconditional operation behind it, so that the wait at the next
+        //  round's top is a counted one that leaves the reservation atomic alone)
         GFFX_WIN_STAMP(6);
         finish(P - 1);
         GFFX_WIN_STAMP(7);
@@ -1294,7 +1381,12 @@ __global__ __launch_bounds__(T, 4) void k_join_pairs(PairArgs A) {
         } else {
             r_next = (uint32_t)r + S.n_blocks;
         }
-        load_round(r_next);
+        if constexpr (QAHEAD) {
+            request_round(r_next);
+            store_counts();
+        } else {
+            load_round(r_next);
+        }
         const uint32_t mine = cnt[0] + cnt[1] + cnt[2] + cnt[3];
         const uint32_t inc = win_wave_scan(mine);
         const uint32_t wtotal = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);  // (uniform) the wave's kept pairs

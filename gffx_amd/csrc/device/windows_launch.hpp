@@ -26,10 +26,13 @@ int launch_windows_kind(const WindowsLaunch &L);
 
 template <int MODE, bool ML, int T, bool OFFS, bool POS, bool WIDE, int KIND>
 static inline int launch_pairs_t(const WindowsLaunch &L) {
-    const int rc = lds_opt_in(reinterpret_cast<const void *>(&k_join_pairs<MODE, ML, T, OFFS, POS, WIDE, KIND>), L.device, L.lds,
+    // regions requested a round ahead and unpacked at the round's top (join_pairs_kernels.hpp): the launches that serve a GROUP of
+    // batches, narrow form, no per-region offsets -- where it was measured; a lone batch's launches (plain, tickets) keep pair_load_round
+    constexpr bool QAHEAD = !WIDE && !OFFS && KIND == kLaunchGroup;
+    const int rc = lds_opt_in(reinterpret_cast<const void *>(&k_join_pairs<MODE, ML, T, OFFS, POS, WIDE, KIND, QAHEAD>), L.device, L.lds,
                               T == 1024 ? 2 * kWinMaxLds : kWinMaxLds);
     if (rc) return rc;
-    hipLaunchKernelGGL((k_join_pairs<MODE, ML, T, OFFS, POS, WIDE, KIND>), dim3(L.grid), dim3(T), L.lds, L.stream, *L.a);
+    hipLaunchKernelGGL((k_join_pairs<MODE, ML, T, OFFS, POS, WIDE, KIND, QAHEAD>), dim3(L.grid), dim3(T), L.lds, L.stream, *L.a);
     return GFFX_OK;
 }
 template <int MODE, bool ML, int T, bool WIDE, int KIND>

@@ -189,6 +189,45 @@ int main(int argc, char **argv) {
         uint32_t grouped = 0;
         if (ng <= 8 && !gffx_hip_batches_timed_runs(bb.data(), ng, kb_mode, 0, flags, strategy, 20, &ms, &grouped))
             printf("group launch: %.2f us per launch of %d batches = %.2f us per pass (HIP events, serial launches, grouped=%u)\n", 1e3 * ms / 20, ng, 1e3 * ms / 20 / ng, grouped);
+#if GFFX_STAMPS
+        if (ng <= 8) {
+            // the pair kernel's phase stamps of ONE group launch (a launch of its own, nothing else in flight): per slot the mean and the
+            // latest time since the launch's first stamp, over the last round of every block
+            std::vector<unsigned long long> z(8192 * 16, 0);
+            const int which = 4;
+            for (auto *x : bb) gffx_hip_batch_sync(x);
+            hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), z.data(), z.size() * 8);
+            hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_sel), &which, sizeof(int));
+            double ms1 = 0;
+            uint32_t grouped1 = 0;
+            if (gffx_hip_batches_timed_runs(bb.data(), ng, kb_mode, 0, flags, strategy, 1, &ms1, &grouped1)) return 1;
+            const int none = 0;
+            hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_sel), &none, sizeof(int));
+            hipMemcpyFromSymbol(z.data(), HIP_SYMBOL(g_stamps), z.size() * 8);
+            unsigned long long t0 = ~0ull;
+            int nb = 0;
+            for (int blk = 0; blk < 8192; blk++)
+                if (z[blk * 16 + 13]) t0 = std::min(t0, z[blk * 16 + 13]), nb++;
+            printf("group stamps: one launch of %d batches (grouped=%u), %d blocks; mean / max us since the launch's first entry:", ng, grouped1, nb);
+            for (int k : {13, 0, 1, 2, 3, 4, 5, 6, 7, 10, 11, 12, 14, 15}) {
+                double m = 0, mx = 0;
+                int n = 0;
+                for (int blk = 0; blk < 8192; blk++)
+                    if (z[blk * 16 + k] && z[blk * 16 + 13]) m += (double)(z[blk * 16 + k] - t0) * 0.01, mx = std::max(mx, (double)(z[blk * 16 + k] - t0) * 0.01), n++;
+                if (n) printf(" [%d]%.2f/%.2f", k, m / n, mx);
+            }
+            // ... and per block, since the top of its last round: what a steady-state round spends where
+            printf("\n  the last round of a block, mean us since its top [0]:");
+            for (int k : {1, 2, 3, 4, 5, 6, 7, 10, 11, 12}) {
+                double m = 0;
+                int n = 0;
+                for (int blk = 0; blk < 8192; blk++)
+                    if (z[blk * 16 + k] && z[blk * 16] && z[blk * 16 + k] >= z[blk * 16]) m += (double)(z[blk * 16 + k] - z[blk * 16]) * 0.01, n++;
+                if (n) printf(" [%d]%.2f", k, m / n);
+            }
+            printf("\n");
+        }
+#endif
         for (auto *x : bb) {
             if (gffx_hip_batch_wait(x)) { fprintf(stderr, "wait: %s\n", gffx_hip_last_error()); return 1; }
             if (gffx_hip_batch_total_hits(x) != gffx_hip_batch_total_hits(b)) printf("MISMATCH: %llu pairs\n", (unsigned long long)gffx_hip_batch_total_hits(x));
