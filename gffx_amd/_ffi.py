@@ -253,6 +253,27 @@ SIGNATURES = {
     "gffx_hip_gff_copy_skipped_lines": (C.c_int, [vp, u64p]),
     "gffx_hip_gff_copy_warn_rows": (C.c_int, [vp, u32p]),
     "gffx_hip_gff_destroy": (None, [vp]),
+    "gffx_hip_genome_create": (C.c_int, [C.c_int, C.c_uint64, C.POINTER(vp)]),
+    "gffx_hip_genome_reserve": (C.c_int, [vp, C.c_uint64]),
+    "gffx_hip_genome_feed": (C.c_int, [vp, u8p, C.c_uint64]),
+    "gffx_hip_genome_finish": (C.c_int, [vp]),
+    "gffx_hip_genome_device": (C.c_int, [vp]),
+    "gffx_hip_genome_n_seq": (C.c_uint32, [vp]),
+    "gffx_hip_genome_n_bases": (C.c_uint64, [vp]),
+    "gffx_hip_genome_name_bytes": (C.c_uint64, [vp]),
+    "gffx_hip_genome_copy_names": (C.c_int, [vp, u8p, u64p]),
+    "gffx_hip_genome_copy_seqs": (C.c_int, [vp, u64p, u32p]),
+    "gffx_hip_genome_copy_bases": (C.c_int, [vp, C.c_uint64, C.c_uint64, u8p]),
+    "gffx_hip_genome_stage_ms": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gffx_hip_genome_destroy": (None, [vp]),
+    "gffx_hip_seq_tile": (C.c_uint32, []),
+    "gffx_hip_seq_create": (C.c_int, [vp, C.c_uint64, u32p, C.c_uint64, u8p, C.c_int, C.c_uint32, C.POINTER(vp)]),
+    "gffx_hip_seq_body_bytes": (C.c_uint64, [vp]),
+    "gffx_hip_seq_copy_offsets": (C.c_int, [vp, u64p, u8p]),
+    "gffx_hip_seq_emit_start": (C.c_int, [vp, C.c_int, C.c_uint64, C.c_uint64]),
+    "gffx_hip_seq_emit_wait": (C.c_int, [vp, C.c_int, C.POINTER(u8p)]),
+    "gffx_hip_seq_stage_ms": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gffx_hip_seq_destroy": (None, [vp]),
 }
 
 # the regex compiler of `gffx search -r` in libgffx_host.so (include/gffx_host.h "gffx_host_regex_*"): name -> (restype, argtypes)

@@ -17,6 +17,7 @@
 //   gffx::commands::annotate::{AnnotateArgs, run}                                (no reference item; annotate.cpp)
 //   gffx::commands::enrich::{EnrichArgs, run}                                    (no reference item; enrich.cpp)
 //   gffx::commands::meta::{MetaArgs, run}                                        (no reference item; meta.cpp)
+//   gffx::commands::seq::{SeqArgs, run}                                          (no reference item; seq.cpp)
 // Compute (Join A, Join B) goes through include/gffx_hip.h only; there is no CPU join here.
 #pragma once
 #include <algorithm>
@@ -549,6 +550,26 @@ struct MetaArgs {
 void run(const MetaArgs &args);
 
 }  // namespace meta
+
+namespace seq {
+
+struct SeqArgs {
+    CommonArgs common;                       // -i, -o, -t, -v
+    std::string fasta;                       // -f/--fasta: the genome, plain FASTA
+    std::vector<std::string> types{"exon"};  // -T/--types: the lines that give segments (order is meaningless)
+    bool join = false;                       // -j/--join: one record per Parent instead of one per line
+    bool translate = false;                  // --translate: amino acids instead of bases
+    uint32_t width = 60;                     // -w/--width: sequence characters per line; 0: one line per record
+    int device = 0;                          // --device
+};
+
+// The sequences under the lines of the -T types, or with -j the spliced sequences of their parents, as FASTA
+// (device/seq_core.hpp has the definition).  The genome is packed and the bodies are made on the device; the headers are the
+// host's.  GFFX_SEQ_OUT_BYTES sets the body bytes per device slice (default 256 MiB; a positive decimal number, anything else is
+// ignored).  The output never depends on it, on -t or on the line-table route.
+void run(const SeqArgs &args);
+
+}  // namespace seq
 }  // namespace commands
 
 // ---- BAM sources of depth / coverage (bam.cpp; commands/depth.rs:297-372, coverage.rs:125-168) ------------------------

@@ -1,5 +1,5 @@
 // main.cpp -- `gffx` command line for the intersect path: `gffx index` (prerequisite),
-// `gffx intersect`, `gffx extract`, `gffx search`, `gffx depth` (BED source), `gffx closest`, `gffx annotate`, `gffx enrich` and `gffx meta` (additions) (reference: main.rs:11-39, commands/depth.rs:34-72, commands/extract.rs:16-35, commands/search.rs:18-51, commands/index.rs:11-23, commands/intersect.rs:32-70,
+// `gffx intersect`, `gffx extract`, `gffx search`, `gffx depth` (BED source), `gffx closest`, `gffx annotate`, `gffx enrich`, `gffx meta` and `gffx seq` (additions) (reference: main.rs:11-39, commands/depth.rs:34-72, commands/extract.rs:16-35, commands/search.rs:18-51, commands/index.rs:11-23, commands/intersect.rs:32-70,
 // utils/common.rs:17-52).  Flag names, short flags, defaults and groups follow the reference's
 // clap derive; usage errors exit 2 like clap, run-time errors print `Error: <msg>` and exit 1.
 #include <unistd.h>
@@ -96,6 +96,7 @@ const char *kTopUsage =
     "  annotate   Count the bases of a region or of the regions of a BED file by feature class (MI355X engine)\n"
     "  enrich     Test the regions of a BED file against feature classes by permutation (MI355X engine)\n"
     "  meta       Sum the depth of a BED, BAM or SAM file around features, along their strand (MI355X engine)\n"
+    "  seq        Write the sequences of features, or of their parents spliced, from a FASTA file (MI355X engine)\n"
     "  help       Print this message\n";
 
 const char *kIntersectUsage =
@@ -252,6 +253,26 @@ const char *kMetaUsage =
     "  column, part (point, up, body, down), from and to (offsets from the anchor, the 5' end or the 3' end; body columns\n"
     "  count from 0 to M), features with bases in the column, bases (summed depth), length, mean_depth = bases / length.\n"
     "  A strand other than '+' or '-' counts as '+' (a warning says how many).\n";
+
+const char *kSeqUsage =
+    "Usage: gffx seq [OPTIONS] --input <FILE> --fasta <FILE>\n\nOptions:\n"
+    "  -i, --input <FILE>       Input GFF file path\n"
+    "  -f, --fasta <FILE>       The genome as plain FASTA (lines of any lengths; a compressed file is refused)\n"
+    "  -o, --output <FILE>      Output file (stdout if not provided)\n"
+    "  -T, --types <T1,T2,...>  Feature types (column 3) whose lines give the segments [default: exon]\n"
+    "  -j, --join               One record per Parent instead of one per line: its segments in order of start, joined\n"
+    "      --translate          Amino acids instead of bases: NCBI table 1 from the phase (column 8) of the first segment,\n"
+    "                           stops as '*', a codon with a letter outside ACGTU as 'X' (e.g. -j --translate -T CDS)\n"
+    "  -w, --width <W>          Sequence characters per line; 0: one line per record [default: 60]\n"
+    "  -t, --threads <NUM>      Number of threads for parallel processing [default: 12]\n"
+    "  -v, --verbose            Enable verbose output\n"
+    "      --device <N>         HIP device to run on [default: 0]\n"
+    "      --stats-json <FILE>  Write the run's stage timers and counts as one JSON object\n\n"
+    "Output: FASTA.  Without -j one record per line of the types, in file order: '>ID seqid:start-end(strand)' ('.' for a\n"
+    "  line without ID).  With -j one record per name in the lines' Parent attributes, in order of first appearance:\n"
+    "  '>name seqid:start-end(strand) segments=k'.  A feature on '-' is reverse-complemented (IUPAC codes, case kept).  A record\n"
+    "  with a member on a seqid the FASTA file lacks, beyond its sequence's end, or (-j) on another seqid or strand than its\n"
+    "  first member is left out (warnings say how many).\n";
 
 const char *kIndexUsage =
     "Usage: gffx index [OPTIONS] --input <INPUT>\n\nOptions:\n"
@@ -530,6 +551,20 @@ void run_meta_cli(const Opts &o) {
     commands::meta::run(a);
 }
 
+void run_seq_cli(const Opts &o) {
+    commands::seq::SeqArgs a;
+    o.require({{"input", kInput}, {"fasta", "--fasta <FILE>"}});
+    o.common(a.common);
+    a.fasta = o.str("fasta");
+    if (o.has("types")) a.types = parse_layers(o.str("types"));
+    a.join = o.has("join");
+    a.translate = o.has("translate");
+    a.width = static_cast<uint32_t>(o.size("width", "--width <W>", a.width));
+    a.device = o.device();
+    o.stats_json();
+    commands::seq::run(a);
+}
+
 void run_index_cli(const Opts &o) {
     o.require({{"input", "--input <INPUT>"}});
     const std::string &input = o.str("input");
@@ -586,6 +621,9 @@ const std::vector<Command> &commands_table() {
          {{'i', "input", true}, {'s', "source", true}, {'o', "output", true}, {'T', "types", true}, {0, "anchor", true}, {0, "scale", true},
           {'u', "upstream", true}, {'d', "downstream", true}, {'w', "bin", true}, {'g', "genome", true}, {0, "matrix", true}, {'t', "threads", true},
           {'v', "verbose", false}, {0, "device", true}, {0, "gpus", true}, {0, "stats-json", true}}},
+        {"seq", kSeqUsage, run_seq_cli,
+         {{'i', "input", true}, {'f', "fasta", true}, {'o', "output", true}, {'T', "types", true}, {'j', "join", false}, {0, "translate", false},
+          {'w', "width", true}, {'t', "threads", true}, {'v', "verbose", false}, {0, "device", true}, {0, "stats-json", true}}},
     };
     return table;
 }

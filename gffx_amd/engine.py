@@ -615,6 +615,9 @@ def __getattr__(name: str):
         fold, tile = _profile_constants()
         globals().update(PROFILE_FOLD=fold, PROFILE_SCAN_TILE=tile)
         return fold if name == "PROFILE_FOLD" else tile
+    if name == "SEQ_TILE":
+        globals().update(SEQ_TILE=seq_tile())
+        return globals()["SEQ_TILE"]
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -1686,3 +1689,153 @@ def gff_index(data: bytes, attr_key: str = "gene_name", skip_types: str = DEFAUL
         g.close()
         raise
     return g
+
+
+# ---- `gffx seq`: the genome object and the sequence plan (device/genome.hip, device/seq.hip) ----------------------------------
+SEQ_MINUS, SEQ_DROPPED = 1, 8  # rec_flags bits (GFFX_SEQ_*); the phase 0 .. 2 sits in bits 1 .. 2
+
+
+def seq_tile() -> int:
+    """SEQ_TILE: the output bytes per block of the emit kernel."""
+    return int(lib().gffx_hip_seq_tile())
+
+
+class Genome:
+    """gffx_hip_genome_*: a plain FASTA text, fed in pieces cut anywhere, packed into one arena of bases on the device.
+    After ``finish``: ``names`` (bytes), ``lengths`` (u32), ``offsets`` (u64, n_seq + 1: where every sequence begins in the
+    arena, the last one the base total) and ``bases(at, n)``."""
+
+    def __init__(self, device: int = 0, chunk_bytes: int = 0):
+        self._h = C.c_void_p()
+        check(lib().gffx_hip_genome_create(int(device), int(chunk_bytes), C.byref(self._h)))
+        self.names: List[bytes] = []
+        self.lengths = np.zeros(0, dtype=np.uint32)
+        self.offsets = np.zeros(1, dtype=np.uint64)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().gffx_hip_genome_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reserve(self, n_bytes: int) -> None:
+        check(lib().gffx_hip_genome_reserve(self._h, int(n_bytes)))
+
+    def feed(self, data: bytes) -> None:
+        buf, p = _u8(data)
+        check(lib().gffx_hip_genome_feed(self._h, p, len(data)))
+
+    def finish(self) -> None:
+        check(lib().gffx_hip_genome_finish(self._h))
+        n = int(lib().gffx_hip_genome_n_seq(self._h))
+        names = np.zeros(max(int(lib().gffx_hip_genome_name_bytes(self._h)), 1), dtype=np.uint8)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        check(lib().gffx_hip_genome_copy_names(self._h, names.ctypes.data_as(_ffi.u8p), off.ctypes.data_as(u64p)))
+        raw = names.tobytes()
+        self.names = [raw[int(off[i]):int(off[i + 1])] for i in range(n)]
+        self.offsets = np.zeros(n + 1, dtype=np.uint64)
+        self.lengths = np.zeros(max(n, 1), dtype=np.uint32)
+        check(lib().gffx_hip_genome_copy_seqs(self._h, self.offsets.ctypes.data_as(u64p), _p(self.lengths)))
+        self.lengths = self.lengths[:n]
+
+    @property
+    def n_bases(self) -> int:
+        return int(lib().gffx_hip_genome_n_bases(self._h))
+
+    def bases(self, at: int = 0, n: Optional[int] = None) -> bytes:
+        n = self.n_bases - at if n is None else n
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        check(lib().gffx_hip_genome_copy_bases(self._h, int(at), int(n), out.ctypes.data_as(_ffi.u8p)))
+        return out[:n].tobytes()
+
+    def sequence(self, i: int) -> bytes:
+        return self.bases(int(self.offsets[i]), int(self.lengths[i]))
+
+    def stage_ms(self) -> Dict[str, float]:
+        a, b = C.c_double(), C.c_double()
+        check(lib().gffx_hip_genome_stage_ms(self._h, C.byref(a), C.byref(b)))
+        return {"lines_ms": a.value, "pack_ms": b.value}
+
+
+def genome_from_fasta(data: bytes, feed_bytes: int = 0, chunk_bytes: int = 0, device: int = 0) -> Genome:
+    """A finished Genome over the whole text (feed_bytes > 0: fed in pieces of that many bytes).  The caller closes it."""
+    g = Genome(device, chunk_bytes)
+    try:
+        if feed_bytes > 0:
+            for i in range(0, len(data), feed_bytes):
+                g.feed(data[i:i + feed_bytes])
+        else:
+            g.feed(data)
+        g.finish()
+    except Exception:
+        g.close()
+        raise
+    return g
+
+
+class SeqPlan:
+    """gffx_hip_seq_*: the bodies of the records of ``rows`` -- (n, 4) u32 (record, sequence number, start - 1, end) -- over a
+    finished Genome.  ``rec_flags[r]`` = SEQ_MINUS | phase << 1 | SEQ_DROPPED.  ``body_off`` (u64, n_records + 1) and ``dropped``
+    (u8) come back from the plan; ``emit(at, n)`` gives bytes [at, at + n) of the concatenated bodies."""
+
+    def __init__(self, genome: Genome, rows, rec_flags, translate: bool = False, width: int = 60):
+        r = _u32(rows).reshape(-1, 4)
+        f = np.ascontiguousarray(rec_flags, dtype=np.uint8)
+        self._genome = genome  # (it must outlive the plan)
+        self.n_records = int(f.shape[0])
+        self._h = C.c_void_p()
+        check(lib().gffx_hip_seq_create(genome._h, r.shape[0], _p(r), self.n_records, f.ctypes.data_as(_ffi.u8p), 1 if translate else 0, int(width),
+                                        C.byref(self._h)))
+        self.body_off = np.zeros(self.n_records + 1, dtype=np.uint64)
+        self.dropped = np.zeros(max(self.n_records, 1), dtype=np.uint8)
+        check(lib().gffx_hip_seq_copy_offsets(self._h, self.body_off.ctypes.data_as(u64p), self.dropped.ctypes.data_as(_ffi.u8p)))
+        self.dropped = self.dropped[:self.n_records]
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().gffx_hip_seq_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def body_bytes(self) -> int:
+        return int(lib().gffx_hip_seq_body_bytes(self._h))
+
+    def emit(self, at: int = 0, n: Optional[int] = None, slot: int = 0) -> bytes:
+        n = self.body_bytes - at if n is None else n
+        if n == 0:
+            return b""
+        check(lib().gffx_hip_seq_emit_start(self._h, slot, int(at), int(n)))
+        p = _ffi.u8p()
+        check(lib().gffx_hip_seq_emit_wait(self._h, slot, C.byref(p)))
+        return C.string_at(p, n)
+
+    def emit_sliced(self, slice_bytes: int) -> bytes:
+        """The whole concatenation in slices of ``slice_bytes``, slice k + 1 started before slice k is taken (as the command does)."""
+        total, out = self.body_bytes, []
+        starts = list(range(0, total, slice_bytes))
+        for k, at in enumerate(starts):
+            if k == 0:
+                check(lib().gffx_hip_seq_emit_start(self._h, 0, at, min(slice_bytes, total - at)))
+            p = _ffi.u8p()
+            check(lib().gffx_hip_seq_emit_wait(self._h, k & 1, C.byref(p)))
+            if k + 1 < len(starts):
+                nxt = starts[k + 1]
+                check(lib().gffx_hip_seq_emit_start(self._h, (k + 1) & 1, nxt, min(slice_bytes, total - nxt)))
+            out.append(C.string_at(p, min(slice_bytes, total - at)))
+        return b"".join(out)
+
+    def stage_ms(self) -> Dict[str, float]:
+        a, b = C.c_double(), C.c_double()
+        check(lib().gffx_hip_seq_stage_ms(self._h, C.byref(a), C.byref(b)))
+        return {"plan_ms": a.value, "emit_ms": b.value}

@@ -263,6 +263,17 @@ def write_gff3_fast(path: str, roots: Dict[str, np.ndarray], tx_per_gene: float 
     return int(out.strip())
 
 
+def write_fasta_fast(path: str, chroms: Sequence[Tuple[str, int]], width: int = 60, seed: int = 7) -> int:
+    """A random genome (ACGT, a few N) for ``chroms`` = (name, length) pairs in lines of ``width``.  Returns the bases written."""
+    tool = build_synth_text()
+    tmp = path + ".lengths"
+    with open(tmp, "w") as f:
+        f.write("".join("%s\t%d\n" % (n, l) for n, l in chroms))
+    out = subprocess.check_output([tool, "fasta", tmp, path, str(width), str(seed)])
+    os.remove(tmp)
+    return int(out.strip())
+
+
 def write_bed_fast(path: str, regions: np.ndarray, names: Sequence[str]) -> None:
     tool = build_synth_text()
     tmp = path + ".regions.bin"

@@ -33,6 +33,7 @@
  *     (index_loader/fts.rs:16-93, prt.rs:54-102, utils/common.rs:389-431)
  *   the line loop, feature_map and the numbering loop of   gffx_hip_gff_* (`gffx index --gpu`)
  *     build_index (index_builder/core.rs:71-203)
+ *   (no reference item: the reference writes no sequences)   gffx_hip_genome_*, gffx_hip_seq_* (`gffx seq`)
  *
  * Semantics (bit-exact with the reference):
  *   a root interval iv of the query's seqid is a HIT iff  iv.start < q.end && iv.end > q.start
@@ -968,6 +969,60 @@ int gffx_hip_gff_copy_roots(const gffx_hip_gff *, uint32_t *out /* 4 per root */
 int gffx_hip_gff_copy_skipped_lines(const gffx_hip_gff *, uint64_t *out);
 int gffx_hip_gff_copy_warn_rows(const gffx_hip_gff *, uint32_t *out);
 void gffx_hip_gff_destroy(gffx_hip_gff *);
+
+/* ---- Genome: a plain FASTA text packed into one arena of bases on the device (`gffx seq`; device/genome.hip) ----------------
+ * The rule of a line is device/seq_core.hpp's: a line ends at '\n', a '\r' directly before it is not part of it; empty lines
+ * are ignored; '>' opens a sequence named up to the first blank or TAB; every other line adds all of its bytes, as they are.
+ *   _create    chunk_bytes: the text per device pass (0: 64 MiB; at most 1 GiB)
+ *   _reserve   optional: room for n_bytes of bases at once (the arena otherwise grows as the text arrives)
+ *   _feed      the next bytes of the text, cut ANYWHERE: inside a header, inside "\r\n", before a last line without '\n'
+ *   _finish    the text is complete; the tables below are GFFX_E_STATE before it
+ * ERRORS (GFFX_E_INVALID, the message names the line, the object keeps the failure): a non-empty line before the first '>', a
+ * '>' line without a name, a name given twice, a sequence of 2^32 bases or more (GFF coordinates are 32-bit).  The arena itself
+ * has 64-bit offsets: a genome may exceed 4 GiB.
+ *   _copy_names  the names concatenated and their n_seq + 1 offsets; _copy_seqs: per sequence where it begins in the arena
+ *                (n_seq + 1 offsets, the last one the base total) and its length; _copy_bases: bases [at, at + n) of the arena
+ *   _stage_ms    HIP-event milliseconds of the line scan and of classify + prefix sums + copy, so far */
+typedef struct gffx_hip_genome gffx_hip_genome;
+int gffx_hip_genome_create(int device, uint64_t chunk_bytes, gffx_hip_genome **out);
+int gffx_hip_genome_reserve(gffx_hip_genome *, uint64_t n_bytes);
+int gffx_hip_genome_feed(gffx_hip_genome *, const uint8_t *bytes, uint64_t n_bytes);
+int gffx_hip_genome_finish(gffx_hip_genome *);
+int gffx_hip_genome_device(const gffx_hip_genome *);
+uint32_t gffx_hip_genome_n_seq(const gffx_hip_genome *);
+uint64_t gffx_hip_genome_n_bases(const gffx_hip_genome *);
+uint64_t gffx_hip_genome_name_bytes(const gffx_hip_genome *);
+int gffx_hip_genome_copy_names(const gffx_hip_genome *, uint8_t *names, uint64_t *name_off /* n_seq + 1 */);
+int gffx_hip_genome_copy_seqs(const gffx_hip_genome *, uint64_t *offset /* n_seq + 1 */, uint32_t *length /* n_seq */);
+int gffx_hip_genome_copy_bases(const gffx_hip_genome *, uint64_t at, uint64_t n, uint8_t *out);
+int gffx_hip_genome_stage_ms(const gffx_hip_genome *, double *lines_ms, double *pack_ms);
+void gffx_hip_genome_destroy(gffx_hip_genome *);
+
+/* ---- Seq: feature and spliced sequences of a genome, wrapped FASTA bodies (`gffx seq`; device/seq.hip, seq_core.hpp) ----------
+ * rows: (record, sequence number of the genome, start - 1, end) per segment, start - 1 < end, any order; a sequence number
+ * >= n_seq stands for a sequence the FASTA lacks.  Every record 0 .. n_records - 1 has at least one row.  rec_flags[r]:
+ * GFFX_SEQ_MINUS | phase << 1 (0 .. 2: bases skipped before the first codon with `translate`) | GFFX_SEQ_DROPPED (dropped by
+ * the caller).  A record's segments are ordered by (start, input order) and concatenated; a minus record is the reverse
+ * complement of that; a record with a member the genome cannot serve is dropped.  The body of a record is its characters in
+ * lines of `width` (0: one line), each ended by '\n'; a dropped record has none.
+ *   _create        the plan: sort, lengths, drops, body sizes and their 64-bit prefix sums (waits for them)
+ *   _copy_offsets  body_off[n_records + 1] into the concatenation of all bodies, dropped[n_records]
+ *   _emit_start    bytes [at, at + n) of that concatenation into slot 0 or 1 (any cut: inside a record, a line, before a
+ *                  newline), enqueued; _emit_wait: the slot's bytes in pinned host memory, valid until the slot's next start
+ *   _tile          the output bytes per block of the emit kernel
+ *   _stage_ms      HIP-event milliseconds of the plan and of the emit kernels so far
+ * The genome must outlive the object. */
+enum { GFFX_SEQ_MINUS = 1, GFFX_SEQ_DROPPED = 8 };
+typedef struct gffx_hip_seq gffx_hip_seq;
+uint32_t gffx_hip_seq_tile(void);
+int gffx_hip_seq_create(const gffx_hip_genome *, uint64_t n_rows, const uint32_t *rows /* 4 per row */, uint64_t n_records,
+                        const uint8_t *rec_flags, int translate, uint32_t width, gffx_hip_seq **out);
+uint64_t gffx_hip_seq_body_bytes(const gffx_hip_seq *);
+int gffx_hip_seq_copy_offsets(const gffx_hip_seq *, uint64_t *body_off /* n_records + 1 */, uint8_t *dropped /* n_records */);
+int gffx_hip_seq_emit_start(gffx_hip_seq *, int slot, uint64_t at, uint64_t n);
+int gffx_hip_seq_emit_wait(gffx_hip_seq *, int slot, const uint8_t **bytes);
+int gffx_hip_seq_stage_ms(const gffx_hip_seq *, double *plan_ms, double *emit_ms);
+void gffx_hip_seq_destroy(gffx_hip_seq *);
 
 #ifdef __cplusplus
 }

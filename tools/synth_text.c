@@ -1,5 +1,5 @@
 /* synth_text.c -- fast writers for the synthetic inputs of bench.py and the full-size tests (test infrastructure, not
- * product code): a GENCODE-shaped GFF3 around given root genes, and a BED file from u32 region triples.
+ * product code): a GENCODE-shaped GFF3 around given root genes, a BED file from u32 region triples, and a random genome.
  * Python's per-line writers take minutes at 3.4 M GFF lines / 100 M BED rows; this takes seconds.
  *
  *   synth_text gff <roots.bin> <names.txt> <out.gff> <tx_per_gene> <exons_per_tx> <seed>
@@ -9,6 +9,9 @@
  *       start) because the roots are); 1-based closed coordinates.
  *   synth_text bed <regions.bin> <names.txt> <out.bed>
  *       regions.bin: u64 n, then n x {chr, start, end} u32; one "name\tstart\tend\n" row each.
+ *   synth_text fasta <lengths.txt> <out.fa> <width> <seed>
+ *       lengths.txt: "name<TAB>length" per line; per name a ">name" line and its random ACGT bases (1 in 1000 an N) in lines
+ *       of <width>.
  */
 #include <inttypes.h>
 #include <stdint.h>
@@ -158,10 +161,46 @@ static int do_bed(int argc, char **argv) {
     return 0;
 }
 
+static int do_fasta(int argc, char **argv) {
+    if (argc < 6) return 2;
+    FILE *f = fopen(argv[2], "r");
+    if (!f) return perror(argv[2]), 1;
+    FILE *o = fopen(argv[3], "wb");
+    if (!o) return perror(argv[3]), 1;
+    static char buf[1 << 22];
+    setvbuf(o, buf, _IOFBF, sizeof buf);
+    const uint64_t width = strtoull(argv[4], NULL, 10);
+    if (width < 1 || width > 4096) return fprintf(stderr, "width 1 .. 4096\n"), 1;
+    g_state = strtoull(argv[5], NULL, 10);
+    char name[4096], line[4100];
+    unsigned long long len;
+    uint64_t total = 0;
+    while (fscanf(f, "%4095s %llu", name, &len) == 2) {
+        fprintf(o, ">%s\n", name);
+        for (uint64_t at = 0; at < len; at += width) {
+            const uint64_t k = len - at < width ? len - at : width;
+            for (uint64_t i = 0; i < k;) {
+                uint64_t r = rnd();  /* 2 bits per base, 32 bases per draw */
+                for (int j = 0; j < 32 && i < k; j++, i++, r >>= 2) line[i] = "ACGT"[r & 3];
+            }
+            if ((rnd() & 15) == 0) line[rnd() % k] = 'N';
+            line[k] = '\n';
+            fwrite(line, 1, (size_t)k + 1, o);
+        }
+        total += len;
+    }
+    fclose(f);
+    if (fclose(o)) return perror("close"), 1;
+    printf("%" PRIu64 "\n", total);
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc >= 2 && !strcmp(argv[1], "fasta")) return do_fasta(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "gff")) return do_gff(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "bed")) return do_bed(argc, argv);
     fprintf(stderr, "usage: synth_text gff <roots.bin> <names.txt> <out.gff> <tx_per_gene> <exons_per_tx> <seed>\n"
-                    "       synth_text bed <regions.bin> <names.txt> <out.bed>\n");
+                    "       synth_text bed <regions.bin> <names.txt> <out.bed>\n"
+                    "       synth_text fasta <lengths.txt> <out.fa> <width> <seed>\n");
     return 2;
 }
