@@ -18,6 +18,7 @@
 //   gffx::commands::enrich::{EnrichArgs, run}                                    (no reference item; enrich.cpp)
 //   gffx::commands::meta::{MetaArgs, run}                                        (no reference item; meta.cpp)
 //   gffx::commands::seq::{SeqArgs, run}                                          (no reference item; seq.cpp)
+//   gffx::commands::effect::{EffectArgs, run}                                    (no reference item; effect.cpp)
 // Compute (Join A, Join B) goes through include/gffx_hip.h only; there is no CPU join here.
 #pragma once
 #include <algorithm>
@@ -570,6 +571,26 @@ struct SeqArgs {
 void run(const SeqArgs &args);
 
 }  // namespace seq
+
+namespace effect {
+
+struct EffectArgs {
+    CommonArgs common;                   // -i, -o, -t, -v
+    std::string fasta;                   // -f/--fasta: the genome, plain FASTA
+    std::string variants;                // -V/--variants: CHROM POS ID REF ALT per line, plain text (VCF)
+    std::string cds_type = "CDS";        // --cds-type: the lines that give a transcript's coding segments
+    std::string exon_type = "exon";      // --exon-type: the lines that give its exons
+    std::optional<std::string> summary;  // --summary: class, alleles, pairs per class
+    int device = 0;                      // --device
+};
+
+// What every single-base substitution of the variants file does to every transcript it hits, one line per (allele, transcript)
+// (device/effect_core.hpp has the definition).  Transcripts, pairs and classes are made on the device; the names and the lines
+// are the host's.  GFFX_EFFECT_CHUNK_ROWS sets the alleles per device chunk (default 4 Mi; a positive decimal number, anything
+// else is ignored).  The output never depends on it, on -t or on the line-table route.
+void run(const EffectArgs &args);
+
+}  // namespace effect
 }  // namespace commands
 
 // ---- BAM sources of depth / coverage (bam.cpp; commands/depth.rs:297-372, coverage.rs:125-168) ------------------------

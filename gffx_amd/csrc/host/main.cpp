@@ -1,5 +1,5 @@
 // main.cpp -- `gffx` command line for the intersect path: `gffx index` (prerequisite),
-// `gffx intersect`, `gffx extract`, `gffx search`, `gffx depth` (BED source), `gffx closest`, `gffx annotate`, `gffx enrich`, `gffx meta` and `gffx seq` (additions) (reference: main.rs:11-39, commands/depth.rs:34-72, commands/extract.rs:16-35, commands/search.rs:18-51, commands/index.rs:11-23, commands/intersect.rs:32-70,
+// `gffx intersect`, `gffx extract`, `gffx search`, `gffx depth` (BED source), `gffx closest`, `gffx annotate`, `gffx enrich`, `gffx meta`, `gffx seq` and `gffx effect` (additions) (reference: main.rs:11-39, commands/depth.rs:34-72, commands/extract.rs:16-35, commands/search.rs:18-51, commands/index.rs:11-23, commands/intersect.rs:32-70,
 // utils/common.rs:17-52).  Flag names, short flags, defaults and groups follow the reference's
 // clap derive; usage errors exit 2 like clap, run-time errors print `Error: <msg>` and exit 1.
 #include <unistd.h>
@@ -97,6 +97,7 @@ const char *kTopUsage =
     "  enrich     Test the regions of a BED file against feature classes by permutation (MI355X engine)\n"
     "  meta       Sum the depth of a BED, BAM or SAM file around features, along their strand (MI355X engine)\n"
     "  seq        Write the sequences of features, or of their parents spliced, from a FASTA file (MI355X engine)\n"
+    "  effect     Classify single-base substitutions against the transcripts they hit (MI355X engine)\n"
     "  help       Print this message\n";
 
 const char *kIntersectUsage =
@@ -273,6 +274,29 @@ const char *kSeqUsage =
     "  '>name seqid:start-end(strand) segments=k'.  A feature on '-' is reverse-complemented (IUPAC codes, case kept).  A record\n"
     "  with a member on a seqid the FASTA file lacks, beyond its sequence's end, or (-j) on another seqid or strand than its\n"
     "  first member is left out (warnings say how many).\n";
+
+const char *kEffectUsage =
+    "Usage: gffx effect [OPTIONS] --input <FILE> --fasta <FILE> --variants <FILE>\n\nOptions:\n"
+    "  -i, --input <FILE>       Input GFF file path\n"
+    "  -f, --fasta <FILE>       The genome as plain FASTA (lines of any lengths; a compressed file is refused)\n"
+    "  -V, --variants <FILE>    The variants as plain text, CHROM POS ID REF ALT per line as in VCF ('#' lines are skipped; a\n"
+    "                           compressed file is refused).  ALT is split at ','; only single-base alleles are taken\n"
+    "  -o, --output <FILE>      Output file (stdout if not provided)\n"
+    "      --cds-type <TYPE>    Feature type (column 3) whose lines give a transcript's coding segments [default: CDS]\n"
+    "      --exon-type <TYPE>   Feature type whose lines give its exons [default: exon]\n"
+    "      --summary <FILE>     Write 'class<TAB>alleles<TAB>pairs' for every class\n"
+    "  -t, --threads <NUM>      Number of threads for parallel processing [default: 12]\n"
+    "  -v, --verbose            Enable verbose output\n"
+    "      --device <N>         HIP device to run on [default: 0]\n"
+    "      --stats-json <FILE>  Write the run's stage timers and counts as one JSON object\n\n"
+    "Output: one TAB-separated line per allele and transcript whose span contains it, the alleles in file order, an allele's\n"
+    "  transcripts in order of first appearance: chrom pos ref alt transcript strand class cds_pos codons aa_pos aa ref_match.\n"
+    "  A transcript is a name in the Parent attributes of the CDS and exon lines.  Classes: partial_codon, coding_unknown,\n"
+    "  stop_retained, synonymous, stop_gained, stop_lost, start_lost, missense, noncoding_exon, 5_prime_UTR, 3_prime_UTR, intron,\n"
+    "  splice_donor, splice_acceptor (the two bases next to an exon) and intergenic (no transcript: one line with '.').  The\n"
+    "  codon is read from the genome, never from REF; ref_match says whether REF is the genome's base.  A transcript with a\n"
+    "  member on a seqid the FASTA file lacks, beyond its sequence's end, or on another seqid or strand than its first member is\n"
+    "  left out (warnings say how many).\n";
 
 const char *kIndexUsage =
     "Usage: gffx index [OPTIONS] --input <INPUT>\n\nOptions:\n"
@@ -565,6 +589,22 @@ void run_seq_cli(const Opts &o) {
     commands::seq::run(a);
 }
 
+void run_effect_cli(const Opts &o) {
+    commands::effect::EffectArgs a;
+    o.require({{"input", kInput}, {"fasta", "--fasta <FILE>"}, {"variants", "--variants <FILE>"}});
+    o.common(a.common);
+    a.fasta = o.str("fasta");
+    a.variants = o.str("variants");
+    if (o.has("cds-type")) a.cds_type = o.str("cds-type");
+    if (o.has("exon-type")) a.exon_type = o.str("exon-type");
+    if (a.cds_type.empty() || a.exon_type.empty()) throw UsageError("'--cds-type <TYPE>' and '--exon-type <TYPE>' take a type name");
+    if (a.cds_type == a.exon_type) throw UsageError("the argument '--cds-type <TYPE>' names the type of '--exon-type <TYPE>': '" + a.cds_type + "'");
+    a.summary = o.opt("summary");
+    a.device = o.device();
+    o.stats_json();
+    commands::effect::run(a);
+}
+
 void run_index_cli(const Opts &o) {
     o.require({{"input", "--input <INPUT>"}});
     const std::string &input = o.str("input");
@@ -624,6 +664,9 @@ const std::vector<Command> &commands_table() {
         {"seq", kSeqUsage, run_seq_cli,
          {{'i', "input", true}, {'f', "fasta", true}, {'o', "output", true}, {'T', "types", true}, {'j', "join", false}, {0, "translate", false},
           {'w', "width", true}, {'t', "threads", true}, {'v', "verbose", false}, {0, "device", true}, {0, "stats-json", true}}},
+        {"effect", kEffectUsage, run_effect_cli,
+         {{'i', "input", true}, {'f', "fasta", true}, {'V', "variants", true}, {'o', "output", true}, {0, "cds-type", true}, {0, "exon-type", true},
+          {0, "summary", true}, {'t', "threads", true}, {'v', "verbose", false}, {0, "device", true}, {0, "stats-json", true}}},
     };
     return table;
 }

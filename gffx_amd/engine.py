@@ -1839,3 +1839,93 @@ class SeqPlan:
         a, b = C.c_double(), C.c_double()
         check(lib().gffx_hip_seq_stage_ms(self._h, C.byref(a), C.byref(b)))
         return {"plan_ms": a.value, "emit_ms": b.value}
+
+
+# ---- `gffx effect`: single-base substitutions against transcripts (device/effect.hip, the rules: effect_core.hpp) --------------
+EFFECT_CLASSES = ("partial_codon", "coding_unknown", "stop_retained", "synonymous", "stop_gained", "stop_lost", "start_lost", "missense",
+                  "noncoding_exon", "5_prime_UTR", "3_prime_UTR", "intron", "splice_donor", "splice_acceptor", "intergenic")
+EFFECT_CDS, EFFECT_EXON = 0, 1  # a member row's kind
+EFFECT_NO_SEQ = 0xFFFFFFFF      # an allele's sequence number when the FASTA lacks its sequence
+EFFECT_RECORD = np.dtype([("q", "<u8"), ("c", "<u8"), ("transcript", "<u4"), ("cls", "u1"), ("k", "u1"), ("ref_match", "u1"), ("aa_ref", "u1"),
+                          ("aa_alt", "u1"), ("codon_ref", "u1", (3,)), ("codon_alt", "u1", (3,)), ("pad", "u1")])
+
+
+class Effect:
+    """gffx_hip_effect_*: per (allele, kept transcript whose span contains it) one EFFECT_RECORD.  ``rows``: (n, 5) u32 (transcript,
+    sequence number, start - 1, end, kind) over a finished Genome; ``tr_flags[t]`` = SEQ_MINUS | phase << 1 | SEQ_DROPPED.
+    ``dropped`` (u8) and ``span`` ((n_transcripts, 2) u32: first and last base) come back from the build.  ``run(alleles)`` --
+    (n, 3) u32 (sequence number, x, REF | ALT << 8) -- gives (offsets[n + 1] u64, ref_match[n] u8, records)."""
+
+    def __init__(self, genome: Genome, rows, tr_flags, max_alleles: int = 1 << 20):
+        r = _u32(rows).reshape(-1, 5)
+        f = np.ascontiguousarray(tr_flags, dtype=np.uint8)
+        assert int(lib().gffx_hip_effect_record_bytes()) == EFFECT_RECORD.itemsize
+        self._genome = genome  # (it must outlive the object)
+        self.n_transcripts = int(f.shape[0])
+        self.max_alleles = int(max_alleles)
+        self._h = C.c_void_p()
+        check(lib().gffx_hip_effect_create(genome._h, r.shape[0], _p(r), self.n_transcripts, f.ctypes.data_as(_ffi.u8p), self.max_alleles, C.byref(self._h)))
+        self.dropped = np.zeros(max(self.n_transcripts, 1), dtype=np.uint8)
+        self.span = np.zeros((max(self.n_transcripts, 1), 2), dtype=np.uint32)
+        check(lib().gffx_hip_effect_copy_transcripts(self._h, self.dropped.ctypes.data_as(_ffi.u8p), _p(self.span)))
+        self.dropped, self.span = self.dropped[:self.n_transcripts], self.span[:self.n_transcripts]
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().gffx_hip_effect_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def start(self, slot: int, alleles) -> int:
+        a = _u32(alleles).reshape(-1, 3)
+        check(lib().gffx_hip_effect_run_start(self._h, int(slot), _p(a), a.shape[0]))
+        return int(a.shape[0])
+
+    def wait(self, slot: int, n: int):
+        """The results of the slot's chunk of n alleles, copied out of the pinned buffers."""
+        off, rm, rec, pairs = u64p(), _ffi.u8p(), _ffi.u8p(), C.c_uint64()
+        check(lib().gffx_hip_effect_run_wait(self._h, int(slot), C.byref(off), C.byref(rm), C.byref(rec), C.byref(pairs)))
+        offsets = np.frombuffer(C.string_at(off, 8 * (n + 1)), dtype=np.uint64).copy()
+        ref_match = np.frombuffer(C.string_at(rm, n), dtype=np.uint8).copy()
+        records = np.frombuffer(C.string_at(rec, EFFECT_RECORD.itemsize * pairs.value), dtype=EFFECT_RECORD).copy()
+        return offsets, ref_match, records
+
+    def run(self, alleles, slot: int = 0):
+        return self.wait(slot, self.start(slot, alleles))
+
+    def run_chunked(self, alleles, chunk_rows: int):
+        """All alleles in chunks of ``chunk_rows``, chunk k + 1 started before chunk k is taken (as the command does): the
+        concatenated (offsets, ref_match, records)."""
+        a = _u32(alleles).reshape(-1, 3)
+        starts = list(range(0, a.shape[0], chunk_rows))
+        offs, rms, recs, base = [np.zeros(1, dtype=np.uint64)], [], [], 0
+        for k, at in enumerate(starts):
+            if k == 0:
+                self.start(0, a[at:at + chunk_rows])
+            n = min(chunk_rows, a.shape[0] - at)
+            if k + 1 < len(starts):
+                self.start((k + 1) & 1, a[starts[k + 1]:starts[k + 1] + chunk_rows])
+                o, m, r = self.wait(k & 1, n)
+            else:
+                o, m, r = self.wait(k & 1, n)
+            offs.append(o[1:] + np.uint64(base))
+            base += int(o[-1])
+            rms.append(m)
+            recs.append(r)
+        return (np.concatenate(offs), np.concatenate(rms) if rms else np.zeros(0, dtype=np.uint8),
+                np.concatenate(recs) if recs else np.zeros(0, dtype=EFFECT_RECORD))
+
+    def stage_ms(self) -> Dict[str, float]:
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        check(lib().gffx_hip_effect_stage_ms(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"build_ms": a.value, "pairs_ms": b.value, "classify_ms": c.value}
+
+    def stats(self) -> Dict[str, int]:
+        kept, grows = C.c_uint64(), C.c_uint64()
+        check(lib().gffx_hip_effect_stats(self._h, C.byref(kept), C.byref(grows)))
+        return {"kept": kept.value, "grows": grows.value}

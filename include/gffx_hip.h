@@ -34,6 +34,7 @@
  *   the line loop, feature_map and the numbering loop of   gffx_hip_gff_* (`gffx index --gpu`)
  *     build_index (index_builder/core.rs:71-203)
  *   (no reference item: the reference writes no sequences)   gffx_hip_genome_*, gffx_hip_seq_* (`gffx seq`)
+ *   (no reference item: the reference reads no variants)     gffx_hip_effect_* (`gffx effect`)
  *
  * Semantics (bit-exact with the reference):
  *   a root interval iv of the query's seqid is a HIT iff  iv.start < q.end && iv.end > q.start
@@ -1023,6 +1024,48 @@ int gffx_hip_seq_emit_start(gffx_hip_seq *, int slot, uint64_t at, uint64_t n);
 int gffx_hip_seq_emit_wait(gffx_hip_seq *, int slot, const uint8_t **bytes);
 int gffx_hip_seq_stage_ms(const gffx_hip_seq *, double *plan_ms, double *emit_ms);
 void gffx_hip_seq_destroy(gffx_hip_seq *);
+
+/* ---- Effect: what a single-base substitution does to every transcript it hits (`gffx effect`; device/effect.hip, the rules:
+ * effect_core.hpp) ----
+ * rows: (transcript, sequence number of the genome, start - 1, end, kind) per member line, kind 0 a CDS line and 1 an exon line,
+ * start - 1 < end, any order; a sequence number >= n_seq stands for a sequence the FASTA lacks.  Every transcript
+ * 0 .. n_transcripts - 1 has at least one row.  tr_flags[t]: GFFX_SEQ_MINUS | phase of the leading CDS segment << 1 |
+ * GFFX_SEQ_DROPPED (dropped by the caller), as for gffx_hip_seq.  A transcript whose members lie on more than one sequence, on a
+ * sequence the genome lacks or beyond its end is dropped; the others are KEPT.  The span of a transcript is [smallest start,
+ * largest end] over all its members.
+ * alleles: (sequence number, x, REF | ALT << 8) per row, x 1-based; sequence number UINT32_MAX: a sequence the FASTA lacks (no
+ * pair, ref_match 0).  Any other number >= n_seq, or x = 0, fails the run with GFFX_E_CHR_RANGE, and the failure sticks.
+ * A chunk's result is a CSR: offsets[n + 1] (u64) over the pairs (allele, kept transcript whose span contains x), the alleles
+ * in input order and an allele's transcripts by number; per pair one 32-byte record
+ *     u64 q (cds_pos - 1), u64 c (aa_pos - 1), u32 transcript, u8 class, k, ref_match, aa_ref, aa_alt, codon_ref[3],
+ *     codon_alt[3], pad                                  (class: enum gffx_effect_class; the unused fields of a class are 0)
+ * and per allele ref_match[n] (u8): REF, case folded, is the genome's base at x.
+ *   _create           sorts the rows and builds the transcripts on the device, then a private interval index over the kept
+ *                     spans (waits for it); max_alleles: the largest chunk
+ *   _copy_transcripts dropped[n_transcripts], span[2 * n_transcripts] (first and last base, 1-based); either may be NULL
+ *   _run_start        a chunk into slot 0 or 1: the pair CSR from the engine's direct pass (waited for: the caller's rows are
+ *                     free on return; the pair buffer grows and the pass replays as for a batch), then the classify kernel and
+ *                     the copies, enqueued; _run_wait: the slot's results in pinned host memory, valid until its next start
+ *   _stage_ms         HIP-event milliseconds of the build, the pair passes and the classify kernel so far
+ *   _stats            kept transcripts; how often a slot's record buffer had to grow
+ * The genome must outlive the object. */
+enum gffx_effect_class {
+    GFFX_EFFECT_PARTIAL_CODON = 0, GFFX_EFFECT_CODING_UNKNOWN = 1, GFFX_EFFECT_STOP_RETAINED = 2, GFFX_EFFECT_SYNONYMOUS = 3,
+    GFFX_EFFECT_STOP_GAINED = 4, GFFX_EFFECT_STOP_LOST = 5, GFFX_EFFECT_START_LOST = 6, GFFX_EFFECT_MISSENSE = 7,
+    GFFX_EFFECT_NONCODING_EXON = 8, GFFX_EFFECT_5_PRIME_UTR = 9, GFFX_EFFECT_3_PRIME_UTR = 10, GFFX_EFFECT_INTRON = 11,
+    GFFX_EFFECT_SPLICE_DONOR = 12, GFFX_EFFECT_SPLICE_ACCEPTOR = 13, GFFX_EFFECT_INTERGENIC = 14
+};
+typedef struct gffx_hip_effect gffx_hip_effect;
+uint32_t gffx_hip_effect_record_bytes(void);
+int gffx_hip_effect_create(const gffx_hip_genome *, uint64_t n_rows, const uint32_t *rows /* 5 per row */, uint64_t n_transcripts,
+                           const uint8_t *tr_flags, uint64_t max_alleles, gffx_hip_effect **out);
+int gffx_hip_effect_copy_transcripts(const gffx_hip_effect *, uint8_t *dropped /* n_transcripts */, uint32_t *span /* 2 per transcript */);
+int gffx_hip_effect_run_start(gffx_hip_effect *, int slot, const uint32_t *alleles /* 3 per row */, uint64_t n);
+int gffx_hip_effect_run_wait(gffx_hip_effect *, int slot, const uint64_t **offsets, const uint8_t **ref_match, const uint8_t **records,
+                             uint64_t *n_pairs);
+int gffx_hip_effect_stage_ms(const gffx_hip_effect *, double *build_ms, double *pairs_ms, double *classify_ms);
+int gffx_hip_effect_stats(const gffx_hip_effect *, uint64_t *kept, uint64_t *grows);
+void gffx_hip_effect_destroy(gffx_hip_effect *);
 
 #ifdef __cplusplus
 }
