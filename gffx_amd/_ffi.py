@@ -149,6 +149,7 @@ SIGNATURES = {
     "gffx_hip_classmap_last_kernel_ms": (C.c_int, [vp, C.POINTER(C.c_double)]),
     "gffx_hip_classmap_stage_ms": (C.c_int, [vp, C.POINTER(C.c_double)]),
     "gffx_hip_classmap_scan_tile": (C.c_uint32, []),
+    "gffx_hip_classmap_carry_tiles": (C.c_uint32, []),
     "gffx_hip_classmap_block_size": (C.c_uint32, []),
     "gffx_hip_classmap_destroy": (None, [vp]),
     "gffx_hip_classmap_perm_begin": (C.c_int, [vp, u32p, C.c_uint32, C.c_uint64]),
@@ -266,6 +267,8 @@ SIGNATURES = {
     "gffx_hip_genome_copy_bases": (C.c_int, [vp, C.c_uint64, C.c_uint64, u8p]),
     "gffx_hip_genome_stage_ms": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gffx_hip_genome_destroy": (None, [vp]),
+    "gffx_hip_scan64_tile": (C.c_uint32, []),
+    "gffx_hip_scan64_carry_tiles": (C.c_uint32, []),
     "gffx_hip_seq_tile": (C.c_uint32, []),
     "gffx_hip_seq_create": (C.c_int, [vp, C.c_uint64, u32p, C.c_uint64, u8p, C.c_int, C.c_uint32, C.POINTER(vp)]),
     "gffx_hip_seq_body_bytes": (C.c_uint64, [vp]),

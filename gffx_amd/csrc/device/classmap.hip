@@ -430,6 +430,8 @@ int classmap_results(gffx_hip_classmap *H, const char *who) {
 
 extern "C" uint32_t gffx_hip_classmap_scan_tile(void) { return kClassScanTile; }
 extern "C" uint32_t gffx_hip_classmap_block_size(void) { return kClassThreads; }
+// tiles per step of k_classmap_carry, _carry_sum and _carry_bases (a block-wide step: one tile per thread)
+extern "C" uint32_t gffx_hip_classmap_carry_tiles(void) { return kClassThreads; }
 
 extern "C" void gffx_hip_classmap_destroy(gffx_hip_classmap *H) {
     if (!H) return;

@@ -389,6 +389,10 @@ extern "C" int gffx_hip_genome_stage_ms(const gffx_hip_genome *h, double *lines_
 
 extern "C" void gffx_hip_genome_destroy(gffx_hip_genome *h) { delete h; }
 
+// the shape of scan64.hpp: values per tile, and tile sums per step of k_scan64_carry (a block-wide step: one per thread)
+extern "C" uint32_t gffx_hip_scan64_tile(void) { return kScan64Tile; }
+extern "C" uint32_t gffx_hip_scan64_carry_tiles(void) { return kScan64Threads; }
+
 // what seq.hip reads of a finished genome
 namespace gffx {
 int genome_view(const gffx_hip_genome *h, const char *who, const uint8_t **arena, const u64 **seq_off, const uint32_t **seq_len, uint32_t *n_seq, int *device) {

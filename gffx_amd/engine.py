@@ -908,9 +908,10 @@ class DepthProfile:
                 "scan_ms": st[2].value, "points_ms": st[3].value}
 
 
-def _classmap_constants() -> Tuple[int, int]:
-    """(events per scan tile, regions per block of the regions kernel) of the class map."""
-    return int(lib().gffx_hip_classmap_scan_tile()), int(lib().gffx_hip_classmap_block_size())
+def _classmap_constants() -> Tuple[int, int, int]:
+    """(events per scan tile, regions per block of the regions kernel, tiles per step of the single-block carry walks) of the
+    class map."""
+    return int(lib().gffx_hip_classmap_scan_tile()), int(lib().gffx_hip_classmap_block_size()), int(lib().gffx_hip_classmap_carry_tiles())
 
 
 class ClassMap:
@@ -1698,6 +1699,13 @@ SEQ_MINUS, SEQ_DROPPED = 1, 8  # rec_flags bits (GFFX_SEQ_*); the phase 0 .. 2 s
 def seq_tile() -> int:
     """SEQ_TILE: the output bytes per block of the emit kernel."""
     return int(lib().gffx_hip_seq_tile())
+
+
+def scan64_constants() -> Tuple[int, int]:
+    """(values per tile, tile sums per step of the single carry block) of the 64-bit prefix sum behind the genome's line and byte
+    offsets, the seq plan's ``pre`` and ``body_off`` and the effect build's ``pre``: a scan of more than tile * carry_tiles values
+    takes a second carry step."""
+    return int(lib().gffx_hip_scan64_tile()), int(lib().gffx_hip_scan64_carry_tiles())
 
 
 class Genome:

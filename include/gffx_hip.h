@@ -683,6 +683,7 @@ int gffx_hip_classmap_copy_class(gffx_hip_classmap *, uint8_t *cls /* nq */);
 int gffx_hip_classmap_last_kernel_ms(gffx_hip_classmap *, double *ms);
 int gffx_hip_classmap_stage_ms(const gffx_hip_classmap *, double *ms /* 6: union, toggles, sort, scan, points, bases */);
 uint32_t gffx_hip_classmap_scan_tile(void);
+uint32_t gffx_hip_classmap_carry_tiles(void); /* tiles per step of the three single-block carry walks */
 uint32_t gffx_hip_classmap_block_size(void);
 void gffx_hip_classmap_destroy(gffx_hip_classmap *);
 
@@ -983,7 +984,9 @@ void gffx_hip_gff_destroy(gffx_hip_gff *);
  * has 64-bit offsets: a genome may exceed 4 GiB.
  *   _copy_names  the names concatenated and their n_seq + 1 offsets; _copy_seqs: per sequence where it begins in the arena
  *                (n_seq + 1 offsets, the last one the base total) and its length; _copy_bases: bases [at, at + n) of the arena
- *   _stage_ms    HIP-event milliseconds of the line scan and of classify + prefix sums + copy, so far */
+ *   _stage_ms    HIP-event milliseconds of the line scan and of classify + prefix sums + copy, so far
+ * gffx_hip_scan64_tile / _carry_tiles: the values per block of the 64-bit prefix sum behind the genome, the seq plan and the
+ * effect build (device/scan64.hpp), and the tile sums its single carry block takes per step */
 typedef struct gffx_hip_genome gffx_hip_genome;
 int gffx_hip_genome_create(int device, uint64_t chunk_bytes, gffx_hip_genome **out);
 int gffx_hip_genome_reserve(gffx_hip_genome *, uint64_t n_bytes);
@@ -998,6 +1001,8 @@ int gffx_hip_genome_copy_seqs(const gffx_hip_genome *, uint64_t *offset /* n_seq
 int gffx_hip_genome_copy_bases(const gffx_hip_genome *, uint64_t at, uint64_t n, uint8_t *out);
 int gffx_hip_genome_stage_ms(const gffx_hip_genome *, double *lines_ms, double *pack_ms);
 void gffx_hip_genome_destroy(gffx_hip_genome *);
+uint32_t gffx_hip_scan64_tile(void);
+uint32_t gffx_hip_scan64_carry_tiles(void);
 
 /* ---- Seq: feature and spliced sequences of a genome, wrapped FASTA bodies (`gffx seq`; device/seq.hip, seq_core.hpp) ----------
  * rows: (record, sequence number of the genome, start - 1, end) per segment, start - 1 < end, any order; a sequence number

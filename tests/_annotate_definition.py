@@ -132,6 +132,62 @@ def sparse(n_seq, T, rows, regions):
     return _pack(n_seq, T, per_seq) + (counts, best)
 
 
+def sparse_np(n_seq, T, rows, regions):
+    """``sparse`` restated over whole arrays, for maps of 10^5 .. 10^6 events (``sparse`` walks every point for every region):
+    the 2 n events sorted by (seqid, position); per layer its depth behind every event by a cumsum of its +1 / -1; the class
+    behind the last event of every (seqid, position); a point where that class differs from the one before (T before the first:
+    a seqid ends at depth 0 everywhere).  A region's bases of class k are B_k(qe) - B_k(qs), B_k(x) = the bases of class k below
+    x on the region's seqid: cb at the last point at or before x, plus the piece from that point to x if its class is k.
+    tests/test_annotate_cpu.py pins it to ``sparse``."""
+    r = _check(n_seq, T, rows)
+    q = np.asarray(regions, np.int64).reshape(-1, 3)
+    if len(q) and np.any(q[:, 0] >= n_seq):
+        raise ValueError("range")
+    m = len(r)
+    seq, pos = np.concatenate([r[:, 1], r[:, 1]]), np.concatenate([r[:, 2], r[:, 3]])
+    lay, d = np.concatenate([r[:, 0], r[:, 0]]), np.concatenate([np.ones(m, np.int64), -np.ones(m, np.int64)])
+    order = np.lexsort((pos, seq))
+    seq, pos, lay, d = seq[order], pos[order], lay[order], d[order]
+    now = np.full(2 * m, T, np.int64)
+    for k in range(T - 1, -1, -1):  # (the smallest covering layer wins: written last)
+        now[np.cumsum(np.where(lay == k, d, 0)) > 0] = k
+    tail = np.ones(2 * m, bool)
+    tail[:-1] = (seq[1:] != seq[:-1]) | (pos[1:] != pos[:-1])
+    t_seq, t_pos, t_cls = seq[tail], pos[tail], now[tail]
+    point = t_cls != np.concatenate([[T], t_cls])[:-1]
+    p_seq, p_pos, p_cls = t_seq[point], t_pos[point], t_cls[point]
+    n = len(p_pos)
+    p_off = np.searchsorted(p_seq, np.arange(n_seq + 1)).astype(np.uint64)
+    length = np.zeros(n, np.int64)
+    if n:
+        inside = p_seq[1:] == p_seq[:-1]
+        assert np.all(p_cls[:-1][~inside] == T) and p_cls[-1] == T  # a seqid's last point has class T
+        length[:-1] = np.where(inside, p_pos[1:] - p_pos[:-1], 0)
+    cb = np.zeros((T, n), np.int64)
+    for k in range(T):
+        mine = np.where(p_cls == k, length, 0)
+        cb[k] = np.cumsum(mine) - mine
+
+    def below(c, x):  # B_k(x) for every k: [T, nq]
+        first = p_off.astype(np.int64)[c]
+        i = np.searchsorted((p_seq << 32) | p_pos, (c << 32) | x, side="right") - 1
+        have = i >= first
+        i, first = np.where(have, i, 0), np.minimum(first, max(n - 1, 0))
+        out = np.zeros((T, len(c)), np.int64)
+        if n:
+            for k in range(T):
+                out[k] = np.where(have, cb[k, i] - cb[k, first] + np.where(p_cls[i] == k, x - p_pos[i], 0), 0)
+        return out
+
+    real = q[:, 1] < q[:, 2]
+    per = np.where(real, below(q[:, 0], q[:, 2]) - below(q[:, 0], q[:, 1]), 0)
+    counts = np.zeros((len(q), T + 1), np.int64)
+    counts[:, :T] = per.T
+    counts[:, T] = np.where(real, q[:, 2] - q[:, 1], 0) - counts[:, :T].sum(1)
+    best = np.where((counts[:, :T] > 0).any(1), np.argmax(counts[:, :T] > 0, 1), T) if T else np.full(len(q), T)
+    return p_off, p_pos.astype(np.uint32), p_cls.astype(np.uint8), cb.astype(np.uint64), counts.astype(np.uint32), best.astype(np.uint8)
+
+
 # ---- the example by hand: layers 0 = CDS, 1 = exon, 2 = gene; two seqids -----------------------------------------------------
 HAND_T, HAND_N_SEQ = 3, 2
 HAND_ROWS = np.array([

@@ -1,5 +1,6 @@
 """`gffx annotate` where no GPU is needed: the two restatements of the definition (tests/_annotate_definition.py) agree with
-each other, with the hand-written example and with the coverage definition; device/classmap_core.hpp, the code the kernels of
+each other, with the hand-written example and with the coverage definition, and the restatement over whole arrays that the large
+device cases use (sparse_np) agrees with them; device/classmap_core.hpp, the code the kernels of
 classmap.hip run, gives the definition's points, running sums and answers in its host build under AddressSanitizer +
 UndefinedBehaviorSanitizer (tools/classmap_check.cpp); the command line knows the command and refuses its usage errors like
 clap; without a handle the C-ABI reports an error."""
@@ -57,6 +58,62 @@ def test_the_sparse_restatement_agrees_with_the_coverage_definition(seed):
     every = cov.merge_rows(rows[:, 1:], n_seq)
     assert np.array_equal(counts[:, 0], cov.covered(first, regions[:, 0], regions[:, 1], regions[:, 2]))
     assert np.array_equal(counts[:, :T].sum(1), cov.covered(every, regions[:, 0], regions[:, 1], regions[:, 2]))
+
+
+# ---- sparse_np, the restatement over whole arrays that the large device cases are held to, against sparse -------------------
+
+def _np_agrees(n_seq, T, rows, regions=None):
+    regions = ad.probe_regions(n_seq, T, rows) if regions is None else regions
+    a, b = ad.sparse(n_seq, T, rows, regions), ad.sparse_np(n_seq, T, rows, regions)
+    for name, x, y in zip(("p_off", "pos", "cls", "cb", "counts", "class"), a, b):
+        assert x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x, y), name
+    return a
+
+
+def test_the_array_restatement_gives_the_hand_answers_and_refuses_what_sparse_refuses():
+    assert ad.same(ad.sparse_np(ad.HAND_N_SEQ, ad.HAND_T, ad.HAND_ROWS, ad.HAND_REGIONS), ad.hand())
+    _np_agrees(ad.HAND_N_SEQ, ad.HAND_T, ad.HAND_ROWS)
+    _np_agrees(3, 4, np.zeros((0, 4), np.uint32), np.array([[0, 5, 25], [2, 0, ad.U32_MAX], [1, 9, 3]], np.uint32))  # no rows
+    _np_agrees(3, 2, ad.HAND_ROWS[ad.HAND_ROWS[:, 0] < 2], np.zeros((0, 3), np.uint32))  # no regions; seqid 2 without points
+    for bad in ([3, 0, 1, 2], [0, 2, 1, 2], [0, 0, 2, 2], [0, 0, 3, 2]):
+        with pytest.raises(ValueError):
+            ad.sparse_np(2, 3, [bad], [])
+    with pytest.raises(ValueError):
+        ad.sparse_np(2, 3, ad.HAND_ROWS, [[2, 0, 1]])
+
+
+@pytest.mark.parametrize("seed", range(40))
+def test_the_array_restatement_agrees_with_sparse_on_random_cases(seed):
+    n_seq, T, rows, regions = ad.random_case(seed)
+    _np_agrees(n_seq, T, rows, np.concatenate([regions, ad.probe_regions(n_seq, T, rows)]))
+    rng = np.random.default_rng(seed)
+    _np_agrees(n_seq, T, np.repeat(rows, 2, 0)[rng.permutation(2 * len(rows))], regions)  # a multiset: order and duplicates
+
+
+def test_the_array_restatement_agrees_with_sparse_on_the_tile_edge_layouts():
+    S, _, _ = engine._classmap_constants()
+    for n in (2, S - 2, S, S + 2):
+        _np_agrees(1, 3, ad.events_case(n, T=3))
+    lead = ad.events_case(S - 16, T=32)
+    P = 1 << 20
+    run = np.array([[k, 0, P, P + 100 + k] for k in range(32)], np.uint32)
+    _np_agrees(1, 32, np.concatenate([lead, run]))  # 32 layers toggle at one position
+    both = np.array([[k, 0, P - 50, P] for k in range(32)] + [[k, 0, P, P + 50] for k in range(32)], np.uint32)
+    assert P not in _np_agrees(1, 32, np.concatenate([lead, both]))[1].tolist()  # a close and an open of every layer at P: no point
+    _np_agrees(2, 2, np.concatenate([ad.events_case(S, T=2, seq=0), ad.events_case(S + 2, T=2, seq=1)]))  # a seqid border
+    i = np.arange(S - 1, dtype=np.int64)
+    inner = np.stack([np.full(S - 1, 1), np.zeros(S - 1, np.int64), 10 + 7 * i, 13 + 7 * i], 1).astype(np.uint32)
+    cover = np.array([[0, 0, 0, 1 << 20], [2, 0, 1, 1 << 20]], np.uint32)
+    want = _np_agrees(1, 3, np.concatenate([inner, cover]))  # rows that cancel under a mask that is not 0: class 0 all the way
+    assert want[1].tolist() == [0, 1 << 20] and want[2].tolist() == [0, 3]
+
+
+def test_the_array_restatement_at_both_ends_of_32_bits():
+    rows = np.array([[1, 0, 0, 1], [0, 0, ad.U32_MAX - 1, ad.U32_MAX], [1, 0, 5, ad.U32_MAX], [0, 1, 0, ad.U32_MAX]], np.uint32)
+    want = _np_agrees(3, 2, rows)
+    assert want[3].max() >= (1 << 32)
+    regions = np.array([[0, 0, ad.U32_MAX], [1, 0, ad.U32_MAX], [1, ad.U32_MAX - 1, ad.U32_MAX], [0, ad.U32_MAX, 0], [2, 0, ad.U32_MAX]], np.uint32)
+    assert _np_agrees(3, 2, rows, regions)[4].tolist() == [[1, ad.U32_MAX - 5, 4], [ad.U32_MAX, 0, 0], [1, 0, 0], [0, 0, 0], [0, 0, ad.U32_MAX]]
 
 
 # ---- device/classmap_core.hpp under the sanitizers --------------------------------------------------------------------
@@ -205,8 +262,8 @@ def test_a_null_handle_and_bad_shapes_are_reported_not_crashed_on():
     assert L.gffx_hip_classmap_create(0, 4, 33, C.byref(h)) == -1 and not h.value
     assert L.gffx_hip_classmap_create(0, 1 << 28, 32, C.byref(h)) == -1 and b"32 bits" in L.gffx_hip_last_error()
     assert L.gffx_hip_classmap_create(0, 4, 3, None) == -1
-    S, B = engine._classmap_constants()
-    assert S >= 4 and S % 4 == 0 and B >= 64
+    S, B, carry = engine._classmap_constants()
+    assert S >= 4 and S % 4 == 0 and B >= 64 and carry >= 64
 
 
 @pytest.mark.skipif(engine.device_count() > 0, reason="checks the behaviour of a machine without a GPU")

@@ -47,7 +47,7 @@ def test_the_hand_example():
 
 
 def _event_counts():
-    S, _ = engine._classmap_constants()
+    S, _, _ = engine._classmap_constants()
     # (a span gives two events, so an event count is even: the odd counts 1, S - 1, S + 1 and 2 S + 1 are taken from both sides)
     return sorted({2, S - 2, S, S + 2, 2 * S, 2 * S + 2})
 
@@ -60,7 +60,7 @@ def test_event_counts_around_the_scan_tile():
 
 
 def test_runs_and_seqid_borders_at_a_tile_edge():
-    S, _ = engine._classmap_constants()
+    S, _, _ = engine._classmap_constants()
     # 32 layers toggle at one position: the run of 32 equal keys lies across the edge between tile 0 and tile 1
     lead = ad.events_case(S - 16, T=32)  # S - 16 events before position P, all far below it
     P = 1 << 20
@@ -126,7 +126,7 @@ def test_the_grouping_of_the_rows_does_not_matter():
 
 
 def test_region_counts_around_the_wave_and_the_block():
-    _, B = engine._classmap_constants()
+    _, B, _ = engine._classmap_constants()
     n_seq, T, rows, _ = ad.random_case(11, n=100)
     rng = np.random.default_rng(5)
     m = build(n_seq, T, rows)
