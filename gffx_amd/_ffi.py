@@ -281,9 +281,11 @@ SIGNATURES = {
     "gffx_hip_effect_create": (C.c_int, [vp, C.c_uint64, u32p, C.c_uint64, u8p, C.c_uint64, C.POINTER(vp)]),
     "gffx_hip_effect_copy_transcripts": (C.c_int, [vp, u8p, u32p]),
     "gffx_hip_effect_run_start": (C.c_int, [vp, C.c_int, u32p, C.c_uint64]),
+    "gffx_hip_effect_run_any_start": (C.c_int, [vp, C.c_int, u32p, C.c_uint64, u8p, C.c_uint64]),
     "gffx_hip_effect_run_wait": (C.c_int, [vp, C.c_int, C.POINTER(u64p), C.POINTER(u8p), C.POINTER(u8p), u64p]),
     "gffx_hip_effect_stage_ms": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gffx_hip_effect_stats": (C.c_int, [vp, u64p, u64p]),
+    "gffx_hip_effect_arena_grows": (C.c_int, [vp, u64p]),
     "gffx_hip_effect_destroy": (None, [vp]),
 }
 

@@ -23,6 +23,13 @@
 //                         there (a segment is short; the engine lists it by start), then effect::classify -- the D search
 //                         and the E search side by side, the three codon bases as independent loads -- and the 32-byte
 //                         record as two 16-byte stores.  Every record has one writer: no atomics.
+// RUN WITH --indels (_run_any_start): a chunk's rows are (sequence number, x0, d, m, 64-bit arena offset) and come
+// with a byte arena that holds R' then A' of every row; the arena goes through the slot's pinned staging.
+//   k_effect_alleles_any  per allele the footprint's region [lo - 1, hi), ref_match over R', and the refusals: a bad sequence
+//                         number, x0 = 0, d = m = 0, d or m beyond 65 535, an insertion in front of base 1, bytes that leave
+//                         the arena
+//   k_effect_pairs_any    k_effect_pairs with the wider row: effect::classify for d == m == 1 (the same records), else
+//                         effect::classify_any
 // The class counts of --summary are summed by the host from the records it formats anyway.
 // The records, the offsets and ref_match of a chunk come back through the slot's pinned buffers (_run_start / _run_wait), so the
 // host formats chunk k while chunk k + 1 is classified.
@@ -44,7 +51,8 @@ namespace {
 
 constexpr int kPairThreads = 256;
 constexpr uint32_t kNoSeq = 0xFFFFFFFFu;  // an allele on a sequence the genome lacks: no pair, ref_match 0
-enum : uint32_t { kErrTranscript = 1u, kErrSort = 2u | 4u, kErrEmptyRow = 8u, kErrEmptyTranscript = 16u, kErrKind = 32u, kErrAllele = 64u };
+enum : uint32_t { kErrTranscript = 1u, kErrSort = 2u | 4u, kErrEmptyRow = 8u, kErrEmptyTranscript = 16u, kErrKind = 32u, kErrAllele = 64u, kErrArena = 128u };
+constexpr uint32_t kMaxAlleleBytes = 65535;
 
 struct Span {  // what the host reads back per transcript
     uint32_t seq, lo0, hi, dropped;
@@ -99,7 +107,7 @@ __global__ __launch_bounds__(256) void k_effect_transcripts(const uint32_t *keys
         const bool ok = effect::build_transcript(start0, end, row_seq, pre, pmax, f0, f1, f2, seq_len, n_seq, &o, &lo0, &hi);
         const uint8_t fl = flags[t];
         const bool keep = ok && !(fl & effect::kFlagDropped);
-        o.flags = fl;
+        o.flags = fl | (o.flags & effect::kFlagOverlap);
         o.base = keep ? seq_off[o.seq] : 0ull;
         s = Span{o.seq, lo0, hi, keep ? 0u : 1u};
     }
@@ -120,6 +128,28 @@ __global__ __launch_bounds__(256) void k_effect_alleles(const uint32_t *alleles,
     q_start[i] = served ? x - 1 : 0u;
     q_end[i] = served ? x : 1u;
     ref_match[i] = served ? effect::ref_match((uint8_t)ra, arena[seq_off[sq] + (x - 1)]) : 0;
+}
+
+// --indels: regions for the engine from the footprint, ref_match over R', the refusal of a bad row.  Rows of 6 words: sequence
+// number, x0, d, m, the offset of R' (d bytes) then A' (m bytes) in bytes[0, n_bytes)
+__global__ __launch_bounds__(256) void k_effect_alleles_any(const uint32_t *alleles, u64 n, const uint8_t *bytes, u64 n_bytes, const uint8_t *arena, const u64 *seq_off,
+                                                            const uint32_t *seq_len, uint32_t n_seq, uint32_t *q_chr, uint32_t *q_start, uint32_t *q_end, uint8_t *ref_match,
+                                                            uint32_t *err) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t *row = alleles + 6 * i;
+    const uint32_t sq = row[0], x0 = row[1], d = row[2], m = row[3];
+    const u64 off = (u64)row[4] | (u64)row[5] << 32;
+    const bool bad = (sq >= n_seq && sq != kNoSeq) || x0 == 0 || (d == 0 && (m == 0 || x0 == 1)) || d > kMaxAlleleBytes || m > kMaxAlleleBytes;
+    const bool outside = off > n_bytes || (u64)d + m > n_bytes - off;  // (its bytes are not read then)
+    if (bad) atomicOr(err, kErrAllele);
+    if (outside) atomicOr(err, kErrArena);
+    const u64 lo = d ? (u64)x0 : (u64)x0 - 1, hi = d ? (u64)x0 + d - 1 : (u64)x0;  // the footprint, 1-based and closed
+    const bool served = !bad && !outside && sq < n_seq && hi <= seq_len[sq < n_seq ? sq : 0];
+    q_chr[i] = served ? sq : n_seq;
+    q_start[i] = served ? (uint32_t)(lo - 1) : 0u;
+    q_end[i] = served ? (uint32_t)hi : 1u;
+    ref_match[i] = served ? effect::ref_match_run(bytes + off, d, arena + seq_off[sq] + (x0 - 1)) : 0;
 }
 
 struct PairArgs {
@@ -163,6 +193,43 @@ __global__ __launch_bounds__(kPairThreads) void k_effect_pairs(const PairArgs a)
     a.out[2 * (seg0 + rank) + 1] = w[1];
 }
 
+struct PairAnyArgs {
+    PairArgs a;            // alleles: the rows of 6 words
+    const uint8_t *bytes;  // the chunk's arena
+};
+
+// one thread per pair, as k_effect_pairs: the same CSR and rank logic, the wider row
+__global__ __launch_bounds__(kPairThreads) void k_effect_pairs_any(const PairAnyArgs args) {
+    const PairArgs &a = args.a;
+    __shared__ u64 s_range[2];
+    const u64 o0 = (u64)blockIdx.x * kPairThreads;
+    if (threadIdx.x == 0) {
+        const u64 o_last = (o0 + kPairThreads < a.n_pairs ? o0 + kPairThreads : a.n_pairs) - 1;
+        s_range[0] = seq::last_le(a.offsets, a.n_alleles + 1, o0);
+        s_range[1] = seq::last_le(a.offsets, a.n_alleles + 1, o_last);
+    }
+    __syncthreads();
+    const u64 o = o0 + threadIdx.x;
+    if (o >= a.n_pairs) return;
+    const u64 i = s_range[0] + seq::last_le(a.offsets + s_range[0], s_range[1] - s_range[0] + 1, o);
+    const u64 seg0 = a.offsets[i], seg1 = a.offsets[i + 1];
+    const uint32_t t = a.fids[o];
+    const uint32_t *row = a.alleles + 6 * i;
+    const uint32_t x0 = row[1], d = row[2], m = row[3];
+    const uint8_t *ins = args.bytes + ((u64)row[4] | (u64)row[5] << 32) + d;  // A' (k_effect_alleles_any has checked the bounds)
+    const uint8_t rm = a.ref_match[i];
+    const effect::Transcript tr = a.tr[t];
+    uint32_t rank = 0;
+    for (u64 j = seg0; j < seg1; ++j) rank += a.fids[j] < t ? 1u : 0u;
+    effect::Record r = d == 1 && m == 1 ? effect::classify(a.rows, tr, a.arena, x0, ins[0]) : effect::classify_any(a.rows, tr, a.arena, x0, d, m, ins);
+    r.transcript = t;
+    r.ref_match = rm;
+    uint4 w[2];
+    __builtin_memcpy(w, &r, 32);
+    a.out[2 * (seg0 + rank)] = w[0];
+    a.out[2 * (seg0 + rank) + 1] = w[1];
+}
+
 }  // namespace
 
 struct gffx_hip_effect : HandleStatus {
@@ -171,7 +238,7 @@ struct gffx_hip_effect : HandleStatus {
     const u64 *seq_off = nullptr;
     const uint32_t *seq_len = nullptr;
     uint32_t n_seq = 0;
-    u64 n_rows = 0, n_tr = 0, n_kept = 0, max_alleles = 0, grows = 0;
+    u64 n_rows = 0, n_tr = 0, n_kept = 0, max_alleles = 0, grows = 0, arena_grows = 0;
     hipStream_t stream[2] = {nullptr, nullptr};
     hipEvent_t ev[2] = {nullptr, nullptr}, slot_ev[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};  // per slot: classify begins, ends, the copies are through
     DevArr<uint32_t> rows, keys_a, keys_b, work, err, len, start0, end, row_seq, pmax;
@@ -187,6 +254,9 @@ struct gffx_hip_effect : HandleStatus {
         DevArr<uint8_t> ref_match;
         DevArr<u64> zero_off;  // the offsets of a chunk when no transcript is kept
         DevArr<uint4> records;
+        DevArr<uint8_t> bytes;         // --indels: the chunk's arena
+        uint8_t *h_bytes = nullptr;    // its pinned staging; grows like the record buffer
+        u64 h_bytes_cap = 0;
         uint8_t *pinned = nullptr;  // offsets, then ref_match, then the records
         u64 pinned_cap = 0, n = 0, pairs = 0;
         uint32_t *h_err = nullptr;  // pinned
@@ -198,6 +268,7 @@ struct gffx_hip_effect : HandleStatus {
             if (stream[k]) (void)hipStreamSynchronize(stream[k]);
             if (slot[k].batch) gffx_hip_batch_destroy(slot[k].batch);
             if (slot[k].pinned) (void)hipHostFree(slot[k].pinned);
+            if (slot[k].h_bytes) (void)hipHostFree(slot[k].h_bytes);
             if (slot[k].h_err) (void)hipHostFree(slot[k].h_err);
             if (ev[k]) (void)hipEventDestroy(ev[k]);
             for (int j = 0; j < 3; ++j)
@@ -318,31 +389,59 @@ extern "C" int gffx_hip_effect_copy_transcripts(const gffx_hip_effect *h, uint8_
     return GFFX_OK;
 }
 
-extern "C" int gffx_hip_effect_run_start(gffx_hip_effect *h, int k, const uint32_t *alleles, uint64_t n) {
-    if (int rc = enter_handle(h, "gffx_hip_effect_run_start")) return rc;
-    if (k < 0 || k > 1) return fail(GFFX_E_INVALID, "gffx_hip_effect_run_start: slot %d (0 or 1)", k);
+namespace {
+
+// _run_start (any == false: rows of 3 words) and _run_any_start (rows of 6 words and an arena) share everything but the two kernels
+int run_start(gffx_hip_effect *h, int k, const uint32_t *alleles, uint64_t n, bool any, const uint8_t *ins_bytes, uint64_t n_bytes, const char *who) {
+    if (int rc = enter_handle(h, who)) return rc;
+    if (k < 0 || k > 1) return fail(GFFX_E_INVALID, "%s: slot %d (0 or 1)", who, k);
     gffx_hip_effect::Slot &sl = h->slot[k];
-    if (sl.busy) return fail(GFFX_E_STATE, "gffx_hip_effect_run_start: slot %d is in flight: call gffx_hip_effect_run_wait first", k);
-    if (n > h->max_alleles) return fail(GFFX_E_INVALID, "gffx_hip_effect_run_start: %llu alleles exceed the object's %llu", (u64)n, h->max_alleles);
-    if (n && !alleles) return fail(GFFX_E_INVALID, "gffx_hip_effect_run_start: alleles is NULL");
+    if (sl.busy) return fail(GFFX_E_STATE, "%s: slot %d is in flight: call gffx_hip_effect_run_wait first", who, k);
+    if (n > h->max_alleles) return fail(GFFX_E_INVALID, "%s: %llu alleles exceed the object's %llu", who, (u64)n, h->max_alleles);
+    if (n && !alleles) return fail(GFFX_E_INVALID, "%s: alleles is NULL", who);
+    if (any && n_bytes && !ins_bytes) return fail(GFFX_E_INVALID, "%s: arena is NULL", who);
     hipStream_t s = h->stream[k];
     sl.n = n, sl.pairs = 0;
     const u64 m = std::max<u64>(n, 1);
-    GFFX_KEEP_HIP(h, sl.alleles.ensure(3 * m));
+    const u64 words = any ? 6 : 3;
+    GFFX_KEEP_HIP(h, sl.alleles.ensure(words * m));
+    if (any && n) {
+        // the arena: into the slot's pinned staging, which grows by an eighth more than asked, then to the device
+        if (n_bytes > sl.h_bytes_cap) {
+            h->arena_grows += sl.h_bytes_cap ? 1 : 0;
+            if (sl.h_bytes) (void)hipHostFree(sl.h_bytes);
+            sl.h_bytes = nullptr, sl.h_bytes_cap = 0;
+            const u64 want = n_bytes + n_bytes / 8;
+            if (hipHostMalloc((void **)&sl.h_bytes, want) != hipSuccess) return keep_failure(h, fail(GFFX_E_OOM, "%s: pinned arena of %llu bytes", who, want));
+            sl.h_bytes_cap = want;
+        }
+        GFFX_KEEP_HIP(h, sl.bytes.ensure(std::max<u64>(sl.h_bytes_cap, 1)));
+        if (n_bytes) {
+            std::memcpy(sl.h_bytes, ins_bytes, n_bytes);
+            GFFX_KEEP_HIP(h, hipMemcpyAsync(sl.bytes.p, sl.h_bytes, n_bytes, hipMemcpyHostToDevice, s));
+        }
+    }
     for (DevArr<uint32_t> *a : {&sl.q_chr, &sl.q_start, &sl.q_end}) GFFX_KEEP_HIP(h, a->ensure(m));
     GFFX_KEEP_HIP(h, sl.ref_match.ensure(m));
     const u64 *d_off = nullptr;
     const uint32_t *d_fids = nullptr;
     if (n) {
-        GFFX_KEEP_HIP(h, hipMemcpyAsync(sl.alleles.p, alleles, 12 * n, hipMemcpyHostToDevice, s));
+        GFFX_KEEP_HIP(h, hipMemcpyAsync(sl.alleles.p, alleles, 4 * words * n, hipMemcpyHostToDevice, s));
         GFFX_KEEP_HIP(h, hipMemsetAsync(h->err.p, 0, 4, s));
-        hipLaunchKernelGGL(k_effect_alleles, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, sl.alleles.p, n, h->arena, h->seq_off, h->seq_len, h->n_seq, sl.q_chr.p,
-                           sl.q_start.p, sl.q_end.p, sl.ref_match.p, h->err.p);
+        if (any)
+            hipLaunchKernelGGL(k_effect_alleles_any, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, sl.alleles.p, n, sl.bytes.p, n_bytes, h->arena, h->seq_off,
+                               h->seq_len, h->n_seq, sl.q_chr.p, sl.q_start.p, sl.q_end.p, sl.ref_match.p, h->err.p);
+        else
+            hipLaunchKernelGGL(k_effect_alleles, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, sl.alleles.p, n, h->arena, h->seq_off, h->seq_len, h->n_seq, sl.q_chr.p,
+                               sl.q_start.p, sl.q_end.p, sl.ref_match.p, h->err.p);
         GFFX_KEEP_HIP(h, hipGetLastError());
         GFFX_KEEP_HIP(h, hipMemcpyAsync(sl.h_err, h->err.p, 4, hipMemcpyDeviceToHost, s));
         GFFX_KEEP_HIP(h, hipStreamSynchronize(s));  // (the caller's rows are free from here on; the engine's stream may read the columns)
         if (*sl.h_err & kErrAllele)
-            return keep_failure(h, fail(GFFX_E_CHR_RANGE, "gffx_hip_effect_run_start: an allele row with a sequence number >= %u (and not %u) or with x = 0", h->n_seq, kNoSeq));
+            return keep_failure(h, any ? fail(GFFX_E_CHR_RANGE, "%s: an allele row with a sequence number >= %u (and not %u), with x0 = 0, with d = m = 0, with d or m above %u, or an insertion at x0 = 1",
+                                              who, h->n_seq, kNoSeq, kMaxAlleleBytes)
+                                       : fail(GFFX_E_CHR_RANGE, "%s: an allele row with a sequence number >= %u (and not %u) or with x = 0", who, h->n_seq, kNoSeq));
+        if (*sl.h_err & kErrArena) return keep_failure(h, fail(GFFX_E_INVALID, "%s: an allele row whose bytes leave the arena of %llu bytes", who, (u64)n_bytes));
     }
     if (n && sl.batch) {
         // the pair CSR: the engine's direct pass, segments in allele order
@@ -371,14 +470,15 @@ extern "C" int gffx_hip_effect_run_start(gffx_hip_effect *h, int k, const uint32
         if (sl.pinned) (void)hipHostFree(sl.pinned);
         sl.pinned = nullptr, sl.pinned_cap = 0;
         const u64 want = bytes + bytes / 8;  // (32 bytes per pair: at 4 Mi alleles of a dozen pairs each 1.7 GB per slot)
-        if (hipHostMalloc((void **)&sl.pinned, want) != hipSuccess) return keep_failure(h, fail(GFFX_E_OOM, "gffx_hip_effect_run_start: pinned buffer of %llu bytes", want));
+        if (hipHostMalloc((void **)&sl.pinned, want) != hipSuccess) return keep_failure(h, fail(GFFX_E_OOM, "%s: pinned buffer of %llu bytes", who, want));
         sl.pinned_cap = want;
     }
     GFFX_KEEP_HIP(h, hipEventRecord(h->slot_ev[k][0], s));
     if (sl.pairs) {
         const PairArgs a{d_off,   d_fids,   n, sl.pairs, sl.alleles.p, sl.ref_match.p, h->tr.p, effect::Rows{h->start0.p, h->end.p, h->pre.p, h->pmax.p},
                          h->arena, sl.records.p};
-        hipLaunchKernelGGL(k_effect_pairs, dim3((uint32_t)((sl.pairs + kPairThreads - 1) / kPairThreads)), dim3(kPairThreads), 0, s, a);
+        if (any) hipLaunchKernelGGL(k_effect_pairs_any, dim3((uint32_t)((sl.pairs + kPairThreads - 1) / kPairThreads)), dim3(kPairThreads), 0, s, PairAnyArgs{a, sl.bytes.p});
+        else hipLaunchKernelGGL(k_effect_pairs, dim3((uint32_t)((sl.pairs + kPairThreads - 1) / kPairThreads)), dim3(kPairThreads), 0, s, a);
         GFFX_KEEP_HIP(h, hipGetLastError());
     }
     GFFX_KEEP_HIP(h, hipEventRecord(h->slot_ev[k][1], s));
@@ -388,6 +488,16 @@ extern "C" int gffx_hip_effect_run_start(gffx_hip_effect *h, int k, const uint32
     GFFX_KEEP_HIP(h, hipEventRecord(h->slot_ev[k][2], s));
     sl.busy = true;
     return GFFX_OK;
+}
+
+}  // namespace
+
+extern "C" int gffx_hip_effect_run_start(gffx_hip_effect *h, int k, const uint32_t *alleles, uint64_t n) {
+    return run_start(h, k, alleles, n, false, nullptr, 0, "gffx_hip_effect_run_start");
+}
+
+extern "C" int gffx_hip_effect_run_any_start(gffx_hip_effect *h, int k, const uint32_t *rows, uint64_t n, const uint8_t *arena, uint64_t arena_bytes) {
+    return run_start(h, k, rows, n, true, arena, arena_bytes, "gffx_hip_effect_run_any_start");
 }
 
 extern "C" int gffx_hip_effect_run_wait(gffx_hip_effect *h, int k, const uint64_t **offsets, const uint8_t **ref_match, const uint8_t **records, uint64_t *n_pairs) {
@@ -418,6 +528,12 @@ extern "C" int gffx_hip_effect_stats(const gffx_hip_effect *h, uint64_t *kept, u
     if (!h) return fail(GFFX_E_INVALID, "gffx_hip_effect_stats: the effect handle is NULL");
     if (kept) *kept = h->n_kept;
     if (grows) *grows = h->grows;
+    return GFFX_OK;
+}
+
+extern "C" int gffx_hip_effect_arena_grows(const gffx_hip_effect *h, uint64_t *grows) {
+    if (!h) return fail(GFFX_E_INVALID, "gffx_hip_effect_arena_grows: the effect handle is NULL");
+    if (grows) *grows = h->arena_grows;
     return GFFX_OK;
 }
 

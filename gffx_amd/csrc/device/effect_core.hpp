@@ -1,5 +1,6 @@
 // effect_core.hpp -- the rules of `gffx effect` for the host (g++) and the device (hipcc): what a single-base
-// substitution at base x (1-based) with alternate base ALT does to one transcript whose span contains x.
+// substitution at base x (1-based) with alternate base ALT does to one transcript whose span contains x.  (What an insertion,
+// a deletion or a multi-base substitution does, `--indels`, is classify_any further down)
 //
 // TRANSCRIPT.  D: its CDS rows ordered by (start, line order), pre the exclusive sums of their lengths, L the total, p the phase
 // of the leading segment, C = (L - p) / 3 for L > p (else 0).  E: its exon rows in the same order, or D when it has none; pmax
@@ -48,7 +49,14 @@ enum : uint8_t {
     kSpliceDonor = 12,
     kSpliceAcceptor = 13,
     kIntergenic = 14,
-    kClasses = 15
+    kClasses = 15,  // what the flagless command lists
+    // --indels only (26.4), behind the 15 of the flagless path
+    kFrameshift = 15,
+    kInframeInsertion = 16,
+    kInframeDeletion = 17,
+    kTranscriptAblation = 18,
+    kUnclassifiedModel = 19,
+    kClassesAll = 20
 };
 GFFX_HD inline const char *class_name(uint32_t cls) {
     switch (cls) {
@@ -67,12 +75,20 @@ GFFX_HD inline const char *class_name(uint32_t cls) {
         case kSpliceDonor: return "splice_donor";
         case kSpliceAcceptor: return "splice_acceptor";
         case kIntergenic: return "intergenic";
+        case kFrameshift: return "frameshift";
+        case kInframeInsertion: return "inframe_insertion";
+        case kInframeDeletion: return "inframe_deletion";
+        case kTranscriptAblation: return "transcript_ablation";
+        case kUnclassifiedModel: return "unclassified_model";
         default: return "?";
     }
 }
 GFFX_HD inline bool is_coding(uint32_t cls) { return cls >= kCodingUnknown && cls <= kMissense; }  // (the four coding columns are filled)
 
 enum : uint32_t { kFlagMinus = 1, kFlagPhase = 6, kFlagDropped = 8 };  // a transcript's flag byte, as seq's rec_flags
+// set by build_transcript, never by the caller: two rows of D or two rows of E overlap (touching rows do not).  Only classify_any
+// reads it.
+enum : uint32_t { kFlagOverlap = 16 };
 
 // what one (allele, transcript) pair gives: 32 bytes, two 16-byte stores.  Coding classes fill everything; partial_codon q
 // only; every other class leaves the coding fields 0.  The codons are the genome's bytes as they are (not case folded).
@@ -193,20 +209,221 @@ GFFX_HD inline Record classify(const Rows &r, const Transcript &t, const uint8_t
     return o;
 }
 
+// ---- --indels: an allele that covers an interval and carries inserted bytes.  After trimming, R' has d bases from
+// x0 on and A' has m bytes (ins).  The footprint F is [x0, x0 + d - 1] for d > 0 and the two flanking bases [x0 - 1, x0] for
+// d == 0; F' = [lo, hi] is F clipped to the span.  F' HITS a set of bases W when it meets W (d > 0) or lies inside W (d == 0).
+// The first rule that applies:
+//   0 unclassified_model   rows of D or of E overlap (kFlagOverlap): prefix sums cannot count an interval's bases then
+//   1 transcript_ablation  d > 0 and F holds the whole span
+//   2 splice               of the donor / acceptor windows (two bases at either end of every gap between E rows, fewer in a gap
+//                          of fewer) that F' hits the one with the smallest first base, the left one on a tie
+//   3 coding               F' hits D.  pos(x) = D bases below x; qa = pos(lo) for d > 0 and pos(x0) for d == 0 (where the bytes
+//                          go in); dc = D bases in F' (d > 0; else 0); [ta, tb) is the run in transcription order.  Then
+//                          partial_codon, start_lost, frameshift, or the windows of 3d (classify_any below)
+//   4 exonic               F' hits E: rule 2 of the SNV at the smallest base of F' in E
+//   5 intron
+// With disjoint rows every count is one binary search over start0 and one difference of pre.
+
+// the bases of rows [f0, ..) below x (1-based, x >= 1): n_lt = f0 + #{rows with start0 < x}, as count_starts gives it
+GFFX_HD inline u64 bases_below(const Rows &r, uint32_t f0, uint32_t n_lt, u64 x) {
+    if (n_lt == f0) return 0;
+    const uint32_t j = n_lt - 1;
+    const u64 e = r.end[j], cut = e < x - 1 ? e : x - 1;  // (start0[j] <= x - 1)
+    return r.pre[j] - r.pre[f0] + (cut - r.start0[j]);
+}
+
+// four searches side by side, their loads independent iteration by iteration: out[l] = first + #{rows with start0 < key[l]},
+// lanes 0 and 1 over D, lanes 2 and 3 over E
+GFFX_HD inline void count_starts(const Rows &r, const Transcript &t, const u64 (&key)[4], uint32_t (&out)[4]) {
+    uint32_t at[4] = {t.d0, t.d0, t.e0, t.e0};
+    uint32_t n[4] = {t.d1 - t.d0, t.d1 - t.d0, t.e1 - t.e0, t.e1 - t.e0};
+    while (n[0] | n[1] | n[2] | n[3]) {
+        uint32_t v[4];
+        for (int l = 0; l < 4; ++l) v[l] = n[l] ? r.start0[at[l] + (n[l] >> 1)] : 0u;
+        for (int l = 0; l < 4; ++l) {
+            const uint32_t h = n[l] >> 1;
+            if (n[l]) {
+                if (v[l] < key[l]) at[l] += h + 1, n[l] -= h + 1;
+                else n[l] = h;
+            }
+        }
+    }
+    for (int l = 0; l < 4; ++l) out[l] = at[l];
+}
+
+// rule 2 for F' = [lo, hi]: the gap between E rows r - 1 and r that can hold the first window hit is the first one with bases
+// that ends at or behind lo (every earlier window ends before lo; were a later one hit, this gap's right window would be too).
+// n_lo = e0 + #{E rows with start0 < lo}.  Touching rows have no gap: start0 - pre ascends by the gaps' lengths, so the first
+// row behind a chain of them is one more search.  Returns kIntron for "no window is hit".
+GFFX_HD inline uint8_t splice_class(const Rows &r, const Transcript &t, u64 lo, u64 hi, bool inside, uint32_t n_lo) {
+    uint32_t g = n_lo > t.e0 + 1 ? n_lo : t.e0 + 1;
+    if (g >= t.e1) return kIntron;
+    if (r.start0[g] == r.end[g - 1]) {  // (rare: a chain of touching rows)
+        const u64 pre0 = r.pre[t.e0], f = (u64)r.start0[g - 1] - (r.pre[g - 1] - pre0);
+        uint32_t at = g, n = t.e1 - g;
+        while (n) {
+            const uint32_t h = n >> 1;
+            if ((u64)r.start0[at + h] - (r.pre[at + h] - pre0) <= f) at += h + 1, n -= h + 1;
+            else n = h;
+        }
+        g = at;
+        if (g >= t.e1) return kIntron;
+    }
+    const bool minus = t.flags & kFlagMinus;
+    const u64 a = r.end[g - 1], b = (u64)r.start0[g] + 1;  // the gap's bases: a + 1 .. b - 1
+    const u64 l0 = a + 1, l1 = a + 2 < b - 1 ? a + 2 : b - 1, r0 = b - 2 > a + 1 ? b - 2 : a + 1, r1 = b - 1;
+    if (inside ? (l0 <= lo && hi <= l1) : (l0 <= hi && lo <= l1)) return minus ? kSpliceAcceptor : kSpliceDonor;
+    if (inside ? (r0 <= lo && hi <= r1) : (r0 <= hi && lo <= r1)) return minus ? kSpliceDonor : kSpliceAcceptor;
+    return kIntron;
+}
+
+// the byte at transcription position tq of the CDS (located on its own, complemented on minus)
+GFFX_HD inline u64 cds_at(const Rows &r, const Transcript &t, u64 tq) {
+    const u64 xm = (t.flags & kFlagMinus) ? t.L - 1 - tq : tq;
+    const u64 row = seq::locate_row(r.pre, t.d0, t.d1, xm);
+    return t.base + (u64)r.start0[row] + (xm - (r.pre[row] - r.pre[t.d0]));
+}
+
+// a non-SNV allele (d != 1 or m != 1, not both 0) against kept transcript t whose span overlaps F.  ins: A', m bytes.  The record's
+// codon and amino-acid bytes stay 0; rule 3 fills q (partial_codon: q only), c and k.  transcript and ref_match are the caller's.
+GFFX_HD inline Record classify_any(const Rows &r, const Transcript &t, const uint8_t *bases, uint32_t x0, uint32_t d, uint32_t m, const uint8_t *ins) {
+    Record o{};
+    if (t.flags & kFlagOverlap) {
+        o.cls = kUnclassifiedModel;
+        return o;
+    }
+    const bool minus = t.flags & kFlagMinus, del = d > 0, has_d = t.d1 > t.d0;
+    // the span: D and E are sorted and disjoint, so their first starts and last ends give it
+    const uint32_t s_d = has_d ? r.start0[t.d0] : 0xFFFFFFFFu, s_e = r.start0[t.e0], e_d = has_d ? r.end[t.d1 - 1] : 0u, e_e = r.end[t.e1 - 1];
+    const u64 span_lo = (u64)(s_d < s_e ? s_d : s_e) + 1, span_hi = e_d > e_e ? e_d : e_e;
+    const u64 f_lo = del ? (u64)x0 : (u64)x0 - 1, f_hi = del ? (u64)x0 + d - 1 : (u64)x0;
+    if (del && f_lo <= span_lo && f_hi >= span_hi) {
+        o.cls = kTranscriptAblation;
+        return o;
+    }
+    const u64 lo = f_lo > span_lo ? f_lo : span_lo, hi = f_hi < span_hi ? f_hi : span_hi, width = hi - lo + 1;
+    const u64 key[4] = {lo, hi + 1, lo, hi + 1};
+    uint32_t n[4];
+    count_starts(r, t, key, n);
+    const u64 d_lo = bases_below(r, t.d0, n[0], lo), d_cov = bases_below(r, t.d0, n[1], hi + 1) - d_lo;
+    const u64 e_lo = bases_below(r, t.e0, n[2], lo), e_cov = bases_below(r, t.e0, n[3], hi + 1) - e_lo;
+    const uint8_t sp = splice_class(r, t, lo, hi, !del, n[2]);
+    if (sp != kIntron) {
+        o.cls = sp;
+        return o;
+    }
+    if (del ? d_cov > 0 : d_cov == width) {
+        const uint32_t p = (t.flags & kFlagPhase) >> 1;
+        const u64 C = t.L > p ? (t.L - p) / 3 : 0, dc = del ? d_cov : 0;
+        const u64 qa = del ? d_lo : d_lo + ((u64)x0 > lo ? 1 : 0);  // (d == 0: lo is in D, the bytes go in behind it unless lo == x0)
+        const u64 ta = minus ? t.L - qa - dc : qa, tb = ta + dc;
+        o.q = ta;
+        if (ta < p || (del ? tb : ta) > p + 3 * C) {
+            o.cls = kPartialCodon;
+            return o;
+        }
+        const u64 c = (ta - p) / 3;
+        const uint32_t k = (uint32_t)((ta - p) % 3);
+        o.c = c, o.k = (uint8_t)k;
+        if (p == 0 && (del ? ta < 3 : (ta == 1 || ta == 2))) {  // (C >= 1: ta + dc <= 3C with dc > 0, or 1 <= ta <= 3C)
+            const u64 a0 = cds_at(r, t, 0), a1 = cds_at(r, t, 1), a2 = cds_at(r, t, 2);
+            const uint8_t g0 = bases[a0], g1 = bases[a1], g2 = bases[a2];
+            if ((minus ? seq::translate(seq::complement(g0), seq::complement(g1), seq::complement(g2)) : seq::translate(g0, g1, g2)) == 'M') {
+                o.cls = kStartLost;
+                return o;
+            }
+        }
+        if (m % 3 != (uint32_t)(dc % 3)) {
+            o.cls = kFrameshift;
+            return o;
+        }
+        // 3d: the reference window's codons against the alternate window's; only what decides the class is kept
+        const u64 n_ref = (k + dc + 2) / 3, w0 = p + 3 * c;  // the reference window: S[w0, w0 + 3 n_ref)
+        const u64 n_alt = m >= dc ? n_ref + (m - dc) / 3 : n_ref - (dc - m) / 3;
+        bool unknown = false, stop_ref = false, stop_alt = false, equal = n_ref == n_alt;
+        const u64 n_max = n_ref > n_alt ? n_ref : n_alt;
+        for (u64 j = 0; j < n_max; ++j) {
+            uint8_t aa_r = 0, aa_a = 0;
+            if (j < n_ref) {
+                const u64 a0 = cds_at(r, t, w0 + 3 * j), a1 = cds_at(r, t, w0 + 3 * j + 1), a2 = cds_at(r, t, w0 + 3 * j + 2);
+                const uint8_t g0 = bases[a0], g1 = bases[a1], g2 = bases[a2];  // three independent loads
+                aa_r = minus ? seq::translate(seq::complement(g0), seq::complement(g1), seq::complement(g2)) : seq::translate(g0, g1, g2);
+            }
+            if (j < n_alt) {
+                uint8_t b[3];
+                for (uint32_t e = 0; e < 3; ++e) {
+                    const u64 at = 3 * j + e;  // byte `at` of the alternate window: S[w0, ta) + I + S[tb, w0 + 3 n_ref)
+                    if (at < k) {
+                        const uint8_t g = bases[cds_at(r, t, w0 + at)];
+                        b[e] = minus ? seq::complement(g) : g;
+                    } else if (at < (u64)k + m) {
+                        b[e] = minus ? seq::complement(ins[m - 1 - (at - k)]) : ins[at - k];
+                    } else {
+                        const uint8_t g = bases[cds_at(r, t, tb + (at - k - m))];
+                        b[e] = minus ? seq::complement(g) : g;
+                    }
+                }
+                aa_a = seq::translate(b[0], b[1], b[2]);
+            }
+            unknown = unknown || aa_r == 'X' || aa_a == 'X';
+            stop_ref = stop_ref || aa_r == '*';
+            stop_alt = stop_alt || aa_a == '*';
+            equal = equal && aa_r == aa_a;
+        }
+        o.cls = unknown ? kCodingUnknown
+                : equal ? (stop_ref ? kStopRetained : kSynonymous)
+                : stop_alt && !stop_ref ? kStopGained
+                : stop_ref && !stop_alt ? kStopLost
+                : m > dc ? kInframeInsertion
+                : m < dc ? kInframeDeletion
+                         : kMissense;
+        return o;
+    }
+    if (del ? e_cov > 0 : e_cov == width) {
+        // the smallest base of F' in E: lo when a row holds it, else the start of the first row behind it
+        const bool lo_in = n[2] > t.e0 && r.end[n[2] - 1] >= lo;
+        const u64 u = lo_in ? lo : (u64)r.start0[n[2]] + 1;
+        o.cls = !has_d ? kNoncodingExon : u < t.cmin ? (minus ? kUtr3 : kUtr5) : u > t.cmax ? (minus ? kUtr5 : kUtr3) : kNoncodingExon;
+        return o;
+    }
+    o.cls = kIntron;
+    return o;
+}
+
+// the trimming of --indels: the longest common prefix, case folded, then the longest common suffix of what remains
+struct Trimmed {
+    uint32_t pfx, d, m;
+};
+GFFX_HD inline Trimmed trim(const uint8_t *ref, uint32_t n_ref, const uint8_t *alt, uint32_t n_alt) {
+    uint32_t pfx = 0;
+    while (pfx < n_ref && pfx < n_alt && ((ref[pfx] ^ alt[pfx]) & 0xDFu) == 0) ++pfx;
+    uint32_t d = n_ref - pfx, m = n_alt - pfx;
+    while (d && m && ((ref[pfx + d - 1] ^ alt[pfx + m - 1]) & 0xDFu) == 0) --d, --m;
+    return Trimmed{pfx, d, m};
+}
+
 // 1 when REF, case folded, is the genome's base, case folded (REF is a letter: no other byte folds onto one)
 GFFX_HD inline uint8_t ref_match(uint8_t ref, uint8_t genome_base) { return (ref & 0xDFu) == (genome_base & 0xDFu) ? 1 : 0; }
 
+// ref_match of an interval: R' (d bytes), case folded, against the genome's bases from g on; 1 for d == 0
+GFFX_HD inline uint8_t ref_match_run(const uint8_t *ref, uint32_t d, const uint8_t *g) {
+    uint8_t ok = 1;
+    for (uint32_t i = 0; i < d; ++i) ok &= ref_match(ref[i], g[i]);
+    return ok;
+}
+
 // ---- what the build does per transcript, once: rows [f0, f2) are its own, [f0, f1) of kind 0.  Writes pmax for its rows and
-// fills t (flags and base are the caller's); returns false for a transcript that cannot be kept: a member on another sequence
+// fills t (base and the caller's bits of flags are the caller's: flags comes back as kFlagOverlap or 0); returns false for a transcript that cannot be kept: a member on another sequence
 // than the first row's, on a sequence the genome lacks, or beyond its end.  *lo0 / *hi: the span [lo0, hi).
 GFFX_HD inline bool build_transcript(const uint32_t *start0, const uint32_t *end, const uint32_t *row_seq, const u64 *pre, uint32_t *pmax, uint32_t f0, uint32_t f1,
                                      uint32_t f2, const uint32_t *seq_len, uint32_t n_seq, Transcript *t, uint32_t *lo0, uint32_t *hi) {
-    bool ok = true;
+    bool ok = true, overlap = false;
     uint32_t lo = 0xFFFFFFFFu, top = 0;
     const uint32_t sq = row_seq[f0];
     for (uint32_t part = 0; part < 2; ++part) {
         uint32_t run = 0;
         for (uint32_t j = part ? f1 : f0; j < (part ? f2 : f1); ++j) {
+            overlap = overlap || start0[j] < run;  // (run: the largest end of the rows before it; 0 for the first)
             run = end[j] > run ? end[j] : run;
             pmax[j] = run;
             lo = start0[j] < lo ? start0[j] : lo;
@@ -219,6 +436,7 @@ GFFX_HD inline bool build_transcript(const uint32_t *start0, const uint32_t *end
     t->e0 = f1 < f2 ? f1 : f0, t->e1 = f1 < f2 ? f2 : f1;
     t->cmin = f0 < f1 ? start0[f0] + 1 : 0, t->cmax = f0 < f1 ? pmax[f1 - 1] : 0;
     t->seq = sq;
+    t->flags = overlap ? kFlagOverlap : 0u;
     t->L = pre[f1] - pre[f0];
     *lo0 = lo, *hi = top;
     return ok;

@@ -5,7 +5,8 @@
 // FASTA packed on the device.  Grouping by Parent and the variants file are string work and stay here; the device gets numeric
 // member rows once (gffx_hip_effect_create) and then chunks of GFFX_EFFECT_CHUNK_ROWS allele rows through two slots, so that
 // chunk k is formatted (on -t threads) while chunk k + 1 is classified.  The class counts of --summary are summed here, from
-// the records.
+// the records.  With --indels the variants are parsed into trimmed alleles of any length, a chunk is rows of six
+// words and a byte arena (gffx_hip_effect_run_any_start), and the summary has 20 lines; without the flag nothing here changes.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -51,8 +52,22 @@ void run(const EffectArgs &args) {
 
     // the variants, on -t threads: parts cut at line starts, the first error of the lowest part wins
     std::vector<et::Allele> alleles;
-    uint64_t not_snv = 0, no_chrom = 0;
-    {
+    std::vector<et::AlleleAny> alleles_any;  // --indels: these in place of alleles
+    uint64_t not_snv = 0, no_chrom = 0, left_out[4] = {0, 0, 0, 0};
+    if (args.indels) {
+        const std::string_view text = vcf.view();
+        const size_t parts = std::max<size_t>(1, std::min<size_t>(threads, text.size() / (1u << 20) + 1));
+        std::vector<et::VcfPartAny> part(parts);
+        parallel_for(parts, parts, [&](size_t p) { part[p] = et::parse_vcf_part_any(text, et::part_begin(text, p, parts), et::part_begin(text, p + 1, parts)); });
+        uint64_t lines_before = 0, total = 0;
+        for (const et::VcfPartAny &P : part) {
+            if (P.bad_line) throw Error("variants file " + args.variants + ", line " + std::to_string(lines_before + P.bad_line) + ": " + P.bad);
+            lines_before += P.lines, total += P.alleles.size();
+            left_out[0] += P.other, left_out[1] += P.too_long, left_out[2] += P.same, left_out[3] += P.ins_at_1;
+        }
+        alleles_any.reserve(total);
+        for (et::VcfPartAny &P : part) alleles_any.insert(alleles_any.end(), P.alleles.begin(), P.alleles.end());
+    } else {
         const std::string_view text = vcf.view();
         const size_t parts = std::max<size_t>(1, std::min<size_t>(threads, text.size() / (1u << 20) + 1));
         std::vector<et::VcfPart> part(parts);
@@ -117,7 +132,7 @@ void run(const EffectArgs &args) {
     const size_t R = T.flags.size();
     const uint64_t chunk = chunk_rows_from_env();
     EffectHandle eff;
-    if (gffx_hip_effect_create(genome.get(), T.rows.size() / 5, T.rows.data(), R, T.flags.data(), std::max<uint64_t>(1, std::min<uint64_t>(chunk, alleles.size())), OutPtr(eff)) !=
+    if (gffx_hip_effect_create(genome.get(), T.rows.size() / 5, T.rows.data(), R, T.flags.data(), std::max<uint64_t>(1, std::min<uint64_t>(chunk, args.indels ? alleles_any.size() : alleles.size())), OutPtr(eff)) !=
         GFFX_OK)
         hip_fail("gffx_hip_effect_create");
     std::vector<uint8_t> dropped(std::max<size_t>(R, 1), 0);
@@ -127,6 +142,7 @@ void run(const EffectArgs &args) {
         n_unservable += dropped[r] && !(T.flags[r] & rules::kFlagDropped);
         n_kept += !dropped[r];
     }
+    if (args.indels) et::warn_left_out(left_out[0], left_out[1], left_out[2], left_out[3]);
     if (not_snv) std::fprintf(stderr, "[WARN] %llu alleles are not single-base substitutions and were left out\n", (unsigned long long)not_snv);
     if (T.orphans) std::fprintf(stderr, "[WARN] %llu features have no Parent and belong to no transcript\n", (unsigned long long)T.orphans);
     if (T.mixed) std::fprintf(stderr, "[WARN] %llu transcripts were dropped: their members lie on more than one seqid or strand\n", (unsigned long long)T.mixed);
@@ -136,8 +152,29 @@ void run(const EffectArgs &args) {
 
     // the alleles' rows; a CHROM the index does not know is left out
     std::vector<uint32_t> arows;
-    arows.reserve(3 * alleles.size());
-    {
+    std::vector<uint8_t> abytes;  // --indels: R' then A' of every row
+    arows.reserve(args.indels ? 6 * alleles_any.size() : 3 * alleles.size());
+    if (args.indels) {
+        size_t kept = 0;
+        std::string_view last;
+        uint32_t last_fa = 0;
+        bool last_known = false, have = false;
+        for (const et::AlleleAny &a : alleles_any) {
+            if (!have || a.chrom != last) {
+                const auto it = index_data.seqid_to_num.find(std::string(a.chrom));
+                last = a.chrom, have = true;
+                last_known = it != index_data.seqid_to_num.end() && it->second < fa_of_seqid.size();
+                last_fa = last_known ? fa_of_seqid[it->second] : 0;
+            }
+            if (!last_known) {
+                ++no_chrom;
+                continue;
+            }
+            et::append_row_any(arows, abytes, a, last_fa);
+            alleles_any[kept++] = a;
+        }
+        alleles_any.resize(kept);
+    } else {
         size_t kept = 0;
         std::string_view last;
         uint32_t last_fa = 0;
@@ -161,14 +198,29 @@ void run(const EffectArgs &args) {
     if (no_chrom) std::fprintf(stderr, "[WARN] %llu alleles lie on a seqid the index does not have and were left out\n", (unsigned long long)no_chrom);
 
     // the chunks: chunk k + 1 is classified while chunk k is formatted
-    const uint64_t n = alleles.size(), n_chunks = (n + chunk - 1) / chunk;
+    const uint64_t n = args.indels ? alleles_any.size() : alleles.size(), n_chunks = (n + chunk - 1) / chunk;
+    // (--indels: a chunk's bytes are those from its first row's offset to the next chunk's; the rows go with offsets into them)
+    const auto row_off = [&](uint64_t i) { return i < n ? (static_cast<uint64_t>(arows[6 * i + 4]) | static_cast<uint64_t>(arows[6 * i + 5]) << 32) : static_cast<uint64_t>(abytes.size()); };
+    std::vector<uint32_t> chunk_rows[2];
     Output out(args.common.output);
     std::string buf = et::kHeader;
     et::Summary sum;
+    et::SummaryAll sum_all;
     uint64_t n_pairs = 0;
     double format_ms = 0;
     const auto start = [&](uint64_t k) {
         const uint64_t lo = k * chunk, m = std::min(chunk, n - lo);
+        if (args.indels) {
+            const uint64_t b0 = row_off(lo), b1 = row_off(lo + m);
+            std::vector<uint32_t> &rows6 = chunk_rows[k & 1];
+            rows6.assign(arows.begin() + 6 * lo, arows.begin() + 6 * (lo + m));
+            for (uint64_t i = 0; i < m; ++i) {
+                const uint64_t rel = row_off(lo + i) - b0;
+                rows6[6 * i + 4] = static_cast<uint32_t>(rel), rows6[6 * i + 5] = static_cast<uint32_t>(rel >> 32);
+            }
+            if (gffx_hip_effect_run_any_start(eff.get(), static_cast<int>(k & 1), rows6.data(), m, abytes.data() + b0, b1 - b0) != GFFX_OK) hip_fail("gffx_hip_effect_run_any_start");
+            return;
+        }
         if (gffx_hip_effect_run_start(eff.get(), static_cast<int>(k & 1), arows.data() + 3 * lo, m) != GFFX_OK) hip_fail("gffx_hip_effect_run_start");
     };
     if (n_chunks) start(0);
@@ -185,9 +237,12 @@ void run(const EffectArgs &args) {
         const size_t parts = std::max<size_t>(1, std::min<size_t>(threads, m / 4096 + 1));
         std::vector<std::string> text(parts);
         std::vector<et::Summary> part_sum(parts);
+        std::vector<et::SummaryAll> part_sum_all(args.indels ? parts : 0);
         parallel_for(parts, parts, [&](size_t p) {
-            for (uint64_t i = m * p / parts; i < m * (p + 1) / parts; ++i)
-                et::format_allele(text[p], part_sum[p], alleles[lo + i], records + off[i], off[i + 1] - off[i], rm[i], T.names, T.strand);
+            for (uint64_t i = m * p / parts; i < m * (p + 1) / parts; ++i) {
+                if (args.indels) et::format_allele_any(text[p], part_sum_all[p], alleles_any[lo + i], records + off[i], off[i + 1] - off[i], rm[i], T.names, T.strand);
+                else et::format_allele(text[p], part_sum[p], alleles[lo + i], records + off[i], off[i + 1] - off[i], rm[i], T.names, T.strand);
+            }
         });
         for (size_t p = 0; p < parts; ++p) {
             if (buf.size() + text[p].size() >= (1u << 20)) {
@@ -197,6 +252,7 @@ void run(const EffectArgs &args) {
             if (text[p].size() >= (1u << 20)) out.write(text[p]);
             else buf += text[p];
             for (uint32_t c = 0; c < rules::kClasses; ++c) sum.alleles[c] += part_sum[p].alleles[c], sum.pairs[c] += part_sum[p].pairs[c];
+            if (args.indels) sum_all.add(part_sum_all[p]);
         }
         n_pairs += pairs;
         format_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -205,7 +261,7 @@ void run(const EffectArgs &args) {
     out.close();
     if (args.summary) {
         Output s(args.summary);
-        s.write(sum.text());
+        s.write(args.indels ? sum_all.text() : sum.text());
         s.close();
     }
     double build_ms = 0, pairs_ms = 0, classify_ms = 0;
@@ -219,6 +275,12 @@ void run(const EffectArgs &args) {
     g_run_stats.count("transcripts_kept", static_cast<double>(n_kept));
     g_run_stats.count("alleles", static_cast<double>(n));
     g_run_stats.count("alleles_not_snv", static_cast<double>(not_snv));
+    if (args.indels) {
+        g_run_stats.count("alleles_other_bytes", static_cast<double>(left_out[0]));
+        g_run_stats.count("alleles_too_long", static_cast<double>(left_out[1]));
+        g_run_stats.count("alleles_equal_to_ref", static_cast<double>(left_out[2]));
+        g_run_stats.count("alleles_insertion_at_1", static_cast<double>(left_out[3]));
+    }
     g_run_stats.count("alleles_no_seqid", static_cast<double>(no_chrom));
     g_run_stats.count("pairs", static_cast<double>(n_pairs));
     g_run_stats.count("chunks", static_cast<double>(n_chunks));

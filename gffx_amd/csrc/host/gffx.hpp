@@ -581,6 +581,7 @@ struct EffectArgs {
     std::string cds_type = "CDS";        // --cds-type: the lines that give a transcript's coding segments
     std::string exon_type = "exon";      // --exon-type: the lines that give its exons
     std::optional<std::string> summary;  // --summary: class, alleles, pairs per class
+    bool indels = false;                 // --indels: insertions, deletions and multi-base substitutions as well
     int device = 0;                      // --device
 };
 

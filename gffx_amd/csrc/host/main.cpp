@@ -298,6 +298,38 @@ const char *kEffectUsage =
     "  member on a seqid the FASTA file lacks, beyond its sequence's end, or on another seqid or strand than its first member is\n"
     "  left out (warnings say how many).\n";
 
+// what `gffx effect` prints for help and usage errors once --indels is among its arguments (without it: kEffectUsage, unchanged)
+const char *kEffectIndelsUsage =
+    "Usage: gffx effect --indels [OPTIONS] --input <FILE> --fasta <FILE> --variants <FILE>\n\nOptions:\n"
+    "  -i, --input <FILE>       Input GFF file path\n"
+    "  -f, --fasta <FILE>       The genome as plain FASTA (lines of any lengths; a compressed file is refused)\n"
+    "  -V, --variants <FILE>    The variants as plain text, CHROM POS ID REF ALT per line as in VCF ('#' lines are skipped; a\n"
+    "                           compressed file is refused).  ALT is split at ','\n"
+    "      --indels             Take insertions, deletions and multi-base substitutions as well: REF and an ALT piece of 1 to\n"
+    "                           65535 bases of ACGTN each\n"
+    "  -o, --output <FILE>      Output file (stdout if not provided)\n"
+    "      --cds-type <TYPE>    Feature type (column 3) whose lines give a transcript's coding segments [default: CDS]\n"
+    "      --exon-type <TYPE>   Feature type whose lines give its exons [default: exon]\n"
+    "      --summary <FILE>     Write 'class<TAB>alleles<TAB>pairs' for every class\n"
+    "  -t, --threads <NUM>      Number of threads for parallel processing [default: 12]\n"
+    "  -v, --verbose            Enable verbose output\n"
+    "      --device <N>         HIP device to run on [default: 0]\n"
+    "      --stats-json <FILE>  Write the run's stage timers and counts as one JSON object\n\n"
+    "Output: one TAB-separated line per allele and transcript whose span it meets, the alleles in file order, an allele's\n"
+    "  transcripts in order of first appearance: chrom pos ref alt transcript strand class cds_pos codons aa_pos aa ref_match;\n"
+    "  pos, ref and alt are the file's own.  REF and the piece are trimmed (case folded; the common prefix first, then the common\n"
+    "  suffix); the genome is not consulted, so nothing is left-aligned.  One base against one base is a single-base substitution\n"
+    "  and gets the lines of the command without --indels.  Every other allele covers its reference bases, an insertion the two\n"
+    "  bases around it, and takes the first of: unclassified_model (rows of the transcript overlap), transcript_ablation (the\n"
+    "  whole span is deleted), splice_donor or splice_acceptor (a deletion meets the two bases next to an exon, an insertion lies\n"
+    "  inside them), then in coding sequence partial_codon, start_lost, frameshift, coding_unknown, stop_retained, synonymous,\n"
+    "  stop_gained, stop_lost, inframe_insertion, inframe_deletion or missense, then noncoding_exon, 5_prime_UTR or 3_prime_UTR,\n"
+    "  then intron; intergenic without a transcript.  For these alleles cds_pos and aa_pos are where the change begins in the\n"
+    "  transcribed coding sequence; codons and aa print '.': the residues an in-frame change replaces are not reported.\n"
+    "  ref_match says whether the trimmed REF is the genome's.  Left out, each kind under a warning of its own: '*', '.', symbolic\n"
+    "  and breakend pieces and any other byte; a REF or piece longer than 65535 bytes; a piece equal to REF; an insertion in front\n"
+    "  of a sequence's first base.  --summary has 20 lines.\n";
+
 const char *kIndexUsage =
     "Usage: gffx index [OPTIONS] --input <INPUT>\n\nOptions:\n"
     "  -i, --input <INPUT>\n"
@@ -600,6 +632,7 @@ void run_effect_cli(const Opts &o) {
     if (a.cds_type.empty() || a.exon_type.empty()) throw UsageError("'--cds-type <TYPE>' and '--exon-type <TYPE>' take a type name");
     if (a.cds_type == a.exon_type) throw UsageError("the argument '--cds-type <TYPE>' names the type of '--exon-type <TYPE>': '" + a.cds_type + "'");
     a.summary = o.opt("summary");
+    a.indels = o.has("indels");
     a.device = o.device();
     o.stats_json();
     commands::effect::run(a);
@@ -666,7 +699,7 @@ const std::vector<Command> &commands_table() {
           {'w', "width", true}, {'t', "threads", true}, {'v', "verbose", false}, {0, "device", true}, {0, "stats-json", true}}},
         {"effect", kEffectUsage, run_effect_cli,
          {{'i', "input", true}, {'f', "fasta", true}, {'V', "variants", true}, {'o', "output", true}, {0, "cds-type", true}, {0, "exon-type", true},
-          {0, "summary", true}, {'t', "threads", true}, {'v', "verbose", false}, {0, "device", true}, {0, "stats-json", true}}},
+          {0, "summary", true}, {0, "indels", false}, {'t', "threads", true}, {'v', "verbose", false}, {0, "device", true}, {0, "stats-json", true}}},
     };
     return table;
 }
@@ -685,6 +718,9 @@ int cli_main(int argc, char **argv) {
         for (const Command &c : commands_table()) {
             if (cmd != c.name) continue;
             usage = c.usage;
+            if (cmd == "effect")
+                for (int k = 2; k < argc && std::strcmp(argv[k], "--") != 0; ++k)
+                    if (std::strcmp(argv[k], "--indels") == 0) usage = kEffectIndelsUsage;
             std::vector<OptSpec> specs = c.specs;
             specs.push_back({'h', "help", false});
             const Opts o(argc, argv, specs);

@@ -1852,10 +1852,34 @@ class SeqPlan:
 # ---- `gffx effect`: single-base substitutions against transcripts (device/effect.hip, the rules: effect_core.hpp) --------------
 EFFECT_CLASSES = ("partial_codon", "coding_unknown", "stop_retained", "synonymous", "stop_gained", "stop_lost", "start_lost", "missense",
                   "noncoding_exon", "5_prime_UTR", "3_prime_UTR", "intron", "splice_donor", "splice_acceptor", "intergenic")
+# what run_any may give as well (`gffx effect --indels`): the 15 above keep their numbers
+EFFECT_CLASSES_ALL = EFFECT_CLASSES + ("frameshift", "inframe_insertion", "inframe_deletion", "transcript_ablation", "unclassified_model")
 EFFECT_CDS, EFFECT_EXON = 0, 1  # a member row's kind
 EFFECT_NO_SEQ = 0xFFFFFFFF      # an allele's sequence number when the FASTA lacks its sequence
 EFFECT_RECORD = np.dtype([("q", "<u8"), ("c", "<u8"), ("transcript", "<u4"), ("cls", "u1"), ("k", "u1"), ("ref_match", "u1"), ("aa_ref", "u1"),
                           ("aa_alt", "u1"), ("codon_ref", "u1", (3,)), ("codon_alt", "u1", (3,)), ("pad", "u1")])
+
+
+def effect_trim(pos: int, ref: bytes, alt: bytes):
+    """The trimming of `gffx effect --indels`: (x0, d, m, R', A').  Case folded, the longest common prefix goes first, then the
+    longest common suffix of what remains; x0 = pos + the prefix.  The genome is not consulted: nothing is left-aligned."""
+    r, a = bytes(ref).upper(), bytes(alt).upper()
+    pfx = 0
+    while pfx < len(r) and pfx < len(a) and r[pfx] == a[pfx]:
+        pfx += 1
+    d, m = len(r) - pfx, len(a) - pfx
+    while d and m and r[pfx + d - 1] == a[pfx + m - 1]:
+        d, m = d - 1, m - 1
+    return int(pos) + pfx, d, m, bytes(ref)[pfx:pfx + d], bytes(alt)[pfx:pfx + m]
+
+
+def effect_rows_any(alleles):
+    """((n, 6) u32 rows, the arena) of run_any for alleles (sequence number, x0, R', A')."""
+    rows, arena = [], bytearray()
+    for q, x0, ref, ins in alleles:
+        rows.append((q, x0, len(ref), len(ins), len(arena) & 0xFFFFFFFF, len(arena) >> 32))
+        arena += bytes(ref) + bytes(ins)
+    return np.array(rows, dtype=np.uint32).reshape(-1, 6), bytes(arena)
 
 
 class Effect:
@@ -1928,6 +1952,47 @@ class Effect:
         return (np.concatenate(offs), np.concatenate(rms) if rms else np.zeros(0, dtype=np.uint8),
                 np.concatenate(recs) if recs else np.zeros(0, dtype=EFFECT_RECORD))
 
+    def start_any(self, slot: int, rows, arena) -> int:
+        """A chunk of --indels rows: (n, 6) u32 (sequence number, x0, d, m, offset low, offset high) into ``arena`` (bytes),
+        where a row's R' then A' stand."""
+        a = _u32(rows).reshape(-1, 6)
+        b = np.frombuffer(bytes(arena), dtype=np.uint8) if len(arena) else np.zeros(1, dtype=np.uint8)
+        check(lib().gffx_hip_effect_run_any_start(self._h, int(slot), _p(a), a.shape[0], b.ctypes.data_as(_ffi.u8p), len(arena)))
+        return int(a.shape[0])
+
+    def run_any(self, rows, arena, slot: int = 0):
+        return self.wait(slot, self.start_any(slot, rows, arena))
+
+    def run_any_chunked(self, rows, arena, chunk_rows: int):
+        """As run_chunked; every chunk is handed the bytes from its first row's offset to its last row's end (the rows' offsets
+        ascend), its offsets rebased."""
+        a = _u32(rows).reshape(-1, 6).copy()
+        off = a[:, 4].astype(np.uint64) | a[:, 5].astype(np.uint64) << np.uint64(32)
+        end = off + a[:, 2].astype(np.uint64) + a[:, 3].astype(np.uint64)
+        starts = list(range(0, a.shape[0], chunk_rows))
+
+        def begin(k):
+            lo, hi = starts[k], min(starts[k] + chunk_rows, a.shape[0])
+            b0, b1 = int(off[lo]), int(end[lo:hi].max())
+            part = a[lo:hi].copy()
+            rel = off[lo:hi] - np.uint64(b0)
+            part[:, 4], part[:, 5] = (rel & np.uint64(0xFFFFFFFF)).astype(np.uint32), (rel >> np.uint64(32)).astype(np.uint32)
+            self.start_any(k & 1, part, arena[b0:b1])
+            return hi - lo
+
+        offs, rms, recs, base = [np.zeros(1, dtype=np.uint64)], [], [], 0
+        n = begin(0) if starts else 0
+        for k in range(len(starts)):
+            n_next = begin(k + 1) if k + 1 < len(starts) else 0
+            o, m, r = self.wait(k & 1, n)
+            offs.append(o[1:] + np.uint64(base))
+            base += int(o[-1])
+            rms.append(m)
+            recs.append(r)
+            n = n_next
+        return (np.concatenate(offs), np.concatenate(rms) if rms else np.zeros(0, dtype=np.uint8),
+                np.concatenate(recs) if recs else np.zeros(0, dtype=EFFECT_RECORD))
+
     def stage_ms(self) -> Dict[str, float]:
         a, b, c = C.c_double(), C.c_double(), C.c_double()
         check(lib().gffx_hip_effect_stage_ms(self._h, C.byref(a), C.byref(b), C.byref(c)))
@@ -1936,4 +2001,6 @@ class Effect:
     def stats(self) -> Dict[str, int]:
         kept, grows = C.c_uint64(), C.c_uint64()
         check(lib().gffx_hip_effect_stats(self._h, C.byref(kept), C.byref(grows)))
-        return {"kept": kept.value, "grows": grows.value}
+        arena = C.c_uint64()
+        check(lib().gffx_hip_effect_arena_grows(self._h, C.byref(arena)))
+        return {"kept": kept.value, "grows": grows.value, "arena_grows": arena.value}

@@ -1053,12 +1053,24 @@ void gffx_hip_seq_destroy(gffx_hip_seq *);
  *                     the copies, enqueued; _run_wait: the slot's results in pinned host memory, valid until its next start
  *   _stage_ms         HIP-event milliseconds of the build, the pair passes and the classify kernel so far
  *   _stats            kept transcripts; how often a slot's record buffer had to grow
+ * INDELS (`gffx effect --indels`): _run_any_start takes rows of 6 words (sequence number, x0, d, m, offset low, offset high) and
+ * a byte arena; a row's d reference bases R' (from x0 on, 1-based) and its m alternate bytes A' stand at arena[offset,
+ * offset + d + m), trimmed by the caller so that they share no first and no last base.  Its footprint is [x0, x0 + d - 1], for
+ * d = 0 the flanking bases [x0 - 1, x0]; it pairs with every kept transcript whose span meets the footprint, provided the
+ * footprint lies inside the sequence.  ref_match: R', case folded, is the genome's (1 for d = 0).  A row with d = m = 1 gives
+ * the record of _run_start; every other row one of the classes 0 .. 19 with q, c and k where the coding rule was reached and
+ * the codon and amino-acid bytes 0.  A bad sequence number, x0 = 0, d = m = 0, d or m above 65535 or d = 0 with x0 = 1 fails
+ * with GFFX_E_CHR_RANGE; a row whose bytes leave the arena with GFFX_E_INVALID; both stick.  _run_wait serves both starts.
+ *   _arena_grows      how often a slot's pinned arena staging had to grow
  * The genome must outlive the object. */
 enum gffx_effect_class {
     GFFX_EFFECT_PARTIAL_CODON = 0, GFFX_EFFECT_CODING_UNKNOWN = 1, GFFX_EFFECT_STOP_RETAINED = 2, GFFX_EFFECT_SYNONYMOUS = 3,
     GFFX_EFFECT_STOP_GAINED = 4, GFFX_EFFECT_STOP_LOST = 5, GFFX_EFFECT_START_LOST = 6, GFFX_EFFECT_MISSENSE = 7,
     GFFX_EFFECT_NONCODING_EXON = 8, GFFX_EFFECT_5_PRIME_UTR = 9, GFFX_EFFECT_3_PRIME_UTR = 10, GFFX_EFFECT_INTRON = 11,
-    GFFX_EFFECT_SPLICE_DONOR = 12, GFFX_EFFECT_SPLICE_ACCEPTOR = 13, GFFX_EFFECT_INTERGENIC = 14
+    GFFX_EFFECT_SPLICE_DONOR = 12, GFFX_EFFECT_SPLICE_ACCEPTOR = 13, GFFX_EFFECT_INTERGENIC = 14,
+    /* _run_any_start only */
+    GFFX_EFFECT_FRAMESHIFT = 15, GFFX_EFFECT_INFRAME_INSERTION = 16, GFFX_EFFECT_INFRAME_DELETION = 17,
+    GFFX_EFFECT_TRANSCRIPT_ABLATION = 18, GFFX_EFFECT_UNCLASSIFIED_MODEL = 19
 };
 typedef struct gffx_hip_effect gffx_hip_effect;
 uint32_t gffx_hip_effect_record_bytes(void);
@@ -1066,10 +1078,13 @@ int gffx_hip_effect_create(const gffx_hip_genome *, uint64_t n_rows, const uint3
                            const uint8_t *tr_flags, uint64_t max_alleles, gffx_hip_effect **out);
 int gffx_hip_effect_copy_transcripts(const gffx_hip_effect *, uint8_t *dropped /* n_transcripts */, uint32_t *span /* 2 per transcript */);
 int gffx_hip_effect_run_start(gffx_hip_effect *, int slot, const uint32_t *alleles /* 3 per row */, uint64_t n);
+int gffx_hip_effect_run_any_start(gffx_hip_effect *, int slot, const uint32_t *rows /* 6 per row */, uint64_t n, const uint8_t *arena,
+                                  uint64_t arena_bytes);
 int gffx_hip_effect_run_wait(gffx_hip_effect *, int slot, const uint64_t **offsets, const uint8_t **ref_match, const uint8_t **records,
                              uint64_t *n_pairs);
 int gffx_hip_effect_stage_ms(const gffx_hip_effect *, double *build_ms, double *pairs_ms, double *classify_ms);
 int gffx_hip_effect_stats(const gffx_hip_effect *, uint64_t *kept, uint64_t *grows);
+int gffx_hip_effect_arena_grows(const gffx_hip_effect *, uint64_t *grows);
 void gffx_hip_effect_destroy(gffx_hip_effect *);
 
 #ifdef __cplusplus

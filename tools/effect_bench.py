@@ -15,6 +15,10 @@ and beside them one host core: bin/effect_host_baseline (`make effect_host_basel
 sanitizers, the same rules through device/effect_core.hpp), likewise one warm-up run and --reps timed ones: its pairs stage (span
 lookup + rules: what the pair passes and k_effect_pairs do), its formatting and its wall clock; its output must be the command's,
 byte for byte.
+--indels (profiles/effect_indels.txt) measures `gffx effect --indels` instead: the `uniform` file with every tenth
+allele turned into an indel (`mixed`: a deletion of the genome's own bases or an insertion, by turns, of 1 to 30 bases drawn from
+the fixed seed), and the SNV-only `uniform` file run with and without the flag, so that k_effect_pairs_any stands beside
+k_effect_pairs on the same pairs; the one-core baseline runs `--run --indels` on the mixed file.
 One JSON object on stdout; --profile FILE writes the lines of profiles/effect.txt (the text, then the JSON).  The files are kept
 in --dir between runs.
 Usage: python tools/effect_bench.py [--genes 63000] [--genome-div 8] [--snvs 5000000] [--seed 5] [--reps 5] [--dir DIR] [--skip-host]
@@ -52,6 +56,84 @@ def write_vcf(path, chrom_names, chrom_idx, pos, seed):
         for at in range(0, len(pos), step):
             f.write("".join("%s\t%d\t.\t%s\t%s\n" % (chrom_names[c], p, bases[r], bases[a]) for c, p, r, a in
                             zip(chrom_idx[at:at + step].tolist(), pos[at:at + step].tolist(), ref[at:at + step].tolist(), alt[at:at + step].tolist())))
+
+
+def write_mixed_vcf(path, snv_vcf, fa, seed):
+    """The lines of snv_vcf, every tenth one an indel of 1 to 30 bases at the same POS: by turns a deletion of the genome's own
+    bases behind POS (REF = the anchor and the bases, ALT = the anchor) and an insertion of random bases behind the anchor."""
+    seqs, name = {}, None
+    with open(fa, "rb") as f:
+        for line in f:
+            if line.startswith(b">"):
+                name = line[1:].split()[0].decode()
+                seqs[name] = []
+            else:
+                seqs[name].append(line.rstrip(b"\r\n"))
+    seqs = {k: b"".join(v) for k, v in seqs.items()}
+    rng = np.random.RandomState(seed)
+    n = 0
+    with open(snv_vcf) as src, open(path, "w") as out:
+        for line in src:
+            if line.startswith("#"):
+                out.write(line)
+                continue
+            n += 1
+            if n % 10:
+                out.write(line)
+                continue
+            chrom, pos = line.split("\t", 2)[:2]
+            pos, ln, seq = int(pos), int(rng.randint(1, 31)), seqs[chrom]
+            anchor = seq[pos - 1:pos].decode().upper()
+            if (n // 10) % 2 and pos + ln <= len(seq):
+                out.write("%s\t%d\t.\t%s\t%s\n" % (chrom, pos, anchor + seq[pos:pos + ln].decode().upper(), anchor))
+            else:
+                out.write("%s\t%d\t.\t%s\t%s\n" % (chrom, pos, anchor, anchor + "".join("ACGT"[b] for b in rng.randint(0, 4, ln))))
+
+
+def indel_runs(a, gffx, tool, gff, fa, vcfs):
+    """The --indels measurements: {name: {wall_s, build_ms, pairs_ms, classify_ms, alleles, pairs}} for the mixed file with the
+    flag, the SNV-only file with it and without it, and the one-core baseline on the mixed file."""
+    out, stats = os.path.join(a.dir, "out.tsv"), os.path.join(a.dir, "stats.json")
+    mixed = os.path.join(a.dir, "mixed_%d_%d_%d_%d.vcf" % (a.snvs, a.genes, a.genome_div, a.seed))
+    if not os.path.exists(mixed):
+        write_mixed_vcf(mixed, vcfs["uniform"], fa, a.seed + 4)
+    res = {}
+    configs = [("mixed --indels", gffx, mixed, ["--indels"]), ("snvs --indels", gffx, vcfs["uniform"], ["--indels"]), ("snvs", gffx, vcfs["uniform"], [])]
+    if a.other_gffx:  # (the flagless command of another build, such as the commit before --indels, on the same file)
+        configs.append(("snvs, other build", a.other_gffx, vcfs["uniform"], []))
+    for name, binary, vcf, flag in configs:
+        runs = []
+        for k in range(a.reps + 1):
+            t0 = time.time()
+            r = subprocess.run([binary, "effect", "-i", gff, "-f", fa, "-V", vcf, "-o", out, "--stats-json", stats] + flag, capture_output=True)
+            wall = time.time() - t0
+            if r.returncode != 0:
+                sys.stderr.write(r.stderr.decode(errors="replace"))
+                sys.exit(r.returncode)
+            flat = json.load(open(stats))
+            flat = dict(flat.get("counts", flat), wall_s=wall)
+            if k:
+                runs.append(flat)
+        res[name] = {"alleles": runs[0]["alleles"], "pairs": runs[0]["pairs"], "output_bytes": os.path.getsize(out), "wall_s": spread([x["wall_s"] for x in runs]),
+                     "build_ms": spread([x["build_kernels_ms"] for x in runs]), "pairs_ms": spread([x["pair_kernels_ms"] for x in runs]),
+                     "classify_ms": spread([x["classify_kernels_ms"] for x in runs])}
+        sys.stderr.write("%s: %s\n" % (name, json.dumps(res[name])))
+    if a.other_gffx:
+        res["flagless_wall_over_other_build"] = round(res["snvs"]["wall_s"]["median"] / res["snvs, other build"]["wall_s"]["median"], 3)
+    res["classify_any_over_classify"] = round(res["snvs --indels"]["classify_ms"]["median"] / res["snvs"]["classify_ms"]["median"], 3)
+    if not a.skip_host:
+        host_out, takes = os.path.join(a.dir, "host.tsv"), []
+        for k in range(a.reps + 1):
+            t0 = time.time()
+            r = subprocess.run([tool, "--run", "--indels", gff, fa, mixed, "CDS", "exon", host_out, "-"], capture_output=True, check=True)
+            words = r.stderr.split(b"\n")[-2].split()
+            t = dict(zip(words[0::2], (float(x) for x in words[1::2])))
+            if k:
+                takes.append({"pairs_ms": t[b"pairs_ms"], "format_ms": t[b"format_ms"], "wall_s": time.time() - t0})
+        subprocess.check_call([gffx, "effect", "--indels", "-i", gff, "-f", fa, "-V", mixed, "-o", out])
+        res["one_host_core mixed --indels"] = dict({k: spread([x[k] for x in takes]) for k in takes[0]}, same_bytes=subprocess.run(["cmp", "-s", out, host_out]).returncode == 0)
+        os.remove(host_out)
+    return res
 
 
 def cds_lines(gff):
@@ -113,6 +195,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--dir", default=None, help="directory for the files (default: a temporary one, removed)")
     ap.add_argument("--skip-host", action="store_true")
+    ap.add_argument("--other-gffx", default=None, help="with --indels: another build's gffx binary, run without the flag on the SNV-only file beside this one's")
+    ap.add_argument("--indels", action="store_true", help="measure --indels on the mixed file and beside the flagless command (profiles/effect_indels.txt)")
     ap.add_argument("--profile", default=None, help="write the measurements as text, then the JSON, to this file")
     a = ap.parse_args()
     if a.dir is None:
@@ -156,6 +240,21 @@ def main():
             g = rng.randint(0, int(edges[-1]), a.snvs).astype(np.int64)
             k = np.searchsorted(edges, g, side="right") - 1
             write_vcf(vcfs[mode], names, c[k], lo[k] + (g - edges[k]), a.seed + 3)
+    if a.indels:
+        tool = os.path.join(ROOT, "gffx_amd", "bin", "effect_host_baseline")
+        if not a.skip_host:
+            subprocess.check_call(["make", "-C", os.path.join(ROOT, "gffx_amd", "csrc"), "effect_host_baseline"], stdout=subprocess.DEVNULL)
+        res = {"genes": a.genes, "genome_bases": sum(l for _, l in chroms), "snvs": a.snvs, "reps": a.reps, "runs": indel_runs(a, gffx, tool, gff, fa, vcfs)}
+        print(json.dumps(res))
+        if a.profile:
+            with open(a.profile, "w") as f:
+                f.write("gffx effect --indels: tools/effect_bench.py --indels --genes %d --genome-div %d --snvs %d --reps %d; one MI355X; one warm-up run, then the timed "
+                        "runs, median [min .. max]; kernel times are HIP events summed over the run\n" % (a.genes, a.genome_div, a.snvs, a.reps))
+                f.write("mixed: the uniform SNV file with every tenth allele a deletion or an insertion of 1 to 30 bases; snvs: that file as it is, with the flag (k_effect_pairs_any) and without it (k_effect_pairs); other build: the flagless command of the build given with --other-gffx (the commit before --indels) on the same file; classify_ms is the classify kernel, pairs_ms the engine's pair passes\n")
+                for name, m in res["runs"].items():
+                    f.write("%s: %s\n" % (name, json.dumps(m)))
+                f.write(json.dumps(res) + "\n")
+        return
     res = {"genes": a.genes, "genome_bases": sum(l for _, l in chroms), "fasta_bytes": os.path.getsize(fa), "gff_bytes": os.path.getsize(gff), "snvs": a.snvs,
            "reps": a.reps, "modes": {}}
     out, stats, summary = os.path.join(a.dir, "out.tsv"), os.path.join(a.dir, "stats.json"), os.path.join(a.dir, "summary.tsv")

@@ -16,6 +16,13 @@
 //                                     "error LINE WHAT"
 //   effect_check --run GFF FASTA VCF CDS_TYPE EXON_TYPE OUT SUMMARY   the command on one core ("-": no summary); warnings and the
 //                                     stage times to stderr
+//   effect_check --run --indels GFF FASTA VCF CDS_TYPE EXON_TYPE OUT SUMMARY   the command with --indels
+//   effect_check --all-classes        the 20 class names of --indels in summary order
+//   effect_check --indel-rules FILE   as --rules, with alleles "I SEQ X0 REF ALT": trimmed already, "-" an empty string; per pair
+//                                     "p TRANSCRIPT CLASS Q C K"; an allele of one base each way prints the line of --rules
+//   effect_check --trim POS REF ALT   "X0 D M" of the trimming
+//   effect_check --vcf-indels FILE PARTS   the variants file as --indels reads it: "allele CHROM POS REF ALT X0 D M" lines, then
+//                                     "left_out OTHER TOO_LONG SAME INS_AT_1", or "error LINE WHAT"
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -101,7 +108,7 @@ struct Host {
             if (f2 > f0) {
                 const bool ok = ef::build_transcript(start0.get(), end.get(), row_seq.get(), pre.get(), pmax.get(), f0, f1, f2, seq_len.get(), n_seq, &o, &lo0[t], &hi[t]);
                 const bool keep = ok && !(flags[t] & ef::kFlagDropped);
-                o.flags = flags[t], o.base = keep ? seq_off[o.seq] : 0;
+                o.flags = flags[t] | (o.flags & ef::kFlagOverlap), o.base = keep ? seq_off[o.seq] : 0;
                 dropped[t] = keep ? 0 : 1;
                 if (keep) by_lo[o.seq].push_back(t);
             }
@@ -125,6 +132,30 @@ struct Host {
             if (hi[L[k]] >= x) out.push_back(L[k]);
         }
         std::sort(out.begin(), out.end());
+    }
+    // the kept transcripts of sequence s whose span meets [lo, hi], by number
+    void hits_range(uint32_t s, u64 lo, u64 hi, std::vector<uint32_t> &out) const {
+        out.clear();
+        if (s >= n_seq || lo < 1 || hi > seq_len[s]) return;
+        const std::vector<uint32_t> &L = by_lo[s];
+        size_t k = std::partition_point(L.begin(), L.end(), [&](uint32_t t) { return lo0[t] < hi; }) - L.begin();
+        while (k > 0 && run_hi[s][k - 1] >= lo) {
+            --k;
+            if (this->hi[L[k]] >= lo) out.push_back(L[k]);
+        }
+        std::sort(out.begin(), out.end());
+    }
+    ef::Record classify_any(uint32_t t, uint32_t x0, uint32_t d, uint32_t m, const uint8_t *ins, uint8_t rm) const {
+        const ef::Rows rows{start0.get(), end.get(), pre.get(), pmax.get()};
+        ef::Record r = d == 1 && m == 1 ? ef::classify(rows, tr[t], arena.get(), x0, ins[0]) : ef::classify_any(rows, tr[t], arena.get(), x0, d, m, ins);
+        r.transcript = t, r.ref_match = rm;
+        return r;
+    }
+    uint8_t ref_match_run(uint32_t s, u64 lo, u64 hi, u64 x0, const uint8_t *ref, uint32_t d) const {
+        if (s >= n_seq || lo < 1 || hi > seq_len[s]) return 0;
+        if (d == 0) return 1;
+        if (seq_off[s] + x0 - 1 + d > seq_off[s + 1]) return 0;  // (bases that --indel-rules was not given)
+        return ef::ref_match_run(ref, d, arena.get() + seq_off[s] + (x0 - 1));
     }
     ef::Record classify(uint32_t t, uint32_t x, uint8_t alt, uint8_t rm) const {
         const ef::Rows rows{start0.get(), end.get(), pre.get(), pmax.get()};
@@ -193,6 +224,97 @@ static int rules(const char *path) {
     return 0;
 }
 
+static void print_pair(const ef::Record &r, bool snv) {
+    if (snv && ef::is_coding(r.cls))
+        std::printf("p %u %s %llu %llu %u %c%c%c %c%c%c %c %c\n", r.transcript, ef::class_name(r.cls), r.q, r.c, (unsigned)r.k, r.codon_ref[0], r.codon_ref[1], r.codon_ref[2],
+                    r.codon_alt[0], r.codon_alt[1], r.codon_alt[2], r.aa_ref, r.aa_alt);
+    else if (snv)
+        std::printf("p %u %s %llu %llu %u - - - -\n", r.transcript, ef::class_name(r.cls), r.q, r.c, (unsigned)r.k);
+    else
+        std::printf("p %u %s %llu %llu %u\n", r.transcript, ef::class_name(r.cls), r.q, r.c, (unsigned)r.k);
+}
+
+static int indel_rules(const char *path) {
+    std::istringstream in(slurp(path));
+    std::vector<uint32_t> rows;
+    std::vector<uint8_t> flags;
+    std::vector<u64> len;
+    std::vector<std::string> bases;
+    struct A {
+        uint32_t s, x0;
+        std::string ref, alt;
+    };
+    std::vector<A> alleles;
+    std::string kind;
+    while (in >> kind) {
+        if (kind == "S") {
+            u64 l;
+            std::string b;
+            in >> l >> b;
+            len.push_back(l), bases.push_back(b == "-" ? "" : b);
+        } else if (kind == "T") {
+            unsigned f;
+            in >> f;
+            flags.push_back((uint8_t)f);
+        } else if (kind == "R") {
+            uint32_t r[5];
+            in >> r[0] >> r[1] >> r[2] >> r[3] >> r[4];
+            rows.insert(rows.end(), r, r + 5);
+        } else if (kind == "I") {
+            A a;
+            in >> a.s >> a.x0 >> a.ref >> a.alt;
+            if (a.ref == "-") a.ref.clear();
+            if (a.alt == "-") a.alt.clear();
+            alleles.push_back(a);
+        } else {
+            return 2;
+        }
+    }
+    Host H;
+    H.build(rows, flags, len, bases);
+    for (uint32_t t = 0; t < H.n_tr; ++t) std::printf("t %u %u %u\n", (unsigned)H.dropped[t], H.lo0[t] + 1, H.hi[t]);
+    std::vector<uint32_t> hit;
+    for (const A &a : alleles) {
+        const uint32_t d = (uint32_t)a.ref.size(), m = (uint32_t)a.alt.size();
+        const u64 lo = d ? (u64)a.x0 : (u64)a.x0 - 1, hi = d ? (u64)a.x0 + d - 1 : (u64)a.x0;
+        // (exact-size copies: a read past R' or A' is the sanitizer's)
+        const std::unique_ptr<uint8_t[]> ref = exact(std::vector<uint8_t>(a.ref.begin(), a.ref.end())), alt = exact(std::vector<uint8_t>(a.alt.begin(), a.alt.end()));
+        H.hits_range(a.s, lo, hi, hit);
+        const uint8_t rm = H.ref_match_run(a.s, lo, hi, a.x0, ref.get(), d);
+        std::printf("a %zu %u\n", hit.size(), (unsigned)rm);
+        for (uint32_t t : hit) print_pair(H.classify_any(t, a.x0, d, m, alt.get(), rm), d == 1 && m == 1);
+    }
+    return 0;
+}
+
+static int trim(const char *pos, const char *ref, const char *alt) {
+    const ef::Trimmed t = ef::trim(reinterpret_cast<const uint8_t *>(ref), (uint32_t)std::strlen(ref), reinterpret_cast<const uint8_t *>(alt), (uint32_t)std::strlen(alt));
+    std::printf("%llu %u %u\n", std::strtoull(pos, nullptr, 10) + t.pfx, t.d, t.m);
+    return 0;
+}
+
+static int vcf_indels(const char *path, size_t parts) {
+    const std::string text = slurp(path);
+    u64 lines_before = 0, cnt[4] = {0, 0, 0, 0};
+    std::vector<et::VcfPartAny> P;
+    for (size_t p = 0; p < parts; ++p) P.push_back(et::parse_vcf_part_any(text, et::part_begin(text, p, parts), et::part_begin(text, p + 1, parts)));
+    for (const et::VcfPartAny &part : P) {
+        if (part.bad_line) {
+            std::printf("error %llu %s\n", lines_before + part.bad_line, part.bad);
+            return 1;
+        }
+        lines_before += part.lines;
+    }
+    for (const et::VcfPartAny &part : P) {
+        for (const et::AlleleAny &a : part.alleles)
+            std::printf("allele %.*s %u %.*s %.*s %llu %u %u\n", (int)a.chrom.size(), a.chrom.data(), a.pos, (int)a.ref.size(), a.ref.data(), (int)a.alt.size(), a.alt.data(), a.x0(),
+                        a.d, a.m);
+        cnt[0] += part.other, cnt[1] += part.too_long, cnt[2] += part.same, cnt[3] += part.ins_at_1;
+    }
+    std::printf("left_out %llu %llu %llu %llu\n", cnt[0], cnt[1], cnt[2], cnt[3]);
+    return 0;
+}
+
 static int vcf(const char *path, size_t parts) {
     const std::string text = slurp(path);
     u64 lines_before = 0, not_snv = 0;
@@ -214,6 +336,8 @@ static int vcf(const char *path, size_t parts) {
 }
 
 static int run(int argc, char **argv) {
+    const bool indels = argc == 10 && std::strcmp(argv[2], "--indels") == 0;
+    if (indels) ++argv, --argc;
     if (argc != 9) return 2;
     const auto t0 = std::chrono::steady_clock::now();
     const std::string gff = slurp(argv[2]), fasta = slurp(argv[3]), variants = slurp(argv[4]);
@@ -223,7 +347,11 @@ static int run(int argc, char **argv) {
         return std::fprintf(stderr, "Error: compressed variants file is not read: decompress \"%s\" first\n", argv[4]), 1;
     const auto t1 = std::chrono::steady_clock::now();
     // the variants
-    et::VcfPart V = et::parse_vcf_part(variants, 0, variants.size());
+    et::VcfPart V;
+    et::VcfPartAny VA;
+    if (indels) VA = et::parse_vcf_part_any(variants, 0, variants.size());
+    else V = et::parse_vcf_part(variants, 0, variants.size());
+    if (indels) V.bad_line = VA.bad_line, V.bad = VA.bad;
     if (V.bad_line) return std::fprintf(stderr, "Error: variants file %s, line %llu: %s\n", argv[4], V.bad_line, V.bad), 1;
     const auto t2 = std::chrono::steady_clock::now();
     // the genome
@@ -299,6 +427,7 @@ static int run(int argc, char **argv) {
     }
     u64 n_unservable = 0, no_chrom = 0;
     for (uint32_t t = 0; t < H.n_tr; ++t) n_unservable += H.dropped[t] && !(T.flags[t] & ef::kFlagDropped);
+    if (indels) et::warn_left_out(VA.other, VA.too_long, VA.same, VA.ins_at_1);
     if (V.not_snv) std::fprintf(stderr, "[WARN] %llu alleles are not single-base substitutions and were left out\n", V.not_snv);
     if (T.orphans) std::fprintf(stderr, "[WARN] %llu features have no Parent and belong to no transcript\n", T.orphans);
     if (T.mixed) std::fprintf(stderr, "[WARN] %llu transcripts were dropped: their members lie on more than one seqid or strand\n", T.mixed);
@@ -310,6 +439,21 @@ static int run(int argc, char **argv) {
     std::vector<u64> off{0};
     std::vector<uint8_t> rms;
     std::vector<et::Allele> taken;
+    std::vector<et::AlleleAny> taken_any;
+    for (const et::AlleleAny &a : VA.alleles) {
+        if (!seqid_num.count(a.chrom)) {
+            ++no_chrom;
+            continue;
+        }
+        const auto fa = fa_of.find(a.chrom);
+        const uint32_t s = fa == fa_of.end() ? 0xFFFFFFFFu : fa->second;
+        const u64 x0 = a.x0(), lo = a.d ? x0 : x0 - 1, hi = a.d ? x0 + a.d - 1 : x0;
+        const uint8_t *rp = reinterpret_cast<const uint8_t *>(a.ref.data()) + a.pfx, *ap = reinterpret_cast<const uint8_t *>(a.alt.data()) + a.pfx;
+        H.hits_range(s, lo, hi, hit);
+        const uint8_t rm = H.ref_match_run(s, lo, hi, x0, rp, a.d);
+        for (uint32_t t : hit) recs.push_back(H.classify_any(t, (uint32_t)x0, a.d, a.m, ap, rm));
+        off.push_back(recs.size()), rms.push_back(rm), taken_any.push_back(a);
+    }
     for (const et::Allele &a : V.alleles) {
         if (!seqid_num.count(a.chrom)) {
             ++no_chrom;
@@ -325,8 +469,10 @@ static int run(int argc, char **argv) {
     const auto t5b = std::chrono::steady_clock::now();
     std::string out = et::kHeader;
     et::Summary sum;
-    const u64 n_alleles = taken.size(), n_pairs = recs.size();
-    for (u64 i = 0; i < n_alleles; ++i) et::format_allele(out, sum, taken[i], recs.data() + off[i], off[i + 1] - off[i], rms[i], T.names, T.strand);
+    et::SummaryAll sum_all;
+    const u64 n_alleles = taken.size() + taken_any.size(), n_pairs = recs.size();
+    for (u64 i = 0; i < taken.size(); ++i) et::format_allele(out, sum, taken[i], recs.data() + off[i], off[i + 1] - off[i], rms[i], T.names, T.strand);
+    for (u64 i = 0; i < taken_any.size(); ++i) et::format_allele_any(out, sum_all, taken_any[i], recs.data() + off[i], off[i + 1] - off[i], rms[i], T.names, T.strand);
     if (no_chrom) std::fprintf(stderr, "[WARN] %llu alleles lie on a seqid the index does not have and were left out\n", no_chrom);
     const auto t6 = std::chrono::steady_clock::now();
     std::ofstream o(argv[7], std::ios::binary);
@@ -335,7 +481,7 @@ static int run(int argc, char **argv) {
     bool ok = (bool)o;
     if (std::strcmp(argv[8], "-") != 0) {
         std::ofstream so(argv[8], std::ios::binary);
-        const std::string s = sum.text();
+        const std::string s = indels ? sum_all.text() : sum.text();
         so.write(s.data(), (std::streamsize)s.size());
         so.close();
         ok = ok && so;
@@ -353,9 +499,16 @@ int main(int argc, char **argv) {
         for (uint32_t c = 0; c < ef::kClasses; ++c) std::printf("%s\n", ef::class_name(c));
         return 0;
     }
+    if (mode == "--all-classes") {
+        for (uint32_t c = 0; c < ef::kClassesAll; ++c) std::printf("%s\n", ef::class_name(c));
+        return 0;
+    }
     if (mode == "--rules" && argc == 3) return rules(argv[2]);
+    if (mode == "--indel-rules" && argc == 3) return indel_rules(argv[2]);
+    if (mode == "--trim" && argc == 5) return trim(argv[2], argv[3], argv[4]);
+    if (mode == "--vcf-indels" && argc == 4) return vcf_indels(argv[2], (size_t)std::max(1, std::atoi(argv[3])));
     if (mode == "--vcf" && argc == 4) return vcf(argv[2], (size_t)std::max(1, std::atoi(argv[3])));
     if (mode == "--run") return run(argc, argv);
-    std::fprintf(stderr, "usage: effect_check --classes | --rules FILE | --vcf FILE PARTS | --run GFF FASTA VCF CDS_TYPE EXON_TYPE OUT SUMMARY\n");
+    std::fprintf(stderr, "usage: effect_check --classes | --all-classes | --rules FILE | --indel-rules FILE | --trim POS REF ALT | --vcf FILE PARTS | --vcf-indels FILE PARTS | --run [--indels] GFF FASTA VCF CDS_TYPE EXON_TYPE OUT SUMMARY\n");
     return 2;
 }
