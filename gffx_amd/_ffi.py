@@ -75,6 +75,7 @@ SIGNATURES = {
     "gffx_hip_batch_block_threads": (C.c_uint32, [vp]),
     "gffx_hip_batch_block_count": (C.c_uint32, [vp]),
     "gffx_hip_batch_block_share": (C.c_uint32, [vp]),
+    "gffx_hip_group_descriptors_fit": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int]),
     "gffx_hip_batch_filter_level": (C.c_uint32, [vp]),
     "gffx_hip_batch_wide_form": (C.c_int, [vp]),
     "gffx_hip_batches_run_n": (C.c_int, [C.POINTER(vp), C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_uint64]),

@@ -94,6 +94,7 @@ static int run_windows_pass(gffx_hip_batch *const *bs, uint32_t n, hipStream_t s
     PairArgs a{};
     a.n_subs = n;
     bool offs = false;
+    bool qdesc = !roots;  // every batch's buffers fit a descriptor each (windows_launch.hpp, launch_pairs_t)
     uint64_t nq_launch = 0;
     int others = (int)ix->busy_batches.v.load(std::memory_order_relaxed);
     for (uint32_t t = 0; t < n; ++t) {
@@ -140,6 +141,24 @@ static int run_windows_pass(gffx_hip_batch *const *bs, uint32_t n, hipStream_t s
         S.vec_ok = b->q.aos ? al(b->q.aos) : (al(b->q.chr) && al(b->q.start) && al(b->q.end));
         S.q = b->q;
         S.nq = b->nq;
+        if (!roots) {
+            // the buffers once more as ready-made descriptors (PairDescs: what a group launch's narrow instantiations read), where they fit
+            const bool pair_out = o.fids != nullptr;
+            const bool fit = pair_descs_fit(b->nq, pair_out ? o.capacity : 0, pair_out);
+            qdesc = qdesc && fit;
+            if (fit) {
+                PairDescs &d = S.d;
+                const uint32_t words = b->q.aos ? 3u : 1u;
+                const uint64_t qbytes = b->nq * 4ull * words;
+                d.q_words = words;
+                d.q0 = pair_desc_make(b->q.aos ? b->q.aos : b->q.chr, qbytes);
+                d.q1 = pair_desc_make(b->q.aos ? b->q.aos : b->q.start, qbytes);
+                d.q2 = pair_desc_make(b->q.aos ? b->q.aos : b->q.end, qbytes);
+                d.counts = pair_desc_make(o.counts, b->nq * 4ull);
+                d.fids = pair_desc_make(o.fids, pair_out ? o.capacity * 4ull : 0ull);
+                d.segbase = pair_desc_make(o.segbase, (b->nq + kWaveGroup - 1) / kWaveGroup * 8ull);
+            }
+        }
     }
     for (uint32_t t = 0; t < n; ++t) bs[t]->others = others, bs[t]->others_busy = others > 0;
     bool ml = meta_bytes(ix) <= kMetaLdsBytes;
@@ -306,7 +325,7 @@ static int run_windows_pass(gffx_hip_batch *const *bs, uint32_t n, hipStream_t s
     ProfEvent pe;
     int lrc = GFFX_OK;
     if (n == 1) prof_begin(b0, roots ? GFFX_K_WINDOWS : GFFX_K_WAVE, &pe);
-    const WindowsLaunch L{ix->device, stream, grid, threads, lds, roots, offs, pos, wide, ml, b0->mode, &a};
+    const WindowsLaunch L{ix->device, stream, grid, threads, lds, roots, offs, pos, wide, ml, b0->mode, &a, qdesc};
     lrc = lkind == kLaunchGroup ? launch_windows_kind<kLaunchGroup>(L) : lkind == kLaunchTickets ? launch_windows_kind<kLaunchTickets>(L) : launch_windows_kind<kLaunchPlain>(L);
     if (n == 1) prof_end(b0, &pe);
     if (lrc) return lrc;
@@ -371,6 +390,11 @@ static int run_windows_on(gffx_hip_batch *const *bs, uint32_t n, hipStream_t str
         return GFFX_OK;
     }
     return run_windows_pass(bs, n, stream, 3, false, alternating);
+}
+
+// (the rule run_windows_pass applies to every batch of a launch: pair_descs_fit, join_pairs_kernels.hpp)
+extern "C" int gffx_hip_group_descriptors_fit(uint64_t n_regions, uint64_t capacity_words, int has_pair_output) {
+    return pair_descs_fit(n_regions, capacity_words, has_pair_output != 0) ? 1 : 0;
 }
 
 int gffx::run_windows(gffx_hip_batch *b) { return run_windows_on(&b, 1, b->stream); }

@@ -169,6 +169,34 @@ struct WaveOut {
 // got through their share faster -- lighter rounds, a luckier CU -- take more of the tail (a static stride all the way left the
 // launch waiting for its slowest block: 10 M regions, mean block life 82 us, longest 94; tickets for EVERY round cost more than
 // they balance: a returning device atomic in front of the taker's gathers, every round).
+// A launch that serves a GROUP reads its buffers through descriptors the HOST made (template argument QDESC of k_join_pairs;
+// DESIGN.md 4.0i): four dwords as the hardware reads them -- base, flags 0x00020000, num_records = the WHOLE buffer's bytes --, so a
+// use site is one wide scalar load with no arithmetic and no branch behind it, the round's or the run's position goes into the
+// vector offset, and the range check alone decides what is read or written: rows beyond the batch, words beyond the capacity, a
+// buffer the pass does not have (num_records 0).  kWinNoLine is the offset of a lane that must not write: every descriptor's bytes
+// are at most kPairDescMaxBytes = kWinNoLine, or the host takes the instantiation that builds its descriptors per round
+// (pair_descs_fit).
+struct PairDesc {
+    uint32_t w[4];
+};
+struct alignas(64) PairDescs {
+    PairDesc q0, q1, q2;  // the three region loads of pair_request_round: the rows' base three times, or chr / start / end (nq x 4 x q_words bytes)
+    PairDesc counts;      // nq x 4 bytes
+    PairDesc fids;        // capacity x 4 bytes (a pass without pair output: empty)
+    PairDesc segbase;     // ceil(nq / kWaveGroup) x 8 bytes (without GFFX_OUT_SEGBASE: empty)
+    uint32_t q_words;     // words per region in q0 .. q2: 3 (rows) or 1 (columns)
+    uint32_t pad_[7];
+};
+constexpr unsigned long long kPairDescMaxBytes = 0x80000000ull;
+__host__ __device__ inline PairDesc pair_desc_make(const void *base, unsigned long long bytes) {
+    const unsigned long long p = (unsigned long long)(uintptr_t)base;
+    return PairDesc{{(uint32_t)p, (uint32_t)(p >> 32) & 0xFFFFu, base ? (uint32_t)bytes : 0u, 0x00020000u}};
+}
+// whether a batch of nq regions whose pair output holds `capacity` words (pair_out: it has one) can be served through PairDescs
+__host__ __device__ inline bool pair_descs_fit(unsigned long long nq, unsigned long long capacity, bool pair_out) {
+    return nq <= kPairDescMaxBytes / 12u && (!pair_out || capacity <= kPairDescMaxBytes / 4u);
+}
+
 struct PairSub {
     QueryView q;
     unsigned long long nq;
@@ -178,6 +206,7 @@ struct PairSub {
     unsigned long long n_static;  // (>= n_blocks when the batch has that many rounds: a block's first round is always its own number)
     uint32_t *ticket;       // zero on entry
     uint32_t *ticket_next;  // the other ticket word: zeroed here for the batch's next pass
+    PairDescs d;            // (pair passes of a group launch; filled for every launch)
 };
 
 // The kernels' one argument.  The main path reads `pv`, the block's `sub` record and the scalars; `ix` is never touched by value: the rare
@@ -435,6 +464,53 @@ template <uint32_t X, uint32_t END>
 struct PairFlush<X, END, true> {
     static __device__ __forceinline__ void run(const uint32_t *, __amdgpu_buffer_rsrc_t, uint32_t, uint32_t) {}
 };
+
+// The same against the descriptor of the WHOLE pair buffer (QDESC: PairDescs::fids), the run's place in the vector offset v4 =
+// 4 x (seg + lane): the range check drops the words at or beyond the capacity one by one, but NOT the lanes past the run.  So the
+// trips that lie inside the run store as they are (one uniform compare per 256 words, as above), and the run's last 1 .. 255 words
+// leave in ONE trip of their own whose stores pick, lane by lane, the offset beyond every buffer (kWinNoLine) for the lanes past
+// the run: a compare and a select in front of each store, no branch around it.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t pair_desc_rsrc(const PairDesc &d) {
+    return *reinterpret_cast<const __amdgpu_buffer_rsrc_t *>(&d);
+}
+template <uint32_t X, uint32_t END, bool DONE = (X + 256u > END)>
+struct PairFlushFull {
+    static __device__ __forceinline__ void run(const uint32_t *st /* strip + lane */, __amdgpu_buffer_rsrc_t rf, uint32_t v4, uint32_t total) {
+        if (X + 256u <= total) {
+            const uint32_t a = st[X], b = st[X + 64], c = st[X + 128], d = st[X + 192];
+            __builtin_amdgcn_raw_buffer_store_b32(a, rf, v4 + X * 4u, 0, 2 /* nt */);
+            __builtin_amdgcn_raw_buffer_store_b32(b, rf, v4 + (X + 64) * 4u, 0, 2);
+            __builtin_amdgcn_raw_buffer_store_b32(c, rf, v4 + (X + 128) * 4u, 0, 2);
+            __builtin_amdgcn_raw_buffer_store_b32(d, rf, v4 + (X + 192) * 4u, 0, 2);
+            PairFlushFull<X + 256, END>::run(st, rf, v4, total);
+        }
+    }
+};
+template <uint32_t X, uint32_t END>
+struct PairFlushFull<X, END, true> {
+    static __device__ __forceinline__ void run(const uint32_t *, __amdgpu_buffer_rsrc_t, uint32_t, uint32_t) {}
+};
+// (st: the wave's strip + lane; the words a lane past the run reads from LDS -- the next strip's, the next wave's -- are not stored)
+__device__ __forceinline__ void pair_flush_rest(const uint32_t *st, __amdgpu_buffer_rsrc_t rf, uint32_t v4, uint32_t lane, uint32_t total) {
+    const uint32_t x0 = total & ~255u;  // (uniform)
+    if (total != x0) {
+        const uint32_t *s = st + x0;
+        const uint32_t a = s[0], b = s[64], c = s[128], d = s[192];
+        // (the four limits as opaque scalars: compared as `lane + 64 j < rest` the left-hand sides are loop-invariant vector values, a
+        //  register each)
+        const int ln = (int)lane;
+        int l0 = (int)(total - x0), l1 = l0 - 64, l2 = l0 - 128, l3 = l0 - 192;
+        asm volatile("" : "+s"(l0), "+s"(l1), "+s"(l2), "+s"(l3));
+        const uint32_t v = v4 + 4u * x0;
+        // (each select made before its word's place is added: folded into the select the four "beyond" offsets are four registers)
+        uint32_t o0 = ln < l0 ? v : kWinNoLine, o1 = ln < l1 ? v : kWinNoLine, o2 = ln < l2 ? v : kWinNoLine, o3 = ln < l3 ? v : kWinNoLine;
+        asm volatile("" : "+v"(o0), "+v"(o1), "+v"(o2), "+v"(o3));
+        __builtin_amdgcn_raw_buffer_store_b32(a, rf, o0, 0, 2 /* nt */);
+        __builtin_amdgcn_raw_buffer_store_b32(b, rf, o1 + 256u, 0, 2);
+        __builtin_amdgcn_raw_buffer_store_b32(c, rf, o2 + 512u, 0, 2);
+        __builtin_amdgcn_raw_buffer_store_b32(d, rf, o3 + 768u, 0, 2);
+    }
+}
 
 // The rare paths.  Sweeps (regions wider than wmax, qs >= qe rows, dense windows, seqids without windows) as a FUNCTION
 // CALL: inlined -- twice, with the bin search and the skip-link walk inside -- that code was most of the round loop's body;
@@ -784,6 +860,18 @@ __device__ __forceinline__ void pair_request_round(const QueryView &q, unsigned 
     w.b = __builtin_amdgcn_raw_buffer_load_b128(r1, o + (aos ? 16u : 0u), 0, kNt);
     w.c = __builtin_amdgcn_raw_buffer_load_b128(r2, o + (aos ? 32u : 0u), 0, kNt);
 }
+// ... through the host's descriptors of the whole batch (QDESC): the round's position in the vector offset; rows beyond the batch
+// read zeros, word by word (the partial last round is pair_take_round's, as before).  nq x 12 <= kPairDescMaxBytes: the offsets of
+// the rounds a block may ask for beyond the batch (fewer than a grid's worth) do not wrap.
+template <uint32_t kChunk>
+__device__ __forceinline__ void pair_request_round(const PairDescs &d, uint32_t r, uint32_t t4, PairRaw &w) {
+    constexpr int kNt = 2;  // nt: streamed once
+    const uint32_t words = d.q_words;
+    const uint32_t o = 4u * words * r * kChunk /* (uniform) */ + __umul24(t4, 4u * words);
+    w.a = __builtin_amdgcn_raw_buffer_load_b128(pair_desc_rsrc(d.q0), o, 0, kNt);
+    w.b = __builtin_amdgcn_raw_buffer_load_b128(pair_desc_rsrc(d.q1), o + (words == 3u ? 16u : 0u), 0, kNt);
+    w.c = __builtin_amdgcn_raw_buffer_load_b128(pair_desc_rsrc(d.q2), o + (words == 3u ? 32u : 0u), 0, kNt);
+}
 template <uint32_t kChunk>
 __device__ __forceinline__ void pair_take_round(const QueryView &q, unsigned long long nq, int vec_ok, uint32_t n_chr, unsigned long long r, uint32_t t4,
                                                 const PairRaw &w, uint32_t (&qc)[4], uint32_t (&qs)[4], uint32_t (&qe)[4], bool &bad) {
@@ -828,8 +916,11 @@ __device__ __forceinline__ void pair_take_round(const QueryView &q, unsigned lon
 // QAHEAD: the next round's regions are requested in one step and unpacked in another (pair_request_round / pair_take_round): in flight
 //      under the scan, the parking, the arrival and the loop's top instead of waited for where they are requested.  The narrow form
 //      without per-region offsets (what bench.py times); the other instantiations keep pair_load_round.
-template <int MODE, bool META_LDS, int T, bool OFFS, bool POS, bool WIDE = false, int KIND = kLaunchPlain, bool QAHEAD = false>
+// QDESC: (with QAHEAD) the regions, the counts, the pair buffer and the segment bases through the host's descriptors of the whole
+//      buffers (PairDescs): no descriptor is built in the round, no pointer tested, no capacity compared.
+template <int MODE, bool META_LDS, int T, bool OFFS, bool POS, bool WIDE = false, int KIND = kLaunchPlain, bool QAHEAD = false, bool QDESC = false>
 __global__ __launch_bounds__(T, 4) void k_join_pairs(PairArgs A) {
+    static_assert(!QDESC || (QAHEAD && !OFFS && !WIDE && KIND == kLaunchGroup), "QDESC: the group launch's narrow form without per-region offsets");
     constexpr bool DYN = KIND == kLaunchGroup, TICK = KIND == kLaunchTickets;
     constexpr bool CONT = WIDE && MODE == GFFX_MODE_CONTAINED;        // a wide lane keeps the roots of its run that end inside the region (inverted: beyond it)
     constexpr bool CREG = WIDE && MODE == GFFX_MODE_CONTAINS_REGION;  // ... the roots over qs that reach the region's end (inverted: that do not, and its run)
@@ -874,7 +965,12 @@ __global__ __launch_bounds__(T, 4) void k_join_pairs(PairArgs A) {
     bool bad = false;              // a region's seqid is out of range
     auto load_round = [&](unsigned long long r) { pair_load_round<kChunk>(q, nq, S.vec_ok, n_chr, r, t4, qc, qs, qe, bad); };
     PairRaw rr;  // (QAHEAD) the requested round, as loaded
-    auto request_round = [&](unsigned long long r) { pair_request_round<kChunk>(q, nq, r, t4, rr); };
+    auto request_round = [&](unsigned long long r) {
+        if constexpr (QDESC)
+            pair_request_round<kChunk>(S.d, (uint32_t)r, t4, rr);
+        else
+            pair_request_round<kChunk>(q, nq, r, t4, rr);
+    };
     auto take_round = [&](unsigned long long r) { pair_take_round<kChunk>(q, nq, S.vec_ok, n_chr, r, t4, rr, qc, qs, qe, bad); };
     const unsigned long long n_rounds = (nq + kChunk - 1) / kChunk;
     if (lb < n_rounds) {  // in flight while the tables are staged
@@ -980,7 +1076,15 @@ __global__ __launch_bounds__(T, 4) void k_join_pairs(PairArgs A) {
     };
     auto group_base = [&](unsigned long long round, unsigned long long seg) {  // GFFX_OUT_SEGBASE: one word per wave and round
         const unsigned long long g = round * kWaves + (uint32_t)wave;
-        if (out.segbase && lane == 0 && g * kWaveGroup < nq) out.segbase[g] = seg;
+        if constexpr (QDESC) {
+            // ONE store on every path, from lane 0: the range check drops a group beyond the batch, and every group of a pass without
+            // segment bases (an empty descriptor)
+            gffx_v2u v;
+            v.x = (uint32_t)seg, v.y = (uint32_t)(seg >> 32);
+            __builtin_amdgcn_raw_buffer_store_b64(v, pair_desc_rsrc(S.d.segbase), lane == 0 ? 8u * (uint32_t)g : kWinNoLine, 0, 0);
+        } else {
+            if (out.segbase && lane == 0 && g * kWaveGroup < nq) out.segbase[g] = seg;
+        }
     };
     // a round's segment base is posted by the wave that issued its atomic: as soon as that wave has its next round's
     // gathers in flight (the atomic's answer is there by then) -- a full round before anybody has to have it
@@ -997,7 +1101,22 @@ __global__ __launch_bounds__(T, 4) void k_join_pairs(PairArgs A) {
         const uint32_t slot = p_slot[i];
         const unsigned long long seg = await_base(slot, p_seq[i]) + p_off[i];
         group_base(p_round[i], seg);
-        if (out.fids) {
+        if constexpr (QDESC) {
+            // the whole pair buffer's descriptor, the run's place in the vector offset: words at or beyond the capacity are dropped one
+            // by one, a pass without pair output has an empty descriptor (PairFlushFull, pair_flush_rest).  A run that starts beyond what a 32-bit
+            // byte offset reaches (an overfull pass: the cursor counts on) is beyond every capacity.
+            const uint32_t total = p_total[i];  // (uniform)
+            const uint32_t *st = s_stage + p_strip[i] * kStage + lane;
+            // (uniform; the two halves tested as 32-bit scalars: as ONE 64-bit compare it is a vector instruction against a register pair)
+            uint32_t seg_far = (uint32_t)(seg >> 32) | ((uint32_t)seg >> 29);
+            asm volatile("" : "+s"(seg_far));
+            const uint32_t seg4 = seg_far ? kWinNoLine : 4u * (uint32_t)seg;
+            uint32_t v4 = seg4 + lane4;
+            asm volatile("" : "+v"(v4));  // (made here, as below)
+            const __amdgpu_buffer_rsrc_t rf = pair_desc_rsrc(S.d.fids);
+            PairFlushFull<0, D * kStage>::run(st, rf, v4, total);
+            pair_flush_rest(st, rf, v4, (uint32_t)lane, total);
+        } else if (out.fids) {
             const uint32_t total = p_total[i];  // (uniform)
             const uint32_t *st = s_stage + p_strip[i] * kStage + lane;
             uint32_t *dst = out.fids + seg;  // (uniform)
@@ -1356,12 +1475,16 @@ __global__ __launch_bounds__(T, 4) void k_join_pairs(PairArgs A) {
             // are dropped by the range check).  A conditional store here would make "no memory operation was issued after the
             // region prefetch" a possible path, and the wait for the prefetched regions at the top of the next round would
             // become s_waitcnt vmcnt(0): a full drain of this round's stores and of the reservation atomic, every round.
-            const unsigned long long left = nq - base;  // (base < nq inside the loop)
-            const uint32_t rows = (uint32_t)min(left, (unsigned long long)kChunk);
             gffx_v4u cv;
             cv.x = cnt[0], cv.y = cnt[1], cv.z = cnt[2], cv.w = cnt[3];
-            __builtin_amdgcn_raw_buffer_store_b128(cv, __builtin_amdgcn_make_buffer_rsrc(out.counts + base, 0, rows * 4u, 0x00020000),
-                                                   4u * t4, 0, 2 /* nt */);
+            if constexpr (QDESC) {  // (the batch's descriptor, the round's position in the offset)
+                __builtin_amdgcn_raw_buffer_store_b128(cv, pair_desc_rsrc(S.d.counts), 4u * ((uint32_t)base + t4), 0, 2 /* nt */);
+            } else {  // (a descriptor of exactly the round's rows)
+                const unsigned long long left = nq - base;  // (base < nq inside the loop)
+                const uint32_t rows = (uint32_t)min(left, (unsigned long long)kChunk);
+                __builtin_amdgcn_raw_buffer_store_b128(cv, __builtin_amdgcn_make_buffer_rsrc(out.counts + base, 0, rows * 4u, 0x00020000),
+                                                       4u * t4, 0, 2 /* nt */);
+            }
         };
         if constexpr (!QAHEAD) store_counts();
         // ---- the oldest round in flight leaves (its segment base was posted a round ago), THEN the next round's regions are

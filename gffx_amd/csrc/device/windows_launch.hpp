@@ -1,8 +1,10 @@
 // windows_launch.hpp -- the window kernels' launch dispatch: run-time {mode, seqid records in LDS, block width, offsets, positions,
 // form} -> template arguments of k_join_pairs / k_join_roots (join_pairs_kernels.hpp), per KIND of launch (kLaunchPlain /
-// kLaunchGroup / kLaunchTickets).  The 64 + 16 instantiations of ONE kind are one translation unit (engine_windows_plain.hip,
-// _group.hip, _tickets.hip define GFFX_WINDOWS_LAUNCH_KIND and include this file: `make -j` compiles them side by side -- one unit
-// with all 240 took five minutes); engine_windows.hip calls launch_windows_kind<KIND>.
+// kLaunchGroup / kLaunchTickets).  The 96 + 24 instantiations of ONE kind (k_join_pairs: 3 modes x 2 x 2 widths x offsets x
+// positions x form; k_join_roots: 3 x 2 x 2 x form) are one translation unit (engine_windows_plain.hip, _group.hip, _tickets.hip
+// define GFFX_WINDOWS_LAUNCH_KIND and include this file: `make -j` compiles them side by side -- one unit with all of them took
+// five minutes); the group unit holds 24 k_join_pairs more, the QDESC set of its QAHEAD instantiations (launch_pairs_t below);
+// engine_windows.hip calls launch_windows_kind<KIND>.
 #pragma once
 #include "engine_private.hpp"
 #include "join_pairs_kernels.hpp"
@@ -16,6 +18,7 @@ struct WindowsLaunch {
     bool roots, offs, pos, wide, ml;
     int mode;
     const PairArgs *a;
+    bool qdesc;  // the group launch's instantiations that read the records' descriptors (launch_pairs_t)
 };
 // Beyond the default 64 KB of dynamic LDS a kernel has to opt in, per function and per device (engine_windows.hip)
 int lds_opt_in(const void *func, int device, uint32_t lds, uint32_t max_lds);
@@ -29,6 +32,21 @@ static inline int launch_pairs_t(const WindowsLaunch &L) {
     // regions requested a round ahead and unpacked at the round's top (join_pairs_kernels.hpp): the launches that serve a GROUP of
     // batches, narrow form, no per-region offsets -- where it was measured; a lone batch's launches (plain, tickets) keep pair_load_round
     constexpr bool QAHEAD = !WIDE && !OFFS && KIND == kLaunchGroup;
+    // ... and read their buffers through the descriptors the host put into the batches' records (PairDescs).  THE RULE
+    // (WindowsLaunch::qdesc, set by run_windows_pass): only when every descriptor of every batch of the launch spans at most 2^31
+    // bytes -- 12 bytes per region, 4 per word of the pair buffer's capacity (pair_descs_fit) --, so that a position is a 32-bit byte
+    // offset and kWinNoLine lies beyond every buffer; a larger batch takes the second set of the same instantiations, which builds
+    // its descriptors per round as every other launch does.
+    constexpr bool QDESC = QAHEAD;
+    if constexpr (QDESC) {
+        if (L.qdesc) {
+            const int rc = lds_opt_in(reinterpret_cast<const void *>(&k_join_pairs<MODE, ML, T, OFFS, POS, WIDE, KIND, QAHEAD, true>), L.device, L.lds,
+                                      T == 1024 ? 2 * kWinMaxLds : kWinMaxLds);
+            if (rc) return rc;
+            hipLaunchKernelGGL((k_join_pairs<MODE, ML, T, OFFS, POS, WIDE, KIND, QAHEAD, true>), dim3(L.grid), dim3(T), L.lds, L.stream, *L.a);
+            return GFFX_OK;
+        }
+    }
     const int rc = lds_opt_in(reinterpret_cast<const void *>(&k_join_pairs<MODE, ML, T, OFFS, POS, WIDE, KIND, QAHEAD>), L.device, L.lds,
                               T == 1024 ? 2 * kWinMaxLds : kWinMaxLds);
     if (rc) return rc;

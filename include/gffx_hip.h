@@ -361,6 +361,14 @@ uint32_t gffx_hip_batch_block_count(const gffx_hip_batch *);
 /* The batch's own blocks of that launch: the whole grid for a launch that serves one batch; for a launch that serves a group of
  * batches (gffx_hip_batches_run_n) _block_count is the launch's grid and this the batch's share of it. */
 uint32_t gffx_hip_batch_block_share(const gffx_hip_batch *);
+/* A launch that serves a group reads every batch's buffers through buffer descriptors the host put into the batch's record -- the
+ * regions, the counts, the pair buffer, the segment bases, each spanning the WHOLE buffer; a round's or a run's place is a 32-bit byte
+ * offset and the hardware's range check drops what lies beyond the batch or the capacity.  The rule: only when every descriptor of
+ * every batch of the launch spans at most 2^31 bytes (12 bytes per region: n_regions <= 2^31 / 12; 4 per word of the pair buffer:
+ * capacity_words <= 2^29 -- ignored for a pass without pair output, has_pair_output 0), so that the offset 2^31 lies beyond every
+ * buffer; otherwise the launch runs the instantiations that build a descriptor per round, as a lone batch's launches do.  Results
+ * are the same either way.  Returns 1 when a batch of that size takes the descriptors, else 0 (a pure function: no device). */
+int gffx_hip_group_descriptors_fit(uint64_t n_regions, uint64_t capacity_words, int has_pair_output);
 /* Coverage filter the batch's last windows-strategy launch staged in LDS: 0 none (the mixed form, or nothing fitted), 1 the coarse
  * one (GFFX_HIP_WIN_FILTER_KB), 2 the fine one (GFFX_HIP_WIN_FILTER_FINE_KB).  A launch takes the fine one where it fits beside its
  * other tables and strips and its blocks run four rounds or more (about 4 M regions: the larger bitmap is staged once per block);
